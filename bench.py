@@ -6,12 +6,16 @@ B=32 clips per GPU to T=1024 tokens (+ the all-gather of ids when N>1), inputs r
 Workload = BASELINE.json configs[1]: 6+6 layers, d_model=512, H=8, dff=1024, max_sequence_chord=1024,
 300-frame synthetic video features (F=1287), random-init procedural weights.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 N>1: one rank per GPU — either started by `python -m torch.distributed.run … bench.py --gpus N …` (the ranks read
 RANK / LOCAL_RANK / WORLD_SIZE), or, when no such environment is present, by this script itself: the parent starts the
 N ranks as child processes before anything touches a GPU and relays rank 0's line.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (attn_decode_kernel<64>, the K/V-streaming
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline; `--dump-outputs DIR`
+writes the chord ids of the last timed step to DIR/chord_ids.npy (float32; inputs and weights are seeded, so two builds can be
+compared id for id).  `--full` (one rank) adds the legs below, each a run of its own after the timed steps.
+
+`roofline` is for the dominant kernel (attn_decode_kernel<64>, the K/V-streaming
 self-attention of the decode step): algorithmic fp32 K/V bytes / the kernel's launch duration inside the captured step
 graph, measured with HIP events on the launch stream; it also carries the cross-attention, the skinny GEMMs, the
 step-level figure (`whole_step`, the honest headline of the decode path) and `prefill` = the cross-attention
@@ -39,8 +43,10 @@ def parse_args():
     ap.add_argument("--seq", type=int, default=1024, help="target_seq_length = max_sequence_chord")
     ap.add_argument("--layers", type=int, default=6)
     ap.add_argument("--d_model", type=int, default=512)
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--no_roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's chord ids to DIR/chord_ids.npy")
+    ap.add_argument("--full", action="store_true", help="also the roofline, v2_lockstep and cpu_baseline legs")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: leave out the cpu_baseline leg")
+    ap.add_argument("--no_roofline", action="store_true", help="with --full: leave out the roofline and v2_lockstep legs")
     return ap.parse_args()
 
 
@@ -464,6 +470,17 @@ def rehearsal(args, rank, world):
     torch.distributed.destroy_process_group()
 
 
+def dump_outputs(path, ids, budget=64 << 20):
+    """What the timed path hands its caller: the (clips, T) chord ids of the last step, as float32 (exact: ids < 2^24).  Above the
+    budget, a fixed, seeded sample of whole clips."""
+    ids = ids.cpu().numpy()
+    cap = max(budget // (4 * ids.shape[1]), 1)
+    if ids.shape[0] > cap:
+        ids = ids[np.sort(np.random.RandomState(0).choice(ids.shape[0], cap, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "chord_ids.npy"), ids.astype(np.float32))
+
+
 def main():
     args = parse_args()
 
@@ -522,11 +539,13 @@ def main():
                                "feedback-greedy (G2) generate incl. video encode" + (" + all_gather of ids" if world > 1 else ""),
                    "global_batch": world * B, "seq_len": T, "parallelism": f"dp{world}"},
     }
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
+    full = args.full and rank == 0 and world == 1
+    if full and not args.no_roofline:
         result["roofline"] = roofline(model, f, (pr, prr, pra), B, T, cfg, headline_generate_ms=1e3 * elapsed / args.steps)
-    if rank == 0 and world == 1 and not args.no_roofline:
         result["v2_lockstep"] = v2_lockstep_leg(device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(cfg, sd, T)
     if rank == 0:
         print(json.dumps(result))

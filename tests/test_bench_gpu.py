@@ -1,10 +1,12 @@
-"""bench.py end to end on the GPU box at a miniature configuration: the single-rank line with its roofline / cpu_baseline
-objects, and the driver's N > 1 form (the script starts its own ranks) with two ranks sharing the one GPU over gloo."""
+"""bench.py end to end on the GPU box at a miniature configuration: the plain line and its dumped outputs, the --full line with its
+roofline / cpu_baseline objects, and the driver's N > 1 form (the script starts its own ranks) with two ranks sharing the one GPU
+over gloo."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,8 +25,17 @@ def run_bench(extra, env_extra=None):
     return json.loads(lines[0])
 
 
+def test_bench_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    rec = run_bench(["--dump-outputs", str(tmp_path)])
+    assert rec["n_gpus"] == 1 and rec["steps"] == 1 and rec["value"] > 0 and rec["ms_per_step"] > 0
+    assert not {"roofline", "v2_lockstep", "cpu_baseline"} & set(rec)
+    ids = np.load(tmp_path / "chord_ids.npy")
+    assert ids.dtype == np.float32 and ids.shape == (3, 48) and np.array_equal(ids, np.round(ids))
+    assert ids.min() >= 0 and ids.max() < 159 and (ids[:, 0] == ids[0, 0]).all()       # one primer chord shared by the clips
+
+
 def test_bench_single_rank_line_has_roofline_and_cpu_baseline():
-    rec = run_bench([])
+    rec = run_bench(["--full"])
     assert rec["n_gpus"] == 1 and rec["value"] > 0 and rec["unit"] == "chord-tokens/s" and rec["dtype"] == "f32"
     r = rec["roofline"]
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):

@@ -220,3 +220,19 @@ def test_v2_builds_three_shallow_layers_whatever_n_layers_says():
     with pytest.raises(IndexError):
         VideoMusicTransformer_V3(version_name="3.1", n_layers=2, num_heads=4, d_model=128, dim_feedforward=256,
                                  total_vf_dim=synthetic.total_vf_dim(1))
+
+
+def test_bench_dump_outputs_keeps_ids_exact_and_samples_a_fixed_set_of_clips(tmp_path):
+    """bench.py --dump-outputs: the last step's (clips, T) ids as float32; above the size budget, the same seeded sample of whole
+    clips, in clip order, every run."""
+    import bench
+    ids = torch.arange(40 * 16).view(40, 16)
+    bench.dump_outputs(str(tmp_path / "all"), ids)
+    got = np.load(tmp_path / "all" / "chord_ids.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, ids.numpy())
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), ids, budget=4 * 16 * 10)
+    a, b = (np.load(tmp_path / d / "chord_ids.npy") for d in ("a", "b"))
+    assert a.shape == (10, 16) and np.array_equal(a, b)
+    rows = a[:, 0].astype(np.int64) // 16
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, ids.numpy()[rows])

@@ -213,14 +213,14 @@ def test_generate_cli_reads_feature_files_and_writes_lab(tmp_path):
 
 
 def test_bench_line_contract(tmp_path):
-    """bench.py prints ONE JSON line with the driver's keys, the roofline object and the cpu_baseline object (small config)."""
+    """bench.py --full prints ONE JSON line with the driver's keys, the roofline object and the cpu_baseline object (small config)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--seq", "48", "--batch", "3",
-                          "--layers", "2", "--d_model", "128"], capture_output=True, text=True, timeout=600)
+                          "--layers", "2", "--d_model", "128", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1

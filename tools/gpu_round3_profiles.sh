@@ -3,8 +3,8 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/r03; export TMPDIR=/tmp
 O=gpurun_out/r03
-python bench.py > $O/r03_bench_line_unprofiled.json 2> $O/bench_final.err; echo "bench rc=$?"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o b -- python3 bench.py --steps 3 --no_cpu_baseline > $O/r03_bench_line_under_rocprofv3.json 2> $O/bench_under_rocprof.err; echo "rocprof bench rc=$?"
+python bench.py --full > $O/r03_bench_line_unprofiled.json 2> $O/bench_final.err; echo "bench rc=$?"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o b -- python3 bench.py --steps 3 --full --no_cpu_baseline > $O/r03_bench_line_under_rocprofv3.json 2> $O/bench_under_rocprof.err; echo "rocprof bench rc=$?"
 cp $(find $O/prof_bench -name "*kernel_stats.csv" | head -1) $O/r03_bench_kernel_stats.csv
 python tools/trace_by_grid.py $O/prof_bench $O/r03_bench_by_grid.json > /dev/null; rm -rf $O/prof_bench
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_fwd -o f -- python3 tools/bench_forward.py > $O/forward_under_rocprof.json 2> $O/forward_under_rocprof.err; echo "rocprof fwd rc=$?"
