@@ -314,20 +314,23 @@ def v2_attention(xq, xkv, sd, prefix, H, cache, causal):
     return linear(o, sd[prefix + "out_proj.weight"], sd[prefix + "out_proj.bias"]).view(L, B, E)
 
 
-def v2_ff(x, sd, prefix):
+def v2_ff(x, sd, prefix, collect=None):
     """GLUExpert for the three shallow layers, SharedMoELayer(6 experts, top-2) for the deep ones
-    (model/video_music_transformer.py:384-416)."""
+    (model/video_music_transformer.py:384-416).  ``collect`` (list): each mixture layer appends its gate logits (..., n_experts)."""
     if prefix + "linear1.weight" in sd:
         return glu_expert(x, sd, prefix)
     sub = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
     n_exp = sub["gate.weight"].shape[0]
+    if collect is not None:
+        collect.append(linear(x, sub["gate.weight"], sub.get("gate.bias")))
     return moe_forward(x, sub, n_exp, k=2, shared=True)
 
 
-def forward_v2(sd, H, x_root, x_attr, sem, key, scene_off, motion, emotion, max_seq_video=300, mask=True, drop_keep=None):
+def forward_v2(sd, H, x_root, x_attr, sem, key, scene_off, motion, emotion, max_seq_video=300, mask=True, drop_keep=None, collect=None):
     """VideoMusicTransformer_V2.forward, version '2.2', chord_embed=False (:427-516): no additive positional
     encoding, RoPE inside every attention, post-norm layers (custom_transformer.py:1228-1240, 1260-1276).  ``mask=False``:
-    tgt_mask=None (:440-443).  ``drop_keep`` (B, S) in {0, 1}: the dropTokenRate mask ``torch.rand(B, S) > rate`` (:488-492)."""
+    tgt_mask=None (:440-443).  ``drop_keep`` (B, S) in {0, 1}: the dropTokenRate mask ``torch.rand(B, S) > rate`` (:488-492).
+    ``collect`` (list): the gate logits of every mixture layer, encoder layers first, each seq-first (L, B, n_experts)."""
     d = sd["Wout.weight"].shape[1]
     cache = rope_cache(d, max_seq_video).to(sd["Wout.weight"].dtype)
     x = sd["embedding_root.weight"][x_root] + sd["embedding_attr.weight"][x_attr]
@@ -347,14 +350,14 @@ def forward_v2(sd, H, x_root, x_attr, sem, key, scene_off, motion, emotion, max_
     for i in range(n_layers_of(sd, "encoder")):
         p = f"transformer.encoder.layers.{i}."
         src = layer_norm(src + v2_attention(src, src, sd, p + "self_attn.", H, cache, False), sd[p + "norm1.weight"], sd[p + "norm1.bias"])
-        src = layer_norm(src + v2_ff(src, sd, p + "ff."), sd[p + "norm2.weight"], sd[p + "norm2.bias"])
+        src = layer_norm(src + v2_ff(src, sd, p + "ff.", collect), sd[p + "norm2.weight"], sd[p + "norm2.bias"])
     memory = layer_norm(src, sd["transformer.encoder.norm.weight"], sd["transformer.encoder.norm.bias"])
     t = xf
     for i in range(n_layers_of(sd, "decoder")):
         p = f"transformer.decoder.layers.{i}."
         t = layer_norm(t + v2_attention(t, t, sd, p + "self_attn.", H, cache, mask is True), sd[p + "norm1.weight"], sd[p + "norm1.bias"])
         t = layer_norm(t + v2_attention(t, memory, sd, p + "cross_attn.", H, cache, False), sd[p + "norm2.weight"], sd[p + "norm2.bias"])
-        t = layer_norm(t + v2_ff(t, sd, p + "ff."), sd[p + "norm3.weight"], sd[p + "norm3.bias"])
+        t = layer_norm(t + v2_ff(t, sd, p + "ff.", collect), sd[p + "norm3.weight"], sd[p + "norm3.bias"])
     t = layer_norm(t, sd["transformer.decoder.norm.weight"], sd["transformer.decoder.norm.bias"])
     return linear(t.permute(1, 0, 2), sd["Wout.weight"], sd["Wout.bias"])
 

@@ -147,7 +147,7 @@ def run_case(i, rs):
             fails.append("decode_vs_forward")
     # the Categorical draw done on the device: every id must be the inverse CDF of the reference's decision distribution at its uniform
     if T > P and mcc >= 1:
-        from tests.test_model_gpu import _check_draws
+        from tests.helpers import check_draws as _check_draws
         u = torch.from_numpy(rs.rand(T, B).astype(np.float32))
         with torch.no_grad():
             tk, lgc = m.generate_batch(f["semantic"], f["key"], f["scene_offset"], f["motion"], f["emotion"], pb(0), pb(1), pb(2),

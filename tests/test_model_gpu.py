@@ -9,6 +9,7 @@ from video2music_amd import synthetic
 from video2music_amd.model.video_music_transformer import VideoMusicTransformer
 from video2music_amd.utilities import constants as C
 from tests.helpers import CFG1, CFG2, synthetic_sd, feats_t
+from tests.helpers import check_draws as _check_draws
 
 pytestmark = pytest.mark.gpu
 LOGIT_TOL = 1e-3        # BASELINE.json: logits within 1e-3 fp32
@@ -458,24 +459,6 @@ def test_scalar_motion_feature_width():
     with torch.no_grad():
         got = m(root, root.cuda(), attr.cuda(), f["semantic"], f["key"], f["scene_offset"], f["motion"], f["emotion"])
     assert (got.cpu() - ref).abs().max().item() < LOGIT_TOL
-
-
-def _check_draws(toks, logits, u, P, max_conseq_N, max_conseq_chord):
-    """Every generated id is the inverse-CDF draw of the reference's decision distribution (:1085-1105) at its uniform:
-    recomputed in fp64 from the returned logits, with a band for fp32 rounding of the device's cumulative sums."""
-    toks, logits, u = toks.cpu().numpy(), logits.cpu().double(), u.cpu().double().numpy()
-    B, T = toks.shape
-    for b in range(B):
-        for cur in range(P, T):
-            pr = torch.softmax(logits[cur - 1, b], -1)[:C.CHORD_END].numpy().copy()
-            if max_conseq_N == 0:
-                pr[0] = 0.0
-            if cur >= max_conseq_chord and all(toks[b, cur - 1] == toks[b, cur - 1 - k] for k in range(1, max_conseq_chord)):
-                pr[toks[b, cur - 1]] = 0.0
-            cdf = np.cumsum(pr)
-            tok, target = int(toks[b, cur]), u[cur - 1, b] * cdf[-1]
-            assert pr[tok] > 0.0, (b, cur, tok)
-            assert (cdf[tok] - pr[tok]) - 1e-5 <= target <= cdf[tok] + 1e-5, (b, cur, tok, target, cdf[tok] - pr[tok], cdf[tok])
 
 
 @pytest.mark.parametrize("cfg,B,T,mcn,mcc", [(CFG1, 3, 48, 0, 2), (CFG1, 2, 40, 1, 3), (CFG2, 5, 96, 0, 2)])
