@@ -124,6 +124,9 @@ int32_t amt_generate_run(amt_handle* h, int32_t n_steps, float* logits_out, void
  *   31: model/rpr.py:59-69 operator by operator) -- the chain that shapes outside the fold's range take anyway.
  *   "fuse_sampling_head" = 0 (any time): every step of a captured decode graph ends with its own sampling-head launch (31 launches
  *   per step); 1, the default: inside a graph the head rides in the prologue of the next step's first self-attention (30).
+ *   "short_context_attn" = 0 (any time): every captured decode graph uses the long-context self-attention kernels; 1, the default:
+ *   a graph whose last step still has at most one K/V batch of keys (128 at head_dim 64) takes the short-context instantiations
+ *   (DESIGN.md §5).  Results are bit-identical either way.
  *   "profile_skip" = 1 | 2 | 3 (any time; results become meaningless): measurement hook of bench.py, leaves the self-attention
  *   (bit 0) and / or cross-attention (bit 1) launches out of the captured decode step, so that what a kernel costs the step is
  *   the difference between two timed generates.  0 restores the real step. */
@@ -147,6 +150,10 @@ int32_t amt_generate_commit(amt_handle* h, const int64_t* chosen, void* stream);
  * branch (plain softmax[:157], root / attr of the committed position stay PAD).  This is the per-step choice
  * `random.uniform(0,1) <= beam_chance` of model/video_music_transformer.py:1074-1084; the host keeps the `beam` rows. */
 int32_t amt_generate_set_branch(amt_handle* h, int32_t beam);
+/* Test access to the self-attention K/V cache, fp32 [2 (K, V)][n_layers][max_batch][H][rows][hd] with rows = max_sequence_chord plus
+ * the padding rows of DESIGN.md §4: dims_out (optional, 6 values) receives the shape; buf (optional, n_floats = their product, device
+ * memory) receives the cache (write = 0) or replaces it (write = 1). */
+int32_t amt_kv_cache_io(amt_handle* h, float* buf, int64_t n_floats, int32_t write, int64_t* dims_out, void* stream);
 /* Copies the (B,T) int64 token matrix (PAD=158 beyond the generated length) to tokens_out. */
 int32_t amt_generate_end(amt_handle* h, int64_t* tokens_out, void* stream);
 /* begin + run(-1) + end. */
@@ -225,7 +232,9 @@ int32_t amt_decode_linear_fwd(const float* x, const float* w, const float* bias,
  * amt_attn_decode_fold_fwd: raw (B, ldq) = u . (W o gamma)^T, columns [0,d) query (and [d,2d) key, [2d,3d) value of the new
  *   position when new_kv = 1); u (B, d) the pre-LayerNorm sum; q = ((raw - mu*fold_g) * rstd + fold_c) * q_scale with the row
  *   statistics of u; xn_out (optional) = LayerNorm(u).  new_kv = 1 also writes the key/value of position *pos_dev into the
- *   caches and attends keys 0..pos; new_kv = 0 attends keys 0..n_keys-1 (cross-attention).
+ *   caches and attends keys 0..pos; new_kv = 0 attends keys 0..n_keys-1 (cross-attention).  new_kv | 2 (Er given): the
+ *   short-context instantiation of the relative-position self-attention, bit-identical to the long one at any length; with it u
+ *   may be null: raw is then the finished query (B, H*hd) as amt_attn_decode_fwd takes it, keys 0..*pos_dev or 0..n_keys-1.
  * amt_decode_gemm_ex_fwd: rows [x (K1 columns) | x2 (K-K1 columns)]; y_low (B, n_low) = act(x . w_low^T + b (+resid)) over the
  *   first K1 columns (all K when x2 is null), y_high (B, n_high) = [x|x2] . w_high^T + b_high.  pro = 1: the staged row is
  *   [relu((x - mu*fold_g)*rstd + fold_c) | LayerNorm(x2)] (statistics of x2's row) and LayerNorm(x2) is y_low's residual.

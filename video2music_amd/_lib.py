@@ -63,6 +63,7 @@ SIGNATURES = {
     "amt_generate_commit": [_P, _P, _P],
     "amt_generate_set_branch": [_P, _I],
     "amt_generate_end": [_P, _P, _P],
+    "amt_kv_cache_io": [_P, _P, C.c_int64, _I, C.POINTER(C.c_int64), _P],
     "amt_generate": [_P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P],
     "amt_v2_decide_batch": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _I, _P],
     "amt_v2_step_decide_batch": [C.POINTER(V2StepArgs), C.POINTER(V2DecideArgs), _I, _P],

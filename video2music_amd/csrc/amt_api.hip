@@ -98,7 +98,6 @@ struct amt_handle {
     // layer-0 q/k/v as table sums: rows of (root, attr, key column, position) projected through layer 0's in-proj
     float *tab_r = nullptr, *tab_a = nullptr, *tab_k = nullptr, *tab_p = nullptr, *tab_cb = nullptr;
     int* pos = nullptr;
-    unsigned* ticket = nullptr;
     float* unif = nullptr;               // [Tcap][maxB] uniforms of the device-side categorical draw (amt_generate_set_uniforms)
     int use_unif = 0;
     int64_t *tokens = nullptr, *roots = nullptr, *attrs = nullptr;   // [maxB][Tcap]
@@ -110,10 +109,12 @@ struct amt_handle {
     const float* vis_resid = nullptr;    // amt_encode_resid: rows added to Linear_vis's output (scene_embed)
     int skip_mask = 0;                   // amt_set_option("profile_skip"): measurement ablation, 1 = no self-attention launches, 2 = no cross-attention launches
     bool fuse_head = true;               // amt_set_option("fuse_sampling_head"): inside a captured graph the head rides in the next step's first attention
+    bool short_attn = true;              // amt_set_option("short_context_attn"): graphs whose every step fits one K/V batch use the short-context self-attention
+    bool step_short = false;             // set by get_graph while it captures such a graph (eager steps keep the long kernels)
     bool plain_chain = false;            // amt_set_option("decode_chain_plain"), before the first amt_finalize: the 49-launch chain without folded LayerNorms
     bool gen_active = false;
     // graphs keyed by the parameters baked into the captured kernel arguments
-    struct GraphKey { int B, T, P, beam, mcN, mcC, S, nsteps, skip, pad; float* logits; };
+    struct GraphKey { int B, T, P, beam, mcN, mcC, S, nsteps, skip, pad, short_ctx, parity; float* logits; };
     struct GraphEntry { GraphKey key; hipGraphExec_t exec; hipGraph_t graph; };
     std::vector<GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;    // capture-only stream (the caller's may be the legacy null stream)
@@ -208,7 +209,11 @@ int32_t ffn_block(amt_handle* h, float* X, const float* l1w, const float* l1b, c
     return proj_resid_ln(h, h->wsH, h->dff, l2w, l2b, X, nw, nb, n2w, n2b, h->wsU, Xout, rows, s);
 }
 
-SampleParams sample_params(amt_handle* h, float* logits_out, float* probs_out, int external) {
+// the device-side position pair: the kernels of the step that processes position `step` read slot step & 1 (SampleParams::pos)
+int* pos_slot(amt_handle* h, int step) { return h->pos + (step & 1); }
+
+// the head that closes the step processing position `step`
+SampleParams sample_params(amt_handle* h, float* logits_out, float* probs_out, int external, int step) {
     SampleParams p{};
     const DecLayer& L = h->dec.back();
     p.u = h->u3; p.ldu = h->d;
@@ -217,7 +222,7 @@ SampleParams sample_params(amt_handle* h, float* logits_out, float* probs_out, i
     p.Wout = W(h, "Wout.weight"); p.bout = W(h, "Wout.bias");
     p.eps = LN_EPS; p.B = h->genB; p.d = h->d;
     p.tokens = h->tokens; p.roots = h->roots; p.attrs = h->attrs; p.T = h->genT;
-    p.pos = h->pos; p.ticket = h->ticket; p.n_primer = h->genP; p.beam = h->beam;
+    p.pos = pos_slot(h, step); p.pos_next = pos_slot(h, step + 1); p.n_primer = h->genP; p.beam = h->beam;
     p.max_conseq_N = h->mcN; p.max_conseq_chord = h->mcC;
     p.logits_out = logits_out; p.probs_out = probs_out;
     p.key = h->keyb; p.PR = h->PR; p.PA = h->PA; p.wkey = h->wkey; p.cbias = W(h, "Linear_chord.bias"); p.pe = h->pe;
@@ -258,8 +263,9 @@ struct StepProf {
 // 5 dependent kernels per layer instead of 8.  Layer 0's q/k/v are table sums written by the sampling head (its input is
 // a sum of embedding-table rows), the last G3 also emits the raw logits, so a step is 6*5 + 1 = 31 launches.
 // fused_sp (captured graphs, round 3): layer 0's self-attention takes the PREVIOUS step's sampling decision in its prologue
-// (attn_decode_sample_kernel) -- the step then needs no sampling-head launch in front of it: 30 launches.
-int32_t enqueue_decoder_step_folded(amt_handle* h, hipStream_t s, StepProf* prof, const SampleParams* fused_sp = nullptr) {
+// (attn_decode_sample_kernel) -- the step then needs no sampling-head launch in front of it: 30 launches.  That launch reads the
+// previous step's slot of the position pair and fills this step's, which the other 29 read.
+int32_t enqueue_decoder_step_folded(amt_handle* h, hipStream_t s, int step, StepProf* prof, const SampleParams* fused_sp = nullptr) {
     const int B = h->genB, d = h->d, dff = h->dff, H = h->H, hd = h->hd;
     const float qscale = 1.0f / sqrtf((float)hd);
     int32_t rc;
@@ -271,7 +277,7 @@ int32_t enqueue_decoder_step_folded(amt_handle* h, hipStream_t s, StepProf* prof
         const float* Vx = Kx + h->kvx_part;
         AttnDecodeParams a{};
         a.k = Kc; a.v = Vc; a.o = h->ob; a.B = B; a.H = H; a.hd = hd; a.cap = h->kv_rows;
-        a.pos = h->pos; a.Er = L.Er; a.er_len = h->Tcap;
+        a.pos = l == 0 && fused_sp ? fused_sp->pos : pos_slot(h, step); a.Er = L.Er; a.er_len = h->Tcap; a.short_ctx = h->step_short;
         if (l == 0 && fused_sp) {
             a.k_new = Kc; a.v_new = Vc; a.new_kv = 1;      // q / k / v of the new position are summed from the projected tables in the kernel
         } else if (l == 0) {
@@ -327,8 +333,8 @@ int32_t enqueue_decoder_step_folded(amt_handle* h, hipStream_t s, StepProf* prof
 }
 
 // the kernels of one decode step up to (not including) the sampling head
-int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, StepProf* prof = nullptr) {
-    if (h->fold) return enqueue_decoder_step_folded(h, s, prof);
+int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, int step, StepProf* prof = nullptr) {
+    if (h->fold) return enqueue_decoder_step_folded(h, s, step, prof);
     const int B = h->genB, d = h->d, dff = h->dff, H = h->H, hd = h->hd;
     const float qscale = 1.0f / sqrtf((float)hd);
     int32_t rc;
@@ -344,7 +350,7 @@ int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, StepProf* prof = null
         g.x = l == 0 ? h->x_in : h->u3; g.ldx = d; g.Wp = L.p_sa; g.bias = L.sa_b; g.N = 3 * d; g.K = d;
         if (l > 0) { g.ln_w = h->dec[l - 1].n3w; g.ln_b = h->dec[l - 1].n3b; g.xn = h->xa; }
         g.mode = 1; g.y = h->qb; g.ldy = d; g.scale = qscale; g.scale_cols = d;
-        g.kcache = Kc; g.vcache = Vc; g.H = H; g.hd = hd; g.cap = h->kv_rows; g.pos = h->pos; g.d = d;
+        g.kcache = Kc; g.vcache = Vc; g.H = H; g.hd = hd; g.cap = h->kv_rows; g.pos = pos_slot(h, step); g.d = d;
         PROF_BEGIN();
         if ((rc = amt_launch_decode_gemm(g, s))) return rc;
         PROF_END(2);
@@ -352,7 +358,7 @@ int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, StepProf* prof = null
         // K2: relative-position self-attention over the cache
         AttnDecodeParams a{};
         a.q = h->qb; a.k = Kc; a.v = Vc; a.o = h->ob; a.B = B; a.H = H; a.hd = hd; a.cap = h->kv_rows;
-        a.pos = h->pos; a.Er = L.Er; a.er_len = h->Tcap;
+        a.pos = pos_slot(h, step); a.Er = L.Er; a.er_len = h->Tcap; a.short_ctx = h->step_short;
         if (!(h->skip_mask & 1)) {
             PROF_BEGIN();
             if ((rc = amt_launch_attn_decode(a, s))) return rc;
@@ -418,8 +424,12 @@ int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, StepProf* prof = null
     return 0;
 }
 
-int32_t get_graph(amt_handle* h, int nsteps, float* logits_out, hipGraphExec_t* out) {
-    amt_handle::GraphKey key{h->genB, h->genT, h->genP, h->beam, h->mcN, h->mcC, h->encS, nsteps, h->skip_mask | (h->fuse_head ? 4 : 0), h->use_unif, logits_out};
+int32_t get_graph(amt_handle* h, int first_pos, int nsteps, float* logits_out, hipGraphExec_t* out) {
+    // the graph's steps process positions first_pos .. first_pos + nsteps - 1: when the last of them still has at most one K/V batch
+    // of keys, every self-attention of the graph is the short-context instantiation (a graph that straddles the limit keeps the long one)
+    const bool short_ctx = h->short_attn && first_pos + nsteps <= amt_attn_decode_stride(h->hd);
+    amt_handle::GraphKey key{h->genB, h->genT, h->genP, h->beam, h->mcN, h->mcC, h->encS, nsteps, h->skip_mask | (h->fuse_head ? 4 : 0), h->use_unif,
+                             short_ctx ? 1 : 0, first_pos & 1, logits_out};
     for (auto& g : h->graphs)
         if (memcmp(&g.key, &key, sizeof(key)) == 0) { *out = g.exec; return 0; }
     hipGraph_t graph;
@@ -432,13 +442,20 @@ int32_t get_graph(amt_handle* h, int nsteps, float* logits_out, hipGraphExec_t* 
     // Inside a graph the sampling head between two steps rides in the prologue of the following step's first self-attention
     // (folded chain, decision on the device): [step, head] x n becomes step, (head+step) x (n-1), head.  The measurement hook that
     // leaves the self-attention launches out keeps the separate head (the decision must still happen).
-    const SampleParams sp = sample_params(h, logits_out, nullptr, 0);
+    // Every node carries the slot of the position pair that belongs to its step's parity, so a graph serves the starts of one parity.
     const bool fuse = h->fold && h->fuse_head && !(h->skip_mask & 1);
+    h->step_short = short_ctx;
     for (int i = 0; i < nsteps && !rc; ++i) {
-        if (fuse && i > 0) rc = enqueue_decoder_step_folded(h, cs, nullptr, &sp);
-        else rc = enqueue_decoder_step(h, cs);
-        if (!rc && !(fuse && i + 1 < nsteps)) rc = amt_launch_sample(sp, cs);
+        const int step = first_pos + i;
+        if (fuse && i > 0) {
+            const SampleParams sp = sample_params(h, logits_out, nullptr, 0, step - 1);
+            rc = enqueue_decoder_step_folded(h, cs, step, nullptr, &sp);
+        } else {
+            rc = enqueue_decoder_step(h, cs, step);
+        }
+        if (!rc && !(fuse && i + 1 < nsteps)) rc = amt_launch_sample(sample_params(h, logits_out, nullptr, 0, step), cs);
     }
+    h->step_short = false;
     hipError_t e = hipStreamEndCapture(cs, &graph);
     if (rc) { if (e == hipSuccess) (void)hipGraphDestroy(graph); return rc; }
     AMT_HIP(e);
@@ -627,13 +644,11 @@ extern "C" int32_t amt_finalize(amt_handle* h) {
         }
         if ((rc = dev_alloc(h, &h->keyb, mb))) return rc;
         if ((rc = dev_alloc(h, &h->pos, (size_t)4))) return rc;
-        if ((rc = dev_alloc(h, &h->ticket, (size_t)4))) return rc;
         if ((rc = dev_alloc(h, &h->unif, (size_t)h->maxB * h->Tcap))) return rc;
         if ((rc = dev_alloc(h, &h->tokens, (size_t)h->maxB * h->Tcap))) return rc;
         if ((rc = dev_alloc(h, &h->roots, (size_t)h->maxB * h->Tcap))) return rc;
         if ((rc = dev_alloc(h, &h->attrs, (size_t)h->maxB * h->Tcap))) return rc;
         AMT_HIP(hipMemset(h->pos, 0, 16));
-        AMT_HIP(hipMemset(h->ticket, 0, 16));
     }
     // Linear_vis zero-padded to a multiple of the GEMM K-step; Linear_chord split into its d x d
     // block and the key column (video_music_transformer.py:999-1001: cat([x, key]) -> Linear(d+1, d))
@@ -723,6 +738,10 @@ extern "C" int32_t amt_set_option(amt_handle* h, const char* name, int32_t value
     }
     if (strcmp(name, "fuse_sampling_head") == 0) {           // 0: every step of a captured graph ends with its own sampling-head launch (31 per step)
         h->fuse_head = value != 0;
+        return 0;
+    }
+    if (strcmp(name, "short_context_attn") == 0) {           // 0: every captured graph uses the long-context self-attention (A/B and parity tests)
+        h->short_attn = value != 0;
         return 0;
     }
     if (strcmp(name, "profile_skip") == 0) {                 // measurement hook of bench.py: leave a kernel class out of the captured step
@@ -881,8 +900,7 @@ extern "C" int32_t amt_generate_begin(amt_handle* h, int32_t B, const int64_t* p
     AMT_LAUNCH_CHECK();
     AMT_HIP(hipMemcpyAsync(h->keyb, key, B * sizeof(float), hipMemcpyDeviceToDevice, s));
     AMT_HIP(hipMemsetAsync(h->pos, 0, 16, s));
-    AMT_HIP(hipMemsetAsync(h->ticket, 0, 16, s));
-    return amt_launch_embed_step(sample_params(h, nullptr, nullptr, 0), 0, s);     // x_in for position 0
+    return amt_launch_embed_step(sample_params(h, nullptr, nullptr, 0, 0), 0, s);     // x_in for position 0
 }
 
 extern "C" int32_t amt_generate_set_uniforms(amt_handle* h, const float* uniforms, void* stream) {
@@ -907,7 +925,7 @@ extern "C" int32_t amt_generate_run(amt_handle* h, int32_t n_steps, float* logit
         while (ns > left) ns >>= 1;
         if (ns < 1) ns = 1;
         hipGraphExec_t exec;
-        if ((rc = get_graph(h, ns, logits_out, &exec))) return rc;
+        if ((rc = get_graph(h, h->steps_done + n_steps - left, ns, logits_out, &exec))) return rc;
         AMT_HIP(hipGraphLaunch(exec, s));
         left -= ns;
     }
@@ -928,10 +946,10 @@ extern "C" int32_t amt_generate_profile(amt_handle* h, int32_t n_steps, double* 
     int32_t rc = 0;
     for (int i = 0; i < n_steps && !rc; ++i) {
         prof.used = 0; prof.cls.clear();
-        rc = enqueue_decoder_step(h, s, &prof);
+        rc = enqueue_decoder_step(h, s, h->steps_done + i, &prof);
         if (rc) break;
         prof.begin();
-        rc = amt_launch_sample(sample_params(h, nullptr, nullptr, 0), s);
+        rc = amt_launch_sample(sample_params(h, nullptr, nullptr, 0, h->steps_done + i), s);
         prof.end(3);
         if (rc) break;
         prof.begin();            // class 4: an empty pair = the cost of the event records themselves
@@ -959,9 +977,9 @@ extern "C" int32_t amt_generate_step_probs(amt_handle* h, float* probs_out, void
     AMT_CHECK_ARG(h && h->gen_active && probs_out, "amt_generate_step_probs: no generation in progress");
     AMT_CHECK_ARG(h->steps_done < h->genT - 1, "amt_generate_step_probs: sequence is complete");
     hipStream_t s = (hipStream_t)stream;
-    int32_t rc = enqueue_decoder_step(h, s);
+    int32_t rc = enqueue_decoder_step(h, s, h->steps_done);
     if (rc) return rc;
-    return amt_launch_sample(sample_params(h, nullptr, probs_out, 1), s);
+    return amt_launch_sample(sample_params(h, nullptr, probs_out, 1, h->steps_done), s);
 }
 
 namespace {
@@ -975,11 +993,26 @@ __global__ void commit_tokens_kernel(int64_t* tokens, const int64_t* chosen, con
 extern "C" int32_t amt_generate_commit(amt_handle* h, const int64_t* chosen, void* stream) {
     AMT_CHECK_ARG(h && h->gen_active && chosen, "amt_generate_commit: no generation in progress");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(commit_tokens_kernel, dim3(1), dim3(h->genB), 0, s, h->tokens, chosen, h->pos, h->genT, h->genP);
+    hipLaunchKernelGGL(commit_tokens_kernel, dim3(1), dim3(h->genB), 0, s, h->tokens, chosen, pos_slot(h, h->steps_done), h->genT, h->genP);
     AMT_LAUNCH_CHECK();
-    int32_t rc = amt_launch_embed_step(sample_params(h, nullptr, nullptr, 1), 1, s);
+    int32_t rc = amt_launch_embed_step(sample_params(h, nullptr, nullptr, 1, h->steps_done), 1, s);
     if (rc) return rc;
     h->steps_done += 1;
+    return 0;
+}
+
+// Test access to the self-attention K/V cache, [2 (K, V)][n_layers][max_batch][H][rows][hd] fp32 where rows = max_sequence_chord
+// plus the padding row(s) that keep the heads off a power-of-two stride: dims_out (6 values) receives that shape; with buf the whole
+// cache is copied out (write = 0) or in (write = 1), n_floats being the caller's count of the product
+extern "C" int32_t amt_kv_cache_io(amt_handle* h, float* buf, int64_t n_floats, int32_t write, int64_t* dims_out, void* stream) {
+    AMT_CHECK_ARG(h && h->KVc, "amt_kv_cache_io: handle not finalized");
+    const int64_t dims[6] = {2, h->nl, h->maxB, h->H, h->kv_rows, h->hd};
+    if (dims_out) for (int i = 0; i < 6; ++i) dims_out[i] = dims[i];
+    if (!buf) return 0;
+    AMT_CHECK_ARG(n_floats == (int64_t)(2 * h->kvc_part), "amt_kv_cache_io: the cache holds %lld floats, not %lld", (long long)(2 * h->kvc_part), (long long)n_floats);
+    const size_t bytes = 2 * h->kvc_part * sizeof(float);
+    if (write) AMT_HIP(hipMemcpyAsync(h->KVc, buf, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    else AMT_HIP(hipMemcpyAsync(buf, h->KVc, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 

@@ -112,16 +112,22 @@ constexpr int UCH_MAX = 4;       // folded prologue: the pre-LN row has at most 
 // the query and of the new key (the V1/V2 self-attention behind a folded norm3; no relative-position table), 5 = the base model's
 // layer-0 self-attention with the PREVIOUS step's sampling decision in its prologue (attn_decode_sample_kernel): wave 0 takes the
 // decision of the folded output head for its clip (sample_device.h), every wave then sums its head's q / k / v of the new position
-// from the projected input tables, head 0 stores the token and the next input row, the launch's last workgroup advances the
-// position -- the sampling head's launch between two steps of a captured graph disappears
+// from the projected input tables, head 0 stores the token and the next input row, workgroup (0, 0) stores the
+// position into the other slot of the position pair -- the sampling head's launch between two steps of a captured graph disappears
 #ifdef AMT_STAMPS
 #define ASTAMP(i) do { __builtin_amdgcn_sched_barrier(0); st_[i] = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define ASTAMP(i) do { } while (0)
 #endif
 
-template <int HD, bool RPR, bool NT, int FOLD, int UCH>
+// SHORT (relative-position self-attention, FOLD 0 / 2 / 5): the instantiation the host picks for a captured graph whose every step has
+// at most STRIDE keys.  The prologue's loads go in FRONT of the one K/V batch, the batch is clamped to the length (rows past it re-read
+// row 0 from cache instead of streaming cap rows nobody consumes) and no second batch is requested, so nothing waits for a dead HBM
+// round trip.  Wave -> key mapping, consumption order and both merges are those of the long path: the output is bit-identical.  At
+// more than STRIDE keys it is still correct (further batches follow one at a time).
+template <int HD, bool RPR, bool NT, int FOLD, int UCH, bool SHORT = false>
 __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, const SampleParams* sp) {
+    static_assert(!SHORT || (RPR && (FOLD == 0 || FOLD == 2 || FOLD == 5)), "the short-context order exists for the base model's self-attention");
 #ifdef AMT_STAMPS
     unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -149,6 +155,13 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
     float4 q4, kn4 = make_float4(0.f, 0.f, 0.f, 0.f), vn4 = kn4;
     constexpr bool fresh = FOLD == 2 || FOLD == 4 || FOLD == 5;   // key/value of position t live in registers, not in the cache
     const int n_keys = fresh ? t : t + 1;
+    // the own key's Er row (relative distance 0) has a constant address: requested with the prologue's loads instead of one exposed L2
+    // round trip behind wave 0's stream.  Not in the long FOLD 2 kernel of hd = 64, d_model <= 512: under its 128-VGPR bound the four
+    // registers spill (ISA: 125 VGPRs without them, 128 + 1 spilled + 8 bytes of scratch with them); it loads the row where it is used
+    constexpr bool own_er = RPR && fresh && !(FOLD == 2 && HD == 64 && UCH == 2 && !SHORT);
+    float4 e_own = make_float4(0.f, 0.f, 0.f, 0.f);
+    // FOLD 5 writes rows at t and advances the position only inside the sequence and the cache (a replay too many must not run away)
+    const bool live = FOLD != 5 || (t < sp->T && t < p.cap);
     const float* eb = RPR ? p.Er + (size_t)(p.er_len - 1 - t) * HD : nullptr;   // Er row of key 0 (wave-uniform)
     // Vector loads return in issue order.  The long prologue of FOLD 2 (11 loads and their address math) goes
     // behind the first K/V batch so that the stream starts at once; the short one of FOLD 1 goes in front of it
@@ -165,7 +178,7 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
             if (t >= q.n_primer) {
                 const int tok = decide_fold_wave<UCH>(q, b, t - 1, lane, h == 0);
                 feedback_of(q, tok, root, attr);
-                if (h == 0 && lane == 0) {
+                if (h == 0 && lane == 0 && live) {
                     q.tokens[(size_t)b * q.T + t] = tok;
                     q.roots[(size_t)b * q.T + t] = root;
                     q.attrs[(size_t)b * q.T + t] = attr;
@@ -173,21 +186,24 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
             } else {
                 // inside the primer the token is given; the logits of the previous position are still owed to a caller who asked for them
                 if (q.logits_out && h == 0) (void)decide_fold_wave<UCH>(q, b, t - 1, lane, true);
-                root = (int)q.roots[(size_t)b * q.T + t];
-                attr = (int)q.attrs[(size_t)b * q.T + t];
+                root = (int)q.roots[(size_t)b * q.T + (live ? t : 0)];
+                attr = (int)q.attrs[(size_t)b * q.T + (live ? t : 0)];
             }
             if (lane == 0) { s_ra[0] = root; s_ra[1] = attr; }
         }
     }
-    if (!F1) load_kv<HD, NT>(b0, kb, vb, j0, sub, c4, p.cap);
+    if (!F1 && !SHORT) load_kv<HD, NT>(b0, kb, vb, j0, sub, c4, p.cap);
     if (!FOLD) {
         q4 = ld4(p.q + ((size_t)b * p.H + h) * HD + c * 4);
+        if (SHORT) load_kv<HD, NT>(b0, kb, vb, j0, sub, c4, n_keys);
     } else if constexpr (FOLD == 5) {
         // The decision (above) and the table rows behind it are two serial L2 round trips before the query exists: the key stream
         // runs meanwhile -- the Er rows of the first batch and the whole SECOND batch are requested here (rows past the end clamp to
         // row 0), so the HBM stream does not idle behind the prologue
+        // (SHORT: the one batch there is, clamped to the length, and nothing behind it in front of the table rows)
+        if (SHORT) load_kv<HD, NT>(b0, kb, vb, j0, sub, c4, n_keys);
         if (RPR) load_er<HD>(b0, eb, j0, sub, c4, n_keys);
-        load_batch<HD, RPR, NT>(b1, kb, vb, eb, j0 + STRIDE, sub, c4, n_keys);
+        if (!SHORT) load_batch<HD, RPR, NT>(b1, kb, vb, eb, j0 + STRIDE, sub, c4, n_keys);
         const SampleParams& q = *sp;
         __syncthreads();
         const int root = s_ra[0], attr = s_ra[1];
@@ -198,10 +214,11 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
         const float* tr = q.tab_r + (size_t)root * d3 + col;
         const float* ta = q.tab_a + (size_t)attr * d3 + col;
         const float* tk = q.tab_k + col;
-        const float* tp = q.tab_p + (size_t)t * d3 + col;
+        const float* tp = q.tab_p + (size_t)(live ? t : 0) * d3 + col;
         const float4 r0 = ld4(tr), a0 = ld4(ta), k0 = ld4(tk), p0 = ld4(tp);
         const float4 r1 = ld4(tr + d), a1 = ld4(ta + d), k1 = ld4(tk + d), p1 = ld4(tp + d);
         const float4 r2 = ld4(tr + 2 * d), a2 = ld4(ta + 2 * d), k2 = ld4(tk + 2 * d), p2 = ld4(tp + 2 * d);
+        if (own_er) e_own = ld4(p.Er + (size_t)(p.er_len - 1) * HD + c4);
         __builtin_amdgcn_sched_barrier(0);
         q4.x = (((r0.x + a0.x) + kv * k0.x) + p0.x) * q.q_scale; q4.y = (((r0.y + a0.y) + kv * k0.y) + p0.y) * q.q_scale;
         q4.z = (((r0.z + a0.z) + kv * k0.z) + p0.z) * q.q_scale; q4.w = (((r0.w + a0.w) + kv * k0.w) + p0.w) * q.q_scale;
@@ -209,7 +226,7 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
         kn4.z = ((r1.z + a1.z) + kv * k1.z) + p1.z; kn4.w = ((r1.w + a1.w) + kv * k1.w) + p1.w;
         vn4.x = ((r2.x + a2.x) + kv * k2.x) + p2.x; vn4.y = ((r2.y + a2.y) + kv * k2.y) + p2.y;
         vn4.z = ((r2.z + a2.z) + kv * k2.z) + p2.z; vn4.w = ((r2.w + a2.w) + kv * k2.w) + p2.w;
-        if (h == 0) {                                 // the next input row x[t] (the residual stream layer 0 starts from)
+        if (h == 0 && live) {                         // the next input row x[t] (the residual stream layer 0 starts from)
             for (int cc = threadIdx.x * 4; cc < d; cc += NW * 64 * 4) {
                 const float4 pr = ld4(q.PR + (size_t)root * d + cc), pa = ld4(q.PA + (size_t)attr * d + cc);
                 const float4 wk = ld4(q.wkey + cc), bb = ld4(q.cbias + cc), pp = ld4(q.pe + (size_t)t * d + cc);
@@ -243,10 +260,11 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
         float4 rcs = make_float4(1.f, 0.f, 1.f, 0.f);
         if (FOLD == 3) rcs = ld4(p.rope + (size_t)(*p.rope_pos) * p.rope_dim + (col % p.rope_dim));     // (cos, sin) of the lane's two pairs
         if (FOLD == 4) rcs = ld4(p.rope + (size_t)t * p.rope_dim + (col % p.rope_dim));
-        if (F1) load_kv<HD, NT>(b0, kb, vb, j0, sub, c4, p.cap);
+        if (F1 || SHORT) load_kv<HD, NT>(b0, kb, vb, j0, sub, c4, SHORT ? n_keys : p.cap);
         // the first batch's Er rows need only the position: issued behind the prologue's loads, they land while the
         // statistics are reduced instead of costing one more L2 round trip after the query exists
         if (RPR && fresh) load_er<HD>(b0, eb, j0, sub, c4, n_keys);
+        if (own_er) e_own = ld4(p.Er + (size_t)(p.er_len - 1) * HD + c4);
         __builtin_amdgcn_sched_barrier(0);             // no consumer of a loaded value moves in front of the loads above
         const float inv_d = 1.0f / (float)d;
         float s = 0.f;
@@ -310,7 +328,7 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
     if (q4.x == 1.2345e-30f) st_[7] = 1;          // stamp 1 = the query exists (prologue loads landed, statistics done)
 #endif
     ASTAMP(1);
-    if (fresh && wave == 0 && sub == 0) {
+    if (fresh && wave == 0 && sub == 0 && live) {
         st4(p.k_new + (((size_t)b * p.H + h) * p.cap + t) * HD + c * 4, kn4);
         st4(p.v_new + (((size_t)b * p.H + h) * p.cap + t) * HD + c * 4, vn4);
     }
@@ -318,7 +336,17 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
     // (fresh variants requested the first batch's Er rows inside their prologue)
     float m = -INFINITY, l = 0.f;
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (FOLD == 5) {
+    if constexpr (SHORT) {
+        consume_batch<HD, RPR>(b0, q4, j0, sub, n_keys, m, l, o);
+        j0 += STRIDE;
+        // not on a graph the host picks this instantiation for, but correctness does not rest on that choice: further batches one
+        // at a time through the same registers (no second buffer to keep alive), consumed in the long path's order
+        while (j0 < n_keys) {
+            load_batch<HD, RPR, NT>(b0, kb, vb, eb, j0, sub, c4, n_keys);
+            consume_batch<HD, RPR>(b0, q4, j0, sub, n_keys, m, l, o);
+            j0 += STRIDE;
+        }
+    } else if constexpr (FOLD == 5) {
         // both batches are in flight since the prologue
         consume_batch<HD, RPR>(b0, q4, j0, sub, n_keys, m, l, o);
         j0 += STRIDE;
@@ -338,8 +366,8 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
     if (fresh && wave == 0) {                        // the current position's own key (relative distance 0)
         float4 k4 = kn4;
         if (RPR) {
-            const float4 e = ld4(p.Er + (size_t)(p.er_len - 1) * HD + c * 4);
-            k4.x += e.x; k4.y += e.y; k4.z += e.z; k4.w += e.w;
+            if (!own_er) e_own = ld4(p.Er + (size_t)(p.er_len - 1) * HD + c * 4);
+            k4.x += e_own.x; k4.y += e_own.y; k4.z += e_own.z; k4.w += e_own.w;
         }
         float s = q4.x * k4.x + q4.y * k4.y + q4.z * k4.z + q4.w * k4.w;
         s = group_sum<LPK>(s);
@@ -404,32 +432,27 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
     }
 #endif
     if constexpr (FOLD == 5) {
-        // every workgroup read *pos at its start; the last one to arrive publishes the position this step processes
-        if (threadIdx.x == 0) {
-            const unsigned n = __hip_atomic_fetch_add(sp->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (n == gridDim.x * gridDim.y - 1) {
-                *sp->pos = t;
-                __hip_atomic_store(sp->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        // every workgroup read the previous position from *pos; the position this step processes goes to the OTHER slot of the pair,
+        // which the remaining launches of the step read: a plain store by one workgroup, nobody in this launch reads that word
+        if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && live) *sp->pos_next = t;
     }
 }
 
-template <int HD, bool RPR, bool NT, int FOLD, int UCH>
+template <int HD, bool RPR, bool NT, int FOLD, int UCH, bool SHORT = false>
 // hd = 64 at d_model <= 512 (the benchmark's shape) is held at 128 VGPRs = two workgroups per CU: it fits without spilling and a
 // launch of more than 256 workgroups (more than 32 clips per chain) then runs in one round (+6-7 % tokens/s at 64-256 clips); the
 // other shapes keep the compiler's own choice (the same bound makes the hd = 16 / 32 relative-position variants spill)
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((HD == 64 && UCH == 2) ? 4 : 1, (HD == 64 && UCH == 2) ? 4 : 8)))
 void attn_decode_kernel(AttnDecodeParams p) {
-    attn_decode_body<HD, RPR, NT, FOLD, UCH>(p, nullptr);
+    attn_decode_body<HD, RPR, NT, FOLD, UCH, SHORT>(p, nullptr);
 }
 
 // layer 0 of the base model's folded chain with the previous step's decision in front (FOLD 5).  No 128-VGPR bound here: with the
 // first K/V batch in flight the decision and the twelve table rows need more (the bound spilled 36 registers); at 32 clips the launch is
 // one workgroup per CU either way, above that this ONE launch of the step's six self-attentions takes two rounds
-template <int HD, bool RPR, bool NT, int UCH>
+template <int HD, bool RPR, bool NT, int UCH, bool SHORT = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_sample_kernel(AttnDecodeParams p, SampleParams sp) {
-    attn_decode_body<HD, RPR, NT, 5, UCH>(p, &sp);
+    attn_decode_body<HD, RPR, NT, 5, UCH, SHORT>(p, &sp);
 }
 
 template <int HD, int FOLD, int UCH>
@@ -440,6 +463,13 @@ void launch_decode_u(const AttnDecodeParams& p, hipStream_t stream) {
     // config 2).  AmtTuning::nt_mask: bit 0 = self-attention, bit 1 = cross-attention.
     const int nt_mask = amt_tuning().nt_mask;
     if (p.Er) {
+        if constexpr (FOLD == 0 || FOLD == 2) {
+            if (p.short_ctx) {                   // the host's choice for a graph of short steps (AttnDecodeParams::short_ctx)
+                if (nt_mask & 1) hipLaunchKernelGGL((attn_decode_kernel<HD, true, true, FOLD, UCH, true>), grid, dim3(NW * 64), 0, stream, p);
+                else hipLaunchKernelGGL((attn_decode_kernel<HD, true, false, FOLD, UCH, true>), grid, dim3(NW * 64), 0, stream, p);
+                return;
+            }
+        }
         if constexpr (FOLD != 4) {               // (the rotary self-attention has no relative-position table: checked by the launcher)
             if (nt_mask & 1) hipLaunchKernelGGL((attn_decode_kernel<HD, true, true, FOLD, UCH>), grid, dim3(NW * 64), 0, stream, p);
             else hipLaunchKernelGGL((attn_decode_kernel<HD, true, false, FOLD, UCH>), grid, dim3(NW * 64), 0, stream, p);
@@ -462,7 +492,11 @@ void launch_decode_sample(const AttnDecodeParams& p, const SampleParams& sp, hip
     dim3 grid(p.H, p.B);
     const bool nt = (amt_tuning().nt_mask & 1) != 0;
 #define AMT_LAUNCH_DS(RPR, NTV, UCHV) hipLaunchKernelGGL((attn_decode_sample_kernel<HD, RPR, NTV, UCHV>), grid, dim3(NW * 64), 0, stream, p, sp)
-    if (sp.d <= 512) {
+#define AMT_LAUNCH_DSS(NTV, UCHV) hipLaunchKernelGGL((attn_decode_sample_kernel<HD, true, NTV, UCHV, true>), grid, dim3(NW * 64), 0, stream, p, sp)
+    if (p.Er && p.short_ctx) {
+        if (sp.d <= 512) { if (nt) AMT_LAUNCH_DSS(true, 2); else AMT_LAUNCH_DSS(false, 2); }
+        else { if (nt) AMT_LAUNCH_DSS(true, 4); else AMT_LAUNCH_DSS(false, 4); }
+    } else if (sp.d <= 512) {
         if (p.Er) { if (nt) AMT_LAUNCH_DS(true, true, 2); else AMT_LAUNCH_DS(true, false, 2); }
         else { if (nt) AMT_LAUNCH_DS(false, true, 2); else AMT_LAUNCH_DS(false, false, 2); }
     } else {
@@ -470,16 +504,20 @@ void launch_decode_sample(const AttnDecodeParams& p, const SampleParams& sp, hip
         else { if (nt) AMT_LAUNCH_DS(false, true, 4); else AMT_LAUNCH_DS(false, false, 4); }
     }
 #undef AMT_LAUNCH_DS
+#undef AMT_LAUNCH_DSS
 }
 
 }  // namespace
 
+// keys one workgroup takes per batch: the limit below which a step qualifies for the short-context instantiations
+int amt_attn_decode_stride(int hd) { return NW * (64 / (hd / 4)) * UNROLL; }
+
 // The base model's layer-0 self-attention of a decode step with the previous step's sampling decision in its prologue (FOLD 5):
 // p as for the plain layer-0 launch (k / v the cache, pos the device position) plus k_new / v_new; sp as amt_launch_sample takes it
-// (folded head: lraw, h1..h4, projected tables).  *pos must hold the position the previous step processed.
+// (folded head: lraw, h1..h4, projected tables).  *pos must hold the position the previous step processed; this step's goes to *pos_next.
 int32_t amt_launch_attn_decode_sample(const AttnDecodeParams& p, const SampleParams& sp, hipStream_t stream) {
     AMT_CHECK_ARG(p.B > 0 && p.H > 0 && p.cap > 0 && p.pos && p.pos == sp.pos && p.k_new && p.v_new, "attn_decode_sample: bad attention arguments");
-    AMT_CHECK_ARG(sp.lraw && sp.h1 && sp.h2 && sp.h3 && sp.h4 && sp.ln_w && sp.ln_b && sp.tab_r && sp.tab_a && sp.tab_k && sp.tab_p && sp.ticket &&
+    AMT_CHECK_ARG(sp.lraw && sp.h1 && sp.h2 && sp.h3 && sp.h4 && sp.ln_w && sp.ln_b && sp.tab_r && sp.tab_a && sp.tab_k && sp.tab_p && sp.pos_next && sp.pos_next != sp.pos &&
                   sp.tokens && sp.roots && sp.attrs && sp.x_next && !sp.sample_external && !sp.probs_out,
                   "attn_decode_sample: needs the folded head, the projected input tables and a device-side decision");
     AMT_CHECK_ARG(sp.B == p.B && sp.d == p.H * p.hd && sp.d % 4 == 0 && sp.d <= UCH_MAX * 256, "attn_decode_sample: shapes of the two halves differ");

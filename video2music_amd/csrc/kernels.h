@@ -93,8 +93,13 @@ struct AttnDecodeParams {
     // (rope_pos; with new_kv = 1 the position is *pos and the new key is rotated too); column n of the d_model-wide query uses
     // entries (n % rope_dim) & ~1 and that + 1 (decode_gemm's rotary epilogue)
     const float* rope; int rope_dim; const int* rope_pos;
+    // relative-position self-attention without a rotary or plain folded prologue (the base model's): launch the short-context
+    // instantiation (prologue first, one K/V batch clamped to the length).  Same result at any length; faster only while the
+    // length stays within amt_attn_decode_stride(hd) keys, which is when the caller sets it
+    int short_ctx;
 };
 int32_t amt_launch_attn_decode(const AttnDecodeParams& p, hipStream_t stream);
+int amt_attn_decode_stride(int hd);
 
 // ---------------- decode-step skinny GEMM (decode_gemm.hip) ----------------
 // packed weight: tiles of 16(n) x 16(k): P[((nt*(K/16)+kt)*64 + lane)*4 + e] = W[nt*16+(lane&15)][kt*16+4*(lane>>4)+e]
@@ -211,8 +216,11 @@ struct SampleParams {
     float eps;
     int B, d;
     int64_t* tokens; int64_t* roots; int64_t* attrs; int T;   // [B][T] sequences (device)
-    int* pos;                        // device step counter (input position); advanced by the last block
-    unsigned* ticket;                // device arrival counter (zero between launches)
+    // The device-side position lives in a pair of slots (parity of the step): the kernels of the step that processes position t read
+    // slot t & 1, the head that closes it reads the same slot and stores t + 1 into the other one with a plain store.  The last readers
+    // of that other slot (the previous step's kernels) ended at a kernel boundary, so there is no race, no arrival counter, no atomic.
+    int* pos;                        // slot of the position this head decides from (input position t)
+    int* pos_next;                   // the other slot of the position pair: the head stores pos + 1 there (nobody in its launch reads it)
     int n_primer;                    // positions < n_primer are given, not sampled
     int beam;                        // 0: feedback greedy (G2), 1: verbatim top-1 (G1)
     int max_conseq_N, max_conseq_chord;

@@ -10,8 +10,8 @@
 // and then builds the next step's decoder input
 //   x[t+1] = Linear_chord([E_root[root]+E_attr[attr], key]) + pe[t+1]                  (:984-1001,1029)
 // from the tables PR = E_root.Wc[:, :d]^T, PA = E_attr.Wc[:, :d]^T precomputed at weight load.
-// The last workgroup to finish advances the device-side position counter that every kernel of
-// the captured step graph reads, so one graph replays for all steps.
+// Workgroup 0 stores the next position into the other slot of the device-side position pair (SampleParams::pos / pos_next) that
+// the kernels of the captured step graph read, so one graph replays for all steps of its parity.
 #include "amt_common.h"
 #include "kernels.h"
 #include "sample_device.h"
@@ -53,15 +53,8 @@ __device__ __forceinline__ void write_next_input(const SampleParams& p, int b, i
 }
 
 __device__ __forceinline__ void advance_pos(const SampleParams& p, int t) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // every block has read *pos before it takes a ticket; the last one publishes t+1
-        const unsigned n = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (n == gridDim.x - 1) {
-            *p.pos = t + 1;
-            __hip_atomic_store(p.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    // the blocks of this launch read *pos, the store goes to the other slot: no block has to wait for another
+    if (blockIdx.x == 0 && threadIdx.x == 0) *p.pos_next = t + 1;
 }
 
 template <int KCH>       // float4 chunks per lane covering d (d <= KCH*256)
@@ -479,6 +472,7 @@ extern "C" int32_t amt_v2_decide_batch(const float* logits, int32_t ld_logits, i
 
 int32_t amt_launch_sample(const SampleParams& p, hipStream_t stream) {
     AMT_CHECK_ARG(p.B > 0 && p.d % 4 == 0 && p.d <= 1024, "sample: bad shape B=%d d=%d", p.B, p.d);
+    AMT_CHECK_ARG(p.pos && p.pos_next && p.pos != p.pos_next, "sample: the position pair needs two distinct slots");
     if (p.lraw) {
         AMT_CHECK_ARG(p.h1 && p.h2 && p.h3 && p.h4 && p.ln_w && p.ln_b && p.ld_lraw >= V, "sample: incomplete folded head");
         switch ((p.d + 255) / 256) {
@@ -502,6 +496,7 @@ int32_t amt_launch_sample(const SampleParams& p, hipStream_t stream) {
 
 int32_t amt_launch_embed_step(const SampleParams& p, int advance, hipStream_t stream) {
     AMT_CHECK_ARG(p.B > 0 && p.d % 4 == 0, "embed_step: bad shape");
+    AMT_CHECK_ARG(p.pos && (!advance || (p.pos_next && p.pos != p.pos_next)), "embed_step: the position pair needs two distinct slots");
     hipLaunchKernelGGL(embed_step_kernel, dim3(p.B), dim3(256), 0, stream, p, advance);
     AMT_LAUNCH_CHECK();
     return 0;
