@@ -127,6 +127,9 @@ int32_t amt_generate_run(amt_handle* h, int32_t n_steps, float* logits_out, void
  *   "short_context_attn" = 0 (any time): every captured decode graph uses the long-context self-attention kernels; 1, the default:
  *   a graph whose last step still has at most one K/V batch of keys (128 at head_dim 64) takes the short-context instantiations
  *   (DESIGN.md §5).  Results are bit-identical either way.
+ *   "gemm_tile_pipeline" = 0 (any time): the skinny GEMMs of the decode step run their serial tile loop; 1, the default: the pipelined
+ *   one (wave-uniform control, next k-tile's LDS reads and folded-FFN fix under this tile's MFMAs).  Part of the key of
+ *   a captured graph; results are bit-identical either way.
  *   "profile_skip" = 1 | 2 | 3 (any time; results become meaningless): measurement hook of bench.py, leaves the self-attention
  *   (bit 0) and / or cross-attention (bit 1) launches out of the captured decode step, so that what a kernel costs the step is
  *   the difference between two timed generates.  0 restores the real step. */
@@ -244,6 +247,10 @@ int32_t amt_attn_decode_fold_fwd(const float* raw, int32_t ldq, float* kcache, f
                                  const float* ln_b, float* xn_out, float* o, int32_t B, int32_t H, int32_t hd,
                                  int32_t cap, const int32_t* pos_dev, int32_t n_keys, int32_t er_len, int32_t new_kv,
                                  float eps, float q_scale, void* stream);
+/* Bit of amt_decode_gemm_args.pro: run the kernel's serial tile loop (LDS read, fix, four MFMAs per k-tile, one after the other) instead
+ * of the pipelined one (next tile's reads and fix under this tile's MFMAs).  Same arithmetic in the same order: y_low / y_high are
+ * bit-identical either way. */
+#define AMT_GEMM_PRO_SERIAL_LOOP 0x100
 typedef struct amt_decode_gemm_args {
     const float* x;  int32_t ldx;          /* first K1 columns of the rows (all K when x2 is null) */
     const float* x2; int32_t ldx2;         /* remaining K - K1 columns, or null */
@@ -251,7 +258,7 @@ typedef struct amt_decode_gemm_args {
     const float* w_low;  const float* bias_low;  const float* resid; int32_t relu;   /* y_low = act(x . w_low^T + b (+ resid)) */
     const float* w_high; const float* bias_high;                                     /* y_high = [x | x2] . w_high^T + b_high */
     int32_t n_low, n_high;
-    int32_t pro;                           /* 1: folded-FFN prologue (see above) */
+    int32_t pro;                           /* 1: folded-FFN prologue (see above); | AMT_GEMM_PRO_SERIAL_LOOP: the serial tile loop */
     const float* fold_g; const float* fold_c; const float* ln_w; const float* ln_b;
     float* y_low; float* y_high;
     float* scratch_low; float* scratch_high;   /* packed copies of the weights, ceil(n/16)*16*K floats each */

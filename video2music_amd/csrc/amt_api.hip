@@ -111,10 +111,11 @@ struct amt_handle {
     bool fuse_head = true;               // amt_set_option("fuse_sampling_head"): inside a captured graph the head rides in the next step's first attention
     bool short_attn = true;              // amt_set_option("short_context_attn"): graphs whose every step fits one K/V batch use the short-context self-attention
     bool step_short = false;             // set by get_graph while it captures such a graph (eager steps keep the long kernels)
+    bool gemm_pipe = true;               // amt_set_option("gemm_tile_pipeline"): 0 = the skinny GEMMs of the decode step run the serial tile loop (DecodeGemmParams::serial_loop)
     bool plain_chain = false;            // amt_set_option("decode_chain_plain"), before the first amt_finalize: the 49-launch chain without folded LayerNorms
     bool gen_active = false;
     // graphs keyed by the parameters baked into the captured kernel arguments
-    struct GraphKey { int B, T, P, beam, mcN, mcC, S, nsteps, skip, pad, short_ctx, parity; float* logits; };
+    struct GraphKey { int B, T, P, beam, mcN, mcC, S, nsteps, skip, pad, short_ctx, parity, gemm_pipe, spare; float* logits; };      // (compared bytewise: an even number of ints, no padding)
     struct GraphEntry { GraphKey key; hipGraphExec_t exec; hipGraph_t graph; };
     std::vector<GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;    // capture-only stream (the caller's may be the legacy null stream)
@@ -254,6 +255,12 @@ struct StepProf {
 #define PROF_BEGIN() do { if (prof) prof->begin(); } while (0)
 #define PROF_END(c) do { if (prof) prof->end(c); } while (0)
 
+// every skinny GEMM of a decode step goes through here: the handle's choice of tile loop rides in the parameters
+int32_t launch_step_gemm(const amt_handle* h, DecodeGemmParams g, hipStream_t s) {
+    g.serial_loop = h->gemm_pipe ? 0 : 1;
+    return amt_launch_decode_gemm(g, s);
+}
+
 // One decode step with every LayerNorm folded through the projection behind it (fold.hip): per layer
 //   SA  self-attention; layers > 0 finish norm3 of the previous layer in the prologue (q, new k/v, residual row)
 //   G1  [u1 | q_raw]   = [o | r] . [Wo | Wc_a,W'_a]      out-proj + residual, and the raw cross-attention query
@@ -301,7 +308,7 @@ int32_t enqueue_decoder_step_folded(amt_handle* h, hipStream_t s, int step, Step
         g1.Wp = L.p_sao; g1.bias = L.sa_ob; g1.resid = r0; g1.ldr = d; g1.y = h->u1; g1.ldy = d;
         g1.n_split = d; g1.N = 2 * d; g1.Wp2 = L.pf_a; g1.bias2 = L.va + 2 * d; g1.y2 = h->qraw; g1.ldy2 = d;
         PROF_BEGIN();
-        if ((rc = amt_launch_decode_gemm(g1, s))) return rc;
+        if ((rc = launch_step_gemm(h, g1, s))) return rc;
         PROF_END(2);
         AttnDecodeParams x{};
         x.k = Kx; x.v = Vx; x.o = h->ob; x.B = B; x.H = H; x.hd = hd; x.cap = h->kx_rows; x.n_keys = h->encS;
@@ -317,7 +324,7 @@ int32_t enqueue_decoder_step_folded(amt_handle* h, hipStream_t s, int step, Step
         g2.Wp = L.p_cao; g2.bias = L.ca_ob; g2.resid = h->xb; g2.ldr = d; g2.y = h->u2; g2.ldy = d;
         g2.n_split = d; g2.N = d + dff; g2.Wp2 = L.pf_b; g2.bias2 = L.vb + 2 * dff; g2.y2 = h->hraw; g2.ldy2 = dff;
         PROF_BEGIN();
-        if ((rc = amt_launch_decode_gemm(g2, s))) return rc;
+        if ((rc = launch_step_gemm(h, g2, s))) return rc;
         PROF_END(2);
         DecodeGemmParams g3{};
         g3.B = B; g3.eps = LN_EPS; g3.scale = 1.f; g3.pro = 1; g3.x = h->hraw; g3.ldx = dff; g3.x2 = h->u2; g3.ldx2 = d;
@@ -326,7 +333,7 @@ int32_t enqueue_decoder_step_folded(amt_handle* h, hipStream_t s, int step, Step
         if (l + 1 < h->nl) { g3.N = 4 * d; g3.Wp2 = L.pf_c; g3.bias2 = L.vc + 6 * d; g3.y2 = h->qkvraw; g3.ldy2 = 3 * d; }
         else { g3.N = d + VS; g3.Wp2 = h->pf_s; g3.bias2 = h->vs + 2 * VS; g3.y2 = h->lraw; g3.ldy2 = VS; }     // raw logits for the sampling head
         PROF_BEGIN();
-        if ((rc = amt_launch_decode_gemm(g3, s))) return rc;
+        if ((rc = launch_step_gemm(h, g3, s))) return rc;
         PROF_END(2);
     }
     return 0;
@@ -352,7 +359,7 @@ int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, int step, StepProf* p
         g.mode = 1; g.y = h->qb; g.ldy = d; g.scale = qscale; g.scale_cols = d;
         g.kcache = Kc; g.vcache = Vc; g.H = H; g.hd = hd; g.cap = h->kv_rows; g.pos = pos_slot(h, step); g.d = d;
         PROF_BEGIN();
-        if ((rc = amt_launch_decode_gemm(g, s))) return rc;
+        if ((rc = launch_step_gemm(h, g, s))) return rc;
         PROF_END(2);
         const float* r0 = l == 0 ? h->x_in : h->xa;
         // K2: relative-position self-attention over the cache
@@ -369,14 +376,14 @@ int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, int step, StepProf* p
         o.B = B; o.eps = LN_EPS; o.scale = 1.f; o.x = h->ob; o.ldx = d; o.Wp = L.p_sao; o.bias = L.sa_ob; o.N = d; o.K = d;
         o.resid = r0; o.ldr = d; o.y = h->u1; o.ldy = d;
         PROF_BEGIN();
-        if ((rc = amt_launch_decode_gemm(o, s))) return rc;
+        if ((rc = launch_step_gemm(h, o, s))) return rc;
         PROF_END(2);
         // K4: LN1 + cross-attention query projection
         DecodeGemmParams c{};
         c.B = B; c.eps = LN_EPS; c.x = h->u1; c.ldx = d; c.Wp = L.p_caq; c.bias = L.ca_b; c.N = d; c.K = d;
         c.ln_w = L.n1w; c.ln_b = L.n1b; c.xn = h->xb; c.scale = qscale; c.scale_cols = d; c.y = h->qb; c.ldy = d;
         PROF_BEGIN();
-        if ((rc = amt_launch_decode_gemm(c, s))) return rc;
+        if ((rc = launch_step_gemm(h, c, s))) return rc;
         PROF_END(2);
         // K5: cross-attention over the clip's video keys
         AttnDecodeParams x{};
@@ -391,14 +398,14 @@ int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, int step, StepProf* p
         o2.B = B; o2.eps = LN_EPS; o2.scale = 1.f; o2.x = h->ob; o2.ldx = d; o2.Wp = L.p_cao; o2.bias = L.ca_ob; o2.N = d; o2.K = d;
         o2.resid = h->xb; o2.ldr = d; o2.y = h->u2; o2.ldy = d;
         PROF_BEGIN();
-        if ((rc = amt_launch_decode_gemm(o2, s))) return rc;
+        if ((rc = launch_step_gemm(h, o2, s))) return rc;
         PROF_END(2);
         // K7: LN2 + FFN up + ReLU
         DecodeGemmParams f1{};
         f1.B = B; f1.eps = LN_EPS; f1.scale = 1.f; f1.x = h->u2; f1.ldx = d; f1.Wp = L.p_l1; f1.bias = L.l1b; f1.N = dff; f1.K = d;
         f1.ln_w = L.n2w; f1.ln_b = L.n2b; f1.xn = h->xc; f1.relu = 1; f1.y = h->hb; f1.ldy = dff;
         PROF_BEGIN();
-        if ((rc = amt_launch_decode_gemm(f1, s))) return rc;
+        if ((rc = launch_step_gemm(h, f1, s))) return rc;
         PROF_END(2);
         // K8: FFN down + residual
         DecodeGemmParams f2{};
@@ -406,7 +413,7 @@ int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, int step, StepProf* p
         f2.resid = h->xc; f2.ldr = d; f2.y = h->u3; f2.ldy = d;
         if (dff <= 1536) {
             PROF_BEGIN();
-            if ((rc = amt_launch_decode_gemm(f2, s))) return rc;
+            if ((rc = launch_step_gemm(h, f2, s))) return rc;
             PROF_END(2);
         } else {
             // dim_feedforward beyond the skinny GEMM's 1536 staged columns: column ranges of 1024, every range adding onto the sum of
@@ -416,7 +423,7 @@ int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, int step, StepProf* p
                 c.x = h->hb + k0; c.K = std::min(FFN_CHUNK, dff - k0); c.Wp = L.p_l2 + (size_t)cdiv(d, 16) * 16 * k0;
                 if (k0) { c.bias = nullptr; c.resid = h->u3; }
                 PROF_BEGIN();
-                if ((rc = amt_launch_decode_gemm(c, s))) return rc;
+                if ((rc = launch_step_gemm(h, c, s))) return rc;
                 PROF_END(2);
             }
         }
@@ -429,7 +436,7 @@ int32_t get_graph(amt_handle* h, int first_pos, int nsteps, float* logits_out, h
     // of keys, every self-attention of the graph is the short-context instantiation (a graph that straddles the limit keeps the long one)
     const bool short_ctx = h->short_attn && first_pos + nsteps <= amt_attn_decode_stride(h->hd);
     amt_handle::GraphKey key{h->genB, h->genT, h->genP, h->beam, h->mcN, h->mcC, h->encS, nsteps, h->skip_mask | (h->fuse_head ? 4 : 0), h->use_unif,
-                             short_ctx ? 1 : 0, first_pos & 1, logits_out};
+                             short_ctx ? 1 : 0, first_pos & 1, h->gemm_pipe ? 1 : 0, 0, logits_out};
     for (auto& g : h->graphs)
         if (memcmp(&g.key, &key, sizeof(key)) == 0) { *out = g.exec; return 0; }
     hipGraph_t graph;
@@ -742,6 +749,10 @@ extern "C" int32_t amt_set_option(amt_handle* h, const char* name, int32_t value
     }
     if (strcmp(name, "short_context_attn") == 0) {           // 0: every captured graph uses the long-context self-attention (A/B and parity tests)
         h->short_attn = value != 0;
+        return 0;
+    }
+    if (strcmp(name, "gemm_tile_pipeline") == 0) {           // 0: the decode step's skinny GEMMs keep the serial tile loop (A/B and bit-identity tests); part of the graph key
+        h->gemm_pipe = value != 0;
         return 0;
     }
     if (strcmp(name, "profile_skip") == 0) {                 // measurement hook of bench.py: leave a kernel class out of the captured step

@@ -81,7 +81,111 @@ __device__ __forceinline__ int glu_pair_bias_col(int n, int N) { const int c = n
 #define STAMP(i) do { } while (0)
 #endif
 
-template <int KCH, bool FULL, int PRO>
+// ---- the tile loop of decode_gemm_kernel<.., PIPE = true> (round 5) ----
+// The folded-FFN fix of one A fragment (PRO 2): two fused multiply-adds per element with mu*rstd per row,
+//   raw half        relu(a*rstd + (c - mu*rstd*g))        LayerNorm half   (a*rstd - mu*rstd)*gamma + beta
+// operands and nesting as in the serial loop below (bit-identical).  AMT_FIXUP_PACKED spells it as the serial loop does, in packed pairs
+// (v_pk_fma_f32); the default is scalar fmaf: beside MFMAs a packed f32 op costs more than the two plain ones it replaces.
+// SIDE 0: raw half, 1: LayerNorm half, 2: `raw` (wave-uniform) chooses per tile -- both forms are computed and one is selected, so the
+// one wave whose tile range straddles K1 stays branch-free too.
+template <int SIDE>
+__device__ __forceinline__ float4 ffn_fix(const float4 a, const float4 g, const float4 h, float rs, float nm, bool raw) {
+    float4 r = a, l = a;
+#ifdef AMT_FIXUP_PACKED
+    const f32x2 a_lo = {a.x, a.y}, a_hi = {a.z, a.w}, g_lo = {g.x, g.y}, g_hi = {g.z, g.w}, h_lo = {h.x, h.y}, h_hi = {h.z, h.w};
+    const f32x2 rs2 = {rs, rs}, nm2 = {nm, nm};
+    if (SIDE != 1) {
+        const f32x2 t_lo = __builtin_elementwise_fma(a_lo, rs2, __builtin_elementwise_fma(nm2, g_lo, h_lo));
+        const f32x2 t_hi = __builtin_elementwise_fma(a_hi, rs2, __builtin_elementwise_fma(nm2, g_hi, h_hi));
+        r = make_float4(fmaxf(t_lo.x, 0.f), fmaxf(t_lo.y, 0.f), fmaxf(t_hi.x, 0.f), fmaxf(t_hi.y, 0.f));
+    }
+    if (SIDE != 0) {
+        const f32x2 t_lo = __builtin_elementwise_fma(__builtin_elementwise_fma(a_lo, rs2, nm2), g_lo, h_lo);
+        const f32x2 t_hi = __builtin_elementwise_fma(__builtin_elementwise_fma(a_hi, rs2, nm2), g_hi, h_hi);
+        l = make_float4(t_lo.x, t_lo.y, t_hi.x, t_hi.y);
+    }
+#else
+    if (SIDE != 1) {
+        r.x = fmaxf(fmaf(a.x, rs, fmaf(nm, g.x, h.x)), 0.f); r.y = fmaxf(fmaf(a.y, rs, fmaf(nm, g.y, h.y)), 0.f);
+        r.z = fmaxf(fmaf(a.z, rs, fmaf(nm, g.z, h.z)), 0.f); r.w = fmaxf(fmaf(a.w, rs, fmaf(nm, g.w, h.w)), 0.f);
+    }
+    if (SIDE != 0) {
+        l.x = fmaf(fmaf(a.x, rs, nm), g.x, h.x); l.y = fmaf(fmaf(a.y, rs, nm), g.y, h.y);
+        l.z = fmaf(fmaf(a.z, rs, nm), g.z, h.z); l.w = fmaf(fmaf(a.w, rs, nm), g.w, h.w);
+    }
+#endif
+    if (SIDE == 0) return r;
+    if (SIDE == 1) return l;
+    return raw ? r : l;
+}
+
+// A wave that owns all KCH tiles walks them in ONE basic block, one tile ahead: tile i+1's ds_read_b128 (A fragment; PRO 2: g and h too)
+// are requested before tile i's four MFMAs and its fix is finished in their shadow, in a second register set.  The group barriers pin
+// that interleave (the scheduler otherwise sinks each read to its use).  One accumulator chain, tiles and .x .y .z .w in the serial order.
+template <int KCH, int PRO, int SIDE>
+__device__ __forceinline__ f32x4 tiles_pipelined(const float* xa, const float* fg, int K, const float4 (&wt)[KCH], float rs, float nm, int k0, int K1) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float4 a[2], g[2], h[2];
+    a[0] = ld4(xa);
+    if (PRO == 2) {
+        g[0] = ld4(fg); h[0] = ld4(fg + K);
+        a[0] = ffn_fix<SIDE>(a[0], g[0], h[0], rs, nm, k0 < K1);
+    }
+    __builtin_amdgcn_sched_barrier(0);               // (the groups below must not pick tile 0's reads and fix)
+#pragma unroll
+    for (int i = 0; i < KCH; ++i) {
+        const int c = i & 1, n = c ^ 1;
+        if (i + 1 < KCH) {
+            a[n] = ld4(xa + (i + 1) * 16);
+            if (PRO == 2) { g[n] = ld4(fg + (i + 1) * 16); h[n] = ld4(fg + K + (i + 1) * 16); }
+        }
+        const float4 w = wt[i];
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c].x, w.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c].y, w.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c].z, w.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c].w, w.w, acc, 0, 0, 0);
+        if (PRO == 2 && i + 1 < KCH) a[n] = ffn_fix<SIDE>(a[n], g[n], h[n], rs, nm, k0 + (i + 1) * 16 < K1);
+        if (i + 1 < KCH) {
+            __builtin_amdgcn_sched_group_barrier(0x100, PRO == 2 ? 3 : 1, 0);      // next tile's LDS reads
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                      // MFMA .x .y
+            if (PRO == 2) __builtin_amdgcn_sched_group_barrier(0x002, SIDE == 2 ? 12 : 6, 0);      // first half of the next fix
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                      // MFMA .z
+            if (PRO == 2) __builtin_amdgcn_sched_group_barrier(0x002, SIDE == 2 ? 12 : 6, 0);      // second half
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                      // MFMA .w
+        }
+    }
+    return acc;
+}
+
+// A wave that owns 0 < nown < KCH tiles: one scalar branch per tile, the next tile's reads still one ahead.  (The read-ahead behind the
+// last owned tile touches at most 16 floats past its row / vector: inside the LDS allocation -- the partial-tile region follows --
+// and never used.)
+template <int KCH, int PRO, int SIDE>
+__device__ __forceinline__ f32x4 tiles_partial(const float* xa, const float* fg, int K, const float4 (&wt)[KCH], float rs, float nm, int k0, int K1, int nown) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float4 a_n = ld4(xa), g_n = a_n, h_n = a_n;
+    if (PRO == 2) { g_n = ld4(fg); h_n = ld4(fg + K); }
+#pragma unroll
+    for (int i = 0; i < KCH - 1; ++i) {
+        if (i < nown) {
+            float4 a0 = a_n;
+            const float4 g = g_n, h = h_n;
+            a_n = ld4(xa + (i + 1) * 16);
+            if (PRO == 2) { g_n = ld4(fg + (i + 1) * 16); h_n = ld4(fg + K + (i + 1) * 16); }
+            if (PRO == 2) a0 = ffn_fix<SIDE>(a0, g, h, rs, nm, k0 + i * 16 < K1);
+            const float4 w = wt[i];
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, w.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, w.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, w.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, w.w, acc, 0, 0, 0);
+        }
+    }
+    return acc;
+}
+
+// PIPE: the tile loop with wave-uniform control and one tile of read-ahead (round 5); false keeps the serial loop of rounds 2-4
+// (DecodeGemmParams::serial_loop: A/B and the bit-identity tests)
+template <int KCH, bool FULL, int PRO, bool PIPE>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
 #ifdef AMT_STAMPS
@@ -289,8 +393,16 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
         if (FULL || i < K) st4(xs + wave * LD + i, v[c]);    // (rows >= B hold a copy of row B-1; their outputs are never stored)
     }
     STAMP(2);
+#ifdef AMT_STAMPS
+    if (tid == 0) *reinterpret_cast<unsigned long long*>(red + NW * 256) = 0;      // the matrix phase's end stamp (below)
+#endif
     __syncthreads();
     STAMP(3);
+#ifdef AMT_STAMPS
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long clk3 = __builtin_amdgcn_s_memtime();                  // shader-clock counter, against the 100 MHz stamps
+    __builtin_amdgcn_sched_barrier(0);
+#endif
 
     // ---- 4. epilogue operands: issued behind the prologue so that no register of the prologue's arithmetic sits
     // next to a pending load (packed VALU ops read register pairs).  Absent operands read a zero word instead of
@@ -324,6 +436,26 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
 
     // ---- main: 4 MFMAs per k-tile ----
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (PIPE) {
+        // The wave index through readfirstlane: the compiler then knows that the first tile, the tile count and the side of K1 are
+        // wave-uniform -- scalar branches (none at all for a wave that owns KCH tiles) and the uniform address parts in SGPRs.
+        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const int kt0s = wv * tpw, nown = min(tpw, kt_n - kt0s);      // tiles kt0s .. kt0s + nown - 1 (none when nown <= 0)
+        const float* xa = xs + (lane & 15) * LD + 4 * (lane >> 4) + kt0s * 16;
+        const float* fg = fgs + 4 * (lane >> 4) + kt0s * 16;
+        const float f_nm = -f_mu * f_rs;
+        if (nown == KCH) {
+            // every wave of the high / unsplit column tiles at K = KCH * 256
+            if (PRO != 2 || (kt0s + KCH) * 16 <= K1) acc = tiles_pipelined<KCH, PRO, 0>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1);
+            else if (kt0s * 16 >= K1) acc = tiles_pipelined<KCH, PRO, 1>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1);
+            else acc = tiles_pipelined<KCH, PRO, 2>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1);
+        } else if (nown > 0) {
+            // fewer tiles (low-column tiles of a split launch, ragged K)
+            if (PRO != 2 || (kt0s + nown) * 16 <= K1) acc = tiles_partial<KCH, PRO, 0>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1, nown);
+            else if (kt0s * 16 >= K1) acc = tiles_partial<KCH, PRO, 1>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1, nown);
+            else acc = tiles_partial<KCH, PRO, 2>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1, nown);
+        }
+    } else {                                         // the serial loop of rounds 2-4, kept as it was (indentation included)
     const float* xa = xs + (lane & 15) * LD + kt0 * 16 + 4 * (lane >> 4);
 #pragma unroll
     for (int i = 0; i < KCH; ++i) {
@@ -356,16 +488,32 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, w.w, acc, 0, 0, 0);
         }
     }
+    }
     // ---- cross-wave reduction in fixed order ----
 #ifdef AMT_STAMPS
-    if (acc[0] == 1.2345e-30f) st_[7] = 1;          // the stamp must follow the MFMA results, not just their issue
+    if (acc[0] == 1.2345e-30f) st_[6] = 1;          // the stamp must follow the MFMA results, not just their issue
 #endif
     STAMP(4);
+#ifdef AMT_STAMPS
+    // end of the workgroup's matrix phase: the latest end-of-MFMA stamp of its 16 waves (one LDS max per wave, in the word behind the partial tiles)
+    unsigned long long* wg_end = reinterpret_cast<unsigned long long*>(red + NW * 256);
+    if (lane == 0) atomicMax(wg_end, st_[4]);
+#endif
     float* rw = red + wave * 256;
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) rw[rr * 64 + lane] = acc[rr];
     __syncthreads();
     STAMP(5);
+#ifdef AMT_STAMPS
+    // slot 7: high word = the workgroup's matrix phase (staging barrier -> last wave's MFMA results) in 10 ns ticks, low word = shader
+    // clocks that wave 0 counted between STAMP 3 and STAMP 5 (their ratio to st[5] - st[3] is the in-kernel clock under MFMA load)
+    {
+        __builtin_amdgcn_sched_barrier(0);
+        const unsigned long long clk5 = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+        st_[7] = ((*wg_end - st_[3]) << 32) | ((clk5 - clk3) & 0xffffffffull);
+    }
+#endif
     float val = 0.f;
     if (tid < 256) {
 #pragma unroll
@@ -414,8 +562,8 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
 #endif
 }
 
-template <int KCH, bool FULL, int PRO>
-int32_t launch_one(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
+template <int KCH, bool FULL, int PRO, bool PIPE>
+int32_t launch_one_loop(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
     // > 64 KiB of dynamic LDS needs the opt-in (gfx950: 160 KiB per CU).  The attribute belongs to the (function, device)
     // pair, so the flag is kept per device ordinal and per instantiation, under a lock (host threads may launch concurrently)
     static bool attr_set[64] = {false};
@@ -426,11 +574,11 @@ int32_t launch_one(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
     {
         std::lock_guard<std::mutex> lock(mu);
         if (!attr_set[dev]) {
-            AMT_HIP(hipFuncSetAttribute((const void*)decode_gemm_kernel<KCH, FULL, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            AMT_HIP(hipFuncSetAttribute((const void*)decode_gemm_kernel<KCH, FULL, PRO, PIPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             attr_set[dev] = true;
         }
     }
-    hipLaunchKernelGGL((decode_gemm_kernel<KCH, FULL, PRO>), dim3(cdiv(p.N, 16), cdiv(p.B, MT), p.n_groups > 1 ? p.n_groups : 1), dim3(NW * 64), lds, stream, p);
+    hipLaunchKernelGGL((decode_gemm_kernel<KCH, FULL, PRO, PIPE>), dim3(cdiv(p.N, 16), cdiv(p.B, MT), p.n_groups > 1 ? p.n_groups : 1), dim3(NW * 64), lds, stream, p);
     AMT_LAUNCH_CHECK();
     return 0;
 }
@@ -442,6 +590,14 @@ int32_t launch_one(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
 // normalised once, and every thread takes part in the final reduction (thread group j reduces tile j).  Same arithmetic per output
 // as decode_gemm_kernel (same k order inside a wave, same fixed wave order in the reduction): results are bit-identical.
 // Plain single-source products only: PRO 0 / 1, packed weights, mode 0, no column split, no rotary epilogue.
+// The pipelined tile loop serves the plain and the folded-FFN prologue (PRO 0 / 2: every skinny GEMM of the folded decode chain); the
+// other prologues keep the serial loop (PRO 4 / 5 sit at 114 - 126 VGPRs of the 128 a 16-wave workgroup may use)
+template <int KCH, bool FULL, int PRO>
+int32_t launch_one(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
+    if constexpr (PRO == 0 || PRO == 2) { if (!p.serial_loop) return launch_one_loop<KCH, FULL, PRO, true>(p, lds, stream); }
+    return launch_one_loop<KCH, FULL, PRO, false>(p, lds, stream);
+}
+
 template <int KCH, int PRO, int NTW>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_wide_kernel(DecodeGemmParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -852,7 +1008,11 @@ int32_t amt_launch_decode_gemm(const DecodeGemmParams& p_in, hipStream_t stream)
     }
     // staged rows | folded-FFN vectors | the waves' partial tiles
     const size_t lds = (size_t)MT * (p.K + XPAD) * sizeof(float) + (p.pro == 1 ? (size_t)(2 * p.K + 2 * MT) * sizeof(float) : 0) +
-                       (p.pro == 2 ? (size_t)(2 * p.K + 2 * p.K1) * sizeof(float) : 0) + (size_t)NW * 256 * sizeof(float);
+                       (p.pro == 2 ? (size_t)(2 * p.K + 2 * p.K1) * sizeof(float) : 0) + (size_t)NW * 256 * sizeof(float)
+#ifdef AMT_STAMPS
+                       + 16                          // the matrix phase's end stamp
+#endif
+        ;
     int32_t rc;
     switch (p.K) {
         case 256: rc = launch_variant<1, true>(p, lds, stream); break;

@@ -159,9 +159,13 @@ struct DecodeGemmParams {
     const float* rope; int rope_cols, rope_dim;
     const float* zero;          // set by the launcher: zero words in global memory
     // diagnostic builds only (-DAMT_STAMPS, tools/ubench_chain.cpp): [workgroup][8] s_memrealtime stamps (100 MHz) of the
-    // kernel's phases; null and unused in the library build
+    // kernel's phases; null and unused in the library build.  Slot 7: (matrix phase of the workgroup, staging barrier -> its last wave's MFMA
+    // results, in stamp ticks) << 32 | shader clocks (s_memtime) wave 0 counted between stamps 3 and 5
     const float* ln2_w; const float* ln2_b;   // a second LayerNorm applied to the normalised rows (norm3 of the last layer, then decoder.norm)
     unsigned long long* stamps;
+    // 1: the serial tile loop of rounds 2-4 (LDS read, fix, wait, four MFMAs per tile under a lane predicate) instead of the pipelined one
+    // (wave-uniform control, next tile's reads and fix under this tile's MFMAs).  Same arithmetic in the same order: bit-identical results
+    int serial_loop;
 };
 int32_t amt_launch_decode_gemm(const DecodeGemmParams& p, hipStream_t stream);
 // allocates the per-device zero words (hipMalloc): call once outside any stream capture

@@ -171,7 +171,9 @@ extern "C" int32_t amt_decode_gemm_ex_fwd(const amt_decode_gemm_args* a, void* s
     DecodeGemmParams g{};
     g.B = a->B; g.eps = a->eps; g.scale = 1.f; g.x = a->x; g.ldx = a->ldx; g.x2 = a->x2; g.ldx2 = a->ldx2; g.K1 = a->K1; g.K = a->K;
     g.Wp = a->scratch_low; g.bias = a->bias_low; g.resid = a->resid; g.ldr = a->n_low; g.relu = a->relu; g.y = a->y_low; g.ldy = a->n_low;
-    g.pro = a->pro; g.fold_g = a->fold_g; g.fold_c = a->fold_c; g.ln_w = a->ln_w; g.ln_b = a->ln_b;
+    AMT_CHECK_ARG((a->pro & ~AMT_GEMM_PRO_SERIAL_LOOP) == 0 || (a->pro & ~AMT_GEMM_PRO_SERIAL_LOOP) == 1, "amt_decode_gemm_ex_fwd: pro takes 0 or 1 (| AMT_GEMM_PRO_SERIAL_LOOP)");
+    g.serial_loop = (a->pro & AMT_GEMM_PRO_SERIAL_LOOP) ? 1 : 0;
+    g.pro = a->pro & ~AMT_GEMM_PRO_SERIAL_LOOP; g.fold_g = a->fold_g; g.fold_c = a->fold_c; g.ln_w = a->ln_w; g.ln_b = a->ln_b;
     g.N = a->n_low + a->n_high;
     if (a->x2) { g.n_split = a->n_low; g.Wp2 = a->scratch_high; g.bias2 = a->bias_high; g.y2 = a->y_high; g.ldy2 = a->n_high; }
     return amt_launch_decode_gemm(g, s);
