@@ -53,19 +53,98 @@ __device__ __forceinline__ float sq4(const float4 a, float m) {
     return (lo.x + lo.y) + (hi.x + hi.y);
 }
 
-// KCH = float4 chunks per lane and row (K <= KCH*256) = weight tiles per wave; FULL: K == KCH*256, no lane
-// predicates; PRO: 0 plain rows, 1 LayerNorm prologue, 2 folded-FFN prologue, 3 gated-linear-unit prologue, 4 two LayerNorms,
-// 5 folded gated FFN prologue (2 with a gate: up * silu(gate) in place of the ReLU).
-//
+// What the kernel does to its input rows before the product (launch_variant maps DecodeGemmParams onto it)
+enum class Pro {
+    Plain,       // rows as they are
+    LayerNorm,   // LayerNorm prologue
+    FoldedFfn,   // folded-FFN prologue: [ relu((raw - mu*g)*rstd + c) | LayerNorm(u) ]
+    Glu,         // gated-linear-unit prologue: x * silu(gate)
+    LayerNorm2,  // two LayerNorms in a row (norm3 of the last layer, then decoder.norm)
+    FoldedGlu,   // folded gated FFN prologue (FoldedFfn with a gate: up * silu(gate) in place of the ReLU)
+};
+constexpr bool pro_layernorm(Pro p) { return p == Pro::LayerNorm || p == Pro::LayerNorm2; }
+constexpr bool pro_folded(Pro p) { return p == Pro::FoldedFfn || p == Pro::FoldedGlu; }      // per-column vectors handed over through LDS
+constexpr bool pro_gated(Pro p) { return p == Pro::Glu || p == Pro::FoldedGlu; }
+
+// KCH = float4 chunks per lane and row (K <= KCH*256) = weight tiles per wave; FULL: K == KCH*256, no lane predicates.
+// First column of chunk c in this lane, and the same clamped into the row (out-of-range lanes re-read the last float4 and discard it)
+__device__ __forceinline__ int chunk_col(int c, int lane) { return (c * 64 + lane) * 4; }
+template <bool FULL>
+__device__ __forceinline__ int chunk_col(int c, int lane, int K) { const int i = chunk_col(c, lane); return FULL ? i : min(i, K - 4); }
+
+__device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
+// the LayerNorm of one float4: (v - mean) * rstd * gamma + beta
+__device__ __forceinline__ float4 ln4(const float4 v, float mean, float rstd, const float4 g, const float4 h) {
+    return make_float4((v.x - mean) * rstd * g.x + h.x, (v.y - mean) * rstd * g.y + h.y, (v.z - mean) * rstd * g.z + h.z, (v.w - mean) * rstd * g.w + h.w);
+}
+// the gated-linear-unit prologue of one float4: u * silu(g) (um = 1, uo = 0), or silu(g) alone (um = 0, uo = 1)
+__device__ __forceinline__ float4 glu4(const float4 v, const float4 g, float um, float uo) {
+    return make_float4((v.x * um + uo) * silu(g.x), (v.y * um + uo) * silu(g.y), (v.z * um + uo) * silu(g.z), (v.w * um + uo) * silu(g.w));
+}
+
+// Two-pass statistics over n columns of the row a wave holds in v.  MUL: w(c) is a 0/1 float weight per chunk and multiplies the
+// chunk's sums (the folded prologues: branch-free); otherwise w(c) is a predicate and guards them (LayerNorm: compile-time true when
+// the row is full).  It takes n, not 1/n, and divides behind the first sum: a reciprocal formed by the caller is scheduled in front of
+// the sums and moves a wait of the folded-FFN prologue (profiles/r06_decode_gemm_refactor_codegen.txt).
+struct RowStats { float mean, rstd; };
+template <bool MUL, int KCH, typename F>
+__device__ __forceinline__ RowStats row_stats(const float4 (&v)[KCH], F w, float n, float eps) {
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) {
+        if constexpr (MUL) s += w(c) * sum4(v[c]);
+        else if (w(c)) s += sum4(v[c]);
+    }
+    const float inv_n = 1.0f / n;
+    const float mean = wave_sum(s) * inv_n;
+    float q = 0.f;
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) {
+        if constexpr (MUL) q += w(c) * sq4(v[c], mean);
+        else if (w(c)) q += sq4(v[c], mean);
+    }
+    return {mean, rsqrtf(wave_sum(q) * inv_n + eps)};
+}
+
+// the LayerNorm vectors' chunks of this lane
+template <int KCH, bool FULL>
+__device__ __forceinline__ void load_ln(float4 (&g)[KCH], float4 (&h)[KCH], const float* w, const float* b, int lane, int K) {
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) {
+        const int ic = chunk_col<FULL>(c, lane, K);
+        g[c] = ld4(w + ic);
+        h[c] = ld4(b + ic);
+    }
+}
+
+// the four MFMAs of one 16 x 16 weight tile: one accumulator chain, .x .y .z .w
+__device__ __forceinline__ f32x4 mfma_tile(const float4 a, const float4 w, f32x4 acc) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w.w, acc, 0, 0, 0);
+    return acc;
+}
+// a wave's partial tile into its [4 r][64 lanes] slot, and the fixed-order sum of the 16 waves' partials for output e
+__device__ __forceinline__ void store_partials(float* rw, const f32x4 acc, int lane) {
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) rw[rr * 64 + lane] = acc[rr];
+}
+__device__ __forceinline__ float sum_partials(const float* red, int e) {
+    float val = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) val += red[w * 256 + e];
+    return val;
+}
 
 // epilogue of a paired gate | up tile (DecodeGemmParams::glu_pair): lanes 0-7 of a 16-lane row hold the gate columns, lanes 8-15 the up
 // columns of the same 8 hidden columns; every lane gets up * silu(gate), the up lanes store it
 __device__ __forceinline__ float glu_pair_value(float val, int c) {
     const float other = __shfl_xor(val, 8, 64);
     const float g = c < 8 ? val : other, u = c < 8 ? other : val;
-    return u * (g / (1.0f + __expf(-g)));
+    return u * silu(g);
 }
-__device__ __forceinline__ float act(float v, int relu) { return relu == 1 ? fmaxf(v, 0.f) : relu == 2 ? v / (1.0f + __expf(-v)) : v; }
+__device__ __forceinline__ float act(float v, int relu) { return relu == 1 ? fmaxf(v, 0.f) : relu == 2 ? silu(v) : v; }
 // column of the stacked bias that belongs to interleaved column n (N = stacked width)
 __device__ __forceinline__ int glu_pair_bias_col(int n, int N) { const int c = n & 15; return (c < 8 ? 0 : N / 2 - 8) + (n >> 4) * 8 + c; }
 
@@ -81,53 +160,62 @@ __device__ __forceinline__ int glu_pair_bias_col(int n, int N) { const int c = n
 #define STAMP(i) do { } while (0)
 #endif
 
-// ---- the tile loop of decode_gemm_kernel<.., PIPE = true> (round 5) ----
-// The folded-FFN fix of one A fragment (PRO 2): two fused multiply-adds per element with mu*rstd per row,
+// The folded-FFN fix of one A fragment (Pro::FoldedFfn).  It is VALU-bound (16 x 1536 elements per workgroup, every workgroup of the
+// launch redoes them: with (a - mu*g)*rstd + c spelled as mul / sub / mul / add / max the fix cost 0.75 us of a 7.5 us launch), so each
+// half is two fused multiply-adds per element with nm = -mu*rstd per row,
 //   raw half        relu(a*rstd + (c - mu*rstd*g))        LayerNorm half   (a*rstd - mu*rstd)*gamma + beta
-// operands and nesting as in the serial loop below (bit-identical).  AMT_FIXUP_PACKED spells it as the serial loop does, in packed pairs
-// (v_pk_fma_f32); the default is scalar fmaf: beside MFMAs a packed f32 op costs more than the two plain ones it replaces.
+// The two spellings are bit-identical.  PACKED issues packed pairs (v_pk_fma_f32): the serial loop's form, and the pipelined loop's
+// under AMT_FIXUP_PACKED; the pipelined loop's default is scalar fmaf: beside MFMAs a packed f32 op costs more than the two plain ones
+// it replaces.
 // SIDE 0: raw half, 1: LayerNorm half, 2: `raw` (wave-uniform) chooses per tile -- both forms are computed and one is selected, so the
 // one wave whose tile range straddles K1 stays branch-free too.
-template <int SIDE>
+#ifdef AMT_FIXUP_PACKED
+constexpr bool FIXUP_PACKED = true;
+#else
+constexpr bool FIXUP_PACKED = false;
+#endif
+template <int SIDE, bool PACKED = FIXUP_PACKED>
 __device__ __forceinline__ float4 ffn_fix(const float4 a, const float4 g, const float4 h, float rs, float nm, bool raw) {
     float4 r = a, l = a;
-#ifdef AMT_FIXUP_PACKED
-    const f32x2 a_lo = {a.x, a.y}, a_hi = {a.z, a.w}, g_lo = {g.x, g.y}, g_hi = {g.z, g.w}, h_lo = {h.x, h.y}, h_hi = {h.z, h.w};
-    const f32x2 rs2 = {rs, rs}, nm2 = {nm, nm};
-    if (SIDE != 1) {
-        const f32x2 t_lo = __builtin_elementwise_fma(a_lo, rs2, __builtin_elementwise_fma(nm2, g_lo, h_lo));
-        const f32x2 t_hi = __builtin_elementwise_fma(a_hi, rs2, __builtin_elementwise_fma(nm2, g_hi, h_hi));
-        r = make_float4(fmaxf(t_lo.x, 0.f), fmaxf(t_lo.y, 0.f), fmaxf(t_hi.x, 0.f), fmaxf(t_hi.y, 0.f));
+    if constexpr (PACKED) {
+        const f32x2 a_lo = {a.x, a.y}, a_hi = {a.z, a.w}, g_lo = {g.x, g.y}, g_hi = {g.z, g.w}, h_lo = {h.x, h.y}, h_hi = {h.z, h.w};
+        const f32x2 rs2 = {rs, rs}, nm2 = {nm, nm};
+        if (SIDE != 1) {
+            const f32x2 t_lo = __builtin_elementwise_fma(a_lo, rs2, __builtin_elementwise_fma(nm2, g_lo, h_lo));
+            const f32x2 t_hi = __builtin_elementwise_fma(a_hi, rs2, __builtin_elementwise_fma(nm2, g_hi, h_hi));
+            r = make_float4(fmaxf(t_lo.x, 0.f), fmaxf(t_lo.y, 0.f), fmaxf(t_hi.x, 0.f), fmaxf(t_hi.y, 0.f));
+        }
+        if (SIDE != 0) {
+            const f32x2 t_lo = __builtin_elementwise_fma(__builtin_elementwise_fma(a_lo, rs2, nm2), g_lo, h_lo);
+            const f32x2 t_hi = __builtin_elementwise_fma(__builtin_elementwise_fma(a_hi, rs2, nm2), g_hi, h_hi);
+            l = make_float4(t_lo.x, t_lo.y, t_hi.x, t_hi.y);
+        }
+    } else {
+        if (SIDE != 1) {
+            r.x = fmaxf(fmaf(a.x, rs, fmaf(nm, g.x, h.x)), 0.f); r.y = fmaxf(fmaf(a.y, rs, fmaf(nm, g.y, h.y)), 0.f);
+            r.z = fmaxf(fmaf(a.z, rs, fmaf(nm, g.z, h.z)), 0.f); r.w = fmaxf(fmaf(a.w, rs, fmaf(nm, g.w, h.w)), 0.f);
+        }
+        if (SIDE != 0) {
+            l.x = fmaf(fmaf(a.x, rs, nm), g.x, h.x); l.y = fmaf(fmaf(a.y, rs, nm), g.y, h.y);
+            l.z = fmaf(fmaf(a.z, rs, nm), g.z, h.z); l.w = fmaf(fmaf(a.w, rs, nm), g.w, h.w);
+        }
     }
-    if (SIDE != 0) {
-        const f32x2 t_lo = __builtin_elementwise_fma(__builtin_elementwise_fma(a_lo, rs2, nm2), g_lo, h_lo);
-        const f32x2 t_hi = __builtin_elementwise_fma(__builtin_elementwise_fma(a_hi, rs2, nm2), g_hi, h_hi);
-        l = make_float4(t_lo.x, t_lo.y, t_hi.x, t_hi.y);
-    }
-#else
-    if (SIDE != 1) {
-        r.x = fmaxf(fmaf(a.x, rs, fmaf(nm, g.x, h.x)), 0.f); r.y = fmaxf(fmaf(a.y, rs, fmaf(nm, g.y, h.y)), 0.f);
-        r.z = fmaxf(fmaf(a.z, rs, fmaf(nm, g.z, h.z)), 0.f); r.w = fmaxf(fmaf(a.w, rs, fmaf(nm, g.w, h.w)), 0.f);
-    }
-    if (SIDE != 0) {
-        l.x = fmaf(fmaf(a.x, rs, nm), g.x, h.x); l.y = fmaf(fmaf(a.y, rs, nm), g.y, h.y);
-        l.z = fmaf(fmaf(a.z, rs, nm), g.z, h.z); l.w = fmaf(fmaf(a.w, rs, nm), g.w, h.w);
-    }
-#endif
     if (SIDE == 0) return r;
     if (SIDE == 1) return l;
     return raw ? r : l;
 }
 
-// A wave that owns all KCH tiles walks them in ONE basic block, one tile ahead: tile i+1's ds_read_b128 (A fragment; PRO 2: g and h too)
-// are requested before tile i's four MFMAs and its fix is finished in their shadow, in a second register set.  The group barriers pin
+// ---- the tile loop of decode_gemm_kernel<.., PIPE = true> ----
+// A wave that owns all KCH tiles walks them in ONE basic block, one tile ahead: tile i+1's ds_read_b128 (A fragment; FoldedFfn: g and h
+// too) are requested before tile i's four MFMAs and its fix is finished in their shadow, in a second register set.  The group barriers pin
 // that interleave (the scheduler otherwise sinks each read to its use).  One accumulator chain, tiles and .x .y .z .w in the serial order.
-template <int KCH, int PRO, int SIDE>
+template <int KCH, Pro PRO, int SIDE>
 __device__ __forceinline__ f32x4 tiles_pipelined(const float* xa, const float* fg, int K, const float4 (&wt)[KCH], float rs, float nm, int k0, int K1) {
+    constexpr bool FIX = PRO == Pro::FoldedFfn;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float4 a[2], g[2], h[2];
     a[0] = ld4(xa);
-    if (PRO == 2) {
+    if (FIX) {
         g[0] = ld4(fg); h[0] = ld4(fg + K);
         a[0] = ffn_fix<SIDE>(a[0], g[0], h[0], rs, nm, k0 < K1);
     }
@@ -137,20 +225,16 @@ __device__ __forceinline__ f32x4 tiles_pipelined(const float* xa, const float* f
         const int c = i & 1, n = c ^ 1;
         if (i + 1 < KCH) {
             a[n] = ld4(xa + (i + 1) * 16);
-            if (PRO == 2) { g[n] = ld4(fg + (i + 1) * 16); h[n] = ld4(fg + K + (i + 1) * 16); }
+            if (FIX) { g[n] = ld4(fg + (i + 1) * 16); h[n] = ld4(fg + K + (i + 1) * 16); }
         }
-        const float4 w = wt[i];
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c].x, w.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c].y, w.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c].z, w.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c].w, w.w, acc, 0, 0, 0);
-        if (PRO == 2 && i + 1 < KCH) a[n] = ffn_fix<SIDE>(a[n], g[n], h[n], rs, nm, k0 + (i + 1) * 16 < K1);
+        acc = mfma_tile(a[c], wt[i], acc);
+        if (FIX && i + 1 < KCH) a[n] = ffn_fix<SIDE>(a[n], g[n], h[n], rs, nm, k0 + (i + 1) * 16 < K1);
         if (i + 1 < KCH) {
-            __builtin_amdgcn_sched_group_barrier(0x100, PRO == 2 ? 3 : 1, 0);      // next tile's LDS reads
+            __builtin_amdgcn_sched_group_barrier(0x100, FIX ? 3 : 1, 0);           // next tile's LDS reads
             __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                      // MFMA .x .y
-            if (PRO == 2) __builtin_amdgcn_sched_group_barrier(0x002, SIDE == 2 ? 12 : 6, 0);      // first half of the next fix
+            if (FIX) __builtin_amdgcn_sched_group_barrier(0x002, SIDE == 2 ? 12 : 6, 0);      // first half of the next fix
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                      // MFMA .z
-            if (PRO == 2) __builtin_amdgcn_sched_group_barrier(0x002, SIDE == 2 ? 12 : 6, 0);      // second half
+            if (FIX) __builtin_amdgcn_sched_group_barrier(0x002, SIDE == 2 ? 12 : 6, 0);      // second half
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                      // MFMA .w
         }
     }
@@ -160,32 +244,29 @@ __device__ __forceinline__ f32x4 tiles_pipelined(const float* xa, const float* f
 // A wave that owns 0 < nown < KCH tiles: one scalar branch per tile, the next tile's reads still one ahead.  (The read-ahead behind the
 // last owned tile touches at most 16 floats past its row / vector: inside the LDS allocation -- the partial-tile region follows --
 // and never used.)
-template <int KCH, int PRO, int SIDE>
+template <int KCH, Pro PRO, int SIDE>
 __device__ __forceinline__ f32x4 tiles_partial(const float* xa, const float* fg, int K, const float4 (&wt)[KCH], float rs, float nm, int k0, int K1, int nown) {
+    constexpr bool FIX = PRO == Pro::FoldedFfn;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float4 a_n = ld4(xa), g_n = a_n, h_n = a_n;
-    if (PRO == 2) { g_n = ld4(fg); h_n = ld4(fg + K); }
+    if (FIX) { g_n = ld4(fg); h_n = ld4(fg + K); }
 #pragma unroll
     for (int i = 0; i < KCH - 1; ++i) {
         if (i < nown) {
             float4 a0 = a_n;
             const float4 g = g_n, h = h_n;
             a_n = ld4(xa + (i + 1) * 16);
-            if (PRO == 2) { g_n = ld4(fg + (i + 1) * 16); h_n = ld4(fg + K + (i + 1) * 16); }
-            if (PRO == 2) a0 = ffn_fix<SIDE>(a0, g, h, rs, nm, k0 + i * 16 < K1);
-            const float4 w = wt[i];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, w.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, w.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, w.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, w.w, acc, 0, 0, 0);
+            if (FIX) { g_n = ld4(fg + (i + 1) * 16); h_n = ld4(fg + K + (i + 1) * 16); }
+            if (FIX) a0 = ffn_fix<SIDE>(a0, g, h, rs, nm, k0 + i * 16 < K1);
+            acc = mfma_tile(a0, wt[i], acc);
         }
     }
     return acc;
 }
 
-// PIPE: the tile loop with wave-uniform control and one tile of read-ahead (round 5); false keeps the serial loop of rounds 2-4
+// PIPE: the tile loop with wave-uniform control and one tile of read-ahead; false keeps the serial loop
 // (DecodeGemmParams::serial_loop: A/B and the bit-identity tests)
-template <int KCH, bool FULL, int PRO, bool PIPE>
+template <int KCH, bool FULL, Pro PRO, bool PIPE>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
 #ifdef AMT_STAMPS
@@ -196,8 +277,8 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
     float* xs = smem;                               // [16][LD]
     // [16 waves][4 r][64 lanes] partial tiles in a region of their own (behind the staged rows and the folded-FFN vectors): a wave stores its
     // partials as soon as its MFMAs are done, with no barrier in between (sharing the rows' region cost one: +0.6 % tokens/s without it)
-    constexpr bool FFN = PRO == 2 || PRO == 5;       // folded-FFN prologues: per-column vectors handed over through LDS
-    float* red = smem + MT * LD + (PRO == 2 ? 2 * K + 2 * MT : PRO == 5 ? 2 * K + 2 * p.K1 : 0);
+    constexpr bool FFN = pro_folded(PRO), LN1 = pro_layernorm(PRO);
+    float* red = smem + MT * LD + (PRO == Pro::FoldedFfn ? 2 * K + 2 * MT : PRO == Pro::FoldedGlu ? 2 * K + 2 * p.K1 : 0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nt = blockIdx.x, m0 = blockIdx.y * MT;
     // column split: tiles below n_split multiply the first K1 input columns by Wp, the others all K by Wp2
@@ -216,45 +297,27 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
     float4 v[KCH];
 #pragma unroll
     for (int c = 0; c < KCH; ++c) {
-        const int i = (c * 64 + lane) * 4, ic = FULL ? i : min(i, K - 4);
+        const int ic = chunk_col<FULL>(c, lane, K);
         v[c] = ld4((ic < K1 ? xr : x2r) + ic);
     }
-    // PRO 5: at least one 256-column chunk belongs to the u half (two at K = 1536, where the launcher asks for K - K1 >= 512: one
+    // FoldedGlu: at least one 256-column chunk belongs to the u half (two at K = 1536, where the launcher asks for K - K1 >= 512: one
     // float4 more per lane would spill at the 128-VGPR budget of a 16-wave workgroup)
-    constexpr int GCH = PRO == 5 ? (KCH == 6 ? 4 : KCH > 1 ? KCH - 1 : 1) : KCH;
-    float4 gv[(PRO == 3 || PRO == 5) ? GCH : 1];
-    if (PRO == 3) {
+    constexpr int GCH = PRO == Pro::FoldedGlu ? (KCH == 6 ? 4 : KCH > 1 ? KCH - 1 : 1) : KCH;
+    float4 gv[pro_gated(PRO) ? GCH : 1];
+    if (PRO == Pro::Glu) {
         const float* gr = p.glu_gate + (size_t)zg * p.x_group_off + (size_t)rc * p.ldx;
 #pragma unroll
-        for (int c = 0; c < KCH; ++c) {
-            const int i = (c * 64 + lane) * 4, ic = FULL ? i : min(i, K - 4);
-            gv[c] = ld4(gr + min(ic, K1 - 4));       // (two-source rows: the chunks past K1 are not gated and re-read the last gate chunk)
-        }
+        for (int c = 0; c < KCH; ++c) gv[c] = ld4(gr + min(chunk_col<FULL>(c, lane, K), K1 - 4));      // (two-source rows: the chunks past K1 are not gated and re-read the last gate chunk)
     }
-    if (PRO == 5) {                                   // raw gate columns of the first K1 staged columns (chunks past K1 re-read the last one)
+    if (PRO == Pro::FoldedGlu) {                      // raw gate columns of the first K1 staged columns (chunks past K1 re-read the last one)
         const float* gr = p.glu_gate + (size_t)rc * p.ldx;
 #pragma unroll
-        for (int c = 0; c < GCH; ++c) gv[c] = ld4(gr + min((c * 64 + lane) * 4, K1 - 4));
+        for (int c = 0; c < GCH; ++c) gv[c] = ld4(gr + min(chunk_col(c, lane), K1 - 4));
     }
     // ---- 2. prologue vectors ----
-    constexpr bool LN1 = PRO == 1 || PRO == 4;      // PRO 4: two LayerNorms in a row (norm3 of the last layer, then decoder.norm)
-    float4 g0[LN1 ? KCH : 1], h0[LN1 ? KCH : 1], g1[PRO == 4 ? KCH : 1], h1[PRO == 4 ? KCH : 1];
-    if (LN1) {
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) {
-            const int i = (c * 64 + lane) * 4, ic = FULL ? i : min(i, K - 4);
-            g0[c] = ld4(p.ln_w + ic);
-            h0[c] = ld4(p.ln_b + ic);
-        }
-    }
-    if (PRO == 4) {
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) {
-            const int i = (c * 64 + lane) * 4, ic = FULL ? i : min(i, K - 4);
-            g1[c] = ld4(p.ln2_w + ic);
-            h1[c] = ld4(p.ln2_b + ic);
-        }
-    }
+    float4 g0[LN1 ? KCH : 1], h0[LN1 ? KCH : 1], g1[PRO == Pro::LayerNorm2 ? KCH : 1], h1[PRO == Pro::LayerNorm2 ? KCH : 1];
+    if constexpr (LN1) load_ln<KCH, FULL>(g0, h0, p.ln_w, p.ln_b, lane, K);
+    if constexpr (PRO == Pro::LayerNorm2) load_ln<KCH, FULL>(g1, h1, p.ln2_w, p.ln2_b, lane, K);
     // folded FFN: the per-column vectors (same for all 16 rows) go through LDS, one float4 per thread (K/2 <= 1024)
     float4 gs_val = make_float4(0.f, 0.f, 0.f, 0.f);
     const int gs_t = min(tid, K / 2 - 1), gs_vec = gs_t >= K / 4, gs_i = (gs_t - gs_vec * (K / 4)) * 4;
@@ -266,7 +329,7 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
     // folded gated FFN: the gate's two vectors [g2 (K1) | c2 (K1)], one more float4 for the first K1/2 threads (clamped)
     float4 gs2_val = make_float4(0.f, 0.f, 0.f, 0.f);
     const int gs2_t = min(tid, K1 / 2 - 1), gs2_vec = gs2_t >= K1 / 4, gs2_i = (gs2_t - gs2_vec * (K1 / 4)) * 4;
-    if (PRO == 5) gs2_val = ld4((gs2_vec ? p.fold_c2 : p.fold_g2) + gs2_i);
+    if (PRO == Pro::FoldedGlu) gs2_val = ld4((gs2_vec ? p.fold_c2 : p.fold_g2) + gs2_i);
     // ---- 3. this wave's weight tiles (tile index clamped: surplus loads repeat the last tile) ----
     float4 wt[KCH];
     const int grp = p.sel ? *p.sel : zg;            // device-chosen weight group (mixture-of-experts, one token) or the launch's group
@@ -285,111 +348,66 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
     const int row = m0 + 4 * (el >> 4) + er, n = nt * 16 + (el & 15);
     const bool live = tid < 256 && row < p.B && n < p.N;
     // ---- prologue math ----
-    if (PRO == 2) {
-        // folded FFN, [ relu((raw - mu*g)*rstd + c) | LayerNorm(u) ] with the statistics of the u half (columns K1..K-1): the rows are
+    const auto in_row = [&](int c) { return FULL || chunk_col(c, lane) < K; };
+    // the folded prologues take their statistics from the u half (columns K1..K-1): 1 there, 0 elsewhere (a multiply keeps the sums branch-free)
+    const auto u_half = [&](int c) { return (chunk_col(c, lane) >= K1 && in_row(c)) ? 1.f : 0.f; };
+    if (PRO == Pro::FoldedFfn) {
+        // folded FFN, [ relu((raw - mu*g)*rstd + c) | LayerNorm(u) ] with the statistics of the u half: the rows are
         // staged RAW, the wave leaves its row's (mu, rstd) and the per-column vectors in LDS, and the fix is applied to the A fragments
         // when they are read for the MFMAs -- under the shadow of the weight tiles still in flight, every element exactly once (a wave
-        // owns its k range), and with ONE barrier instead of two (round 3: 1.56 us of a 6.5 us launch were this prologue)
+        // owns its k range), and with ONE barrier instead of two (1.56 us of a 6.5 us launch were this prologue)
         float* gs = smem + MT * LD;                 // [2][K]: g|gamma , c|beta ; then [16][2]: mu, rstd per staged row
-        const float inv_n = 1.0f / (float)(K - K1);
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) {
-            const int i = (c * 64 + lane) * 4;
-            s += ((i >= K1 && (FULL || i < K)) ? 1.f : 0.f) * sum4(v[c]);
-        }
-        const float mean = wave_sum(s) * inv_n;
-        float q = 0.f;
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) {
-            const int i = (c * 64 + lane) * 4;
-            q += ((i >= K1 && (FULL || i < K)) ? 1.f : 0.f) * sq4(v[c], mean);
-        }
-        const float rstd = rsqrtf(wave_sum(q) * inv_n + p.eps);
-        gs[2 * K + 2 * wave + (lane & 1)] = (lane & 1) ? rstd : mean;      // (every lane stores one of the two words: no branch)
+        const RowStats st = row_stats<true>(v, u_half, (float)(K - K1), p.eps);
+        gs[2 * K + 2 * wave + (lane & 1)] = (lane & 1) ? st.rstd : st.mean;      // (every lane stores one of the two words: no branch)
         st4(gs + gs_vec * K + gs_i, gs_val);        // unconditional (surplus threads repeat the last float4): a guarded
                                                     // store lets the compiler sink the load behind the weight loads
-    } else if (PRO == 5) {
-        // [ up * silu(gate) | LayerNorm(u) ], both halves of the gated unit finished with the statistics of the u half (columns K1..K-1)
+    } else if (PRO == Pro::FoldedGlu) {
+        // [ up * silu(gate) | LayerNorm(u) ], both halves of the gated unit finished with the statistics of the u half
         float* gs = smem + MT * LD;                 // [2][K]: g|gamma , c|beta , then [2][K1]: the gate's g2 , c2
         st4(gs + gs_vec * K + gs_i, gs_val);
         st4(gs + 2 * K + gs2_vec * K1 + gs2_i, gs2_val);
-        const float inv_n = 1.0f / (float)(K - K1);
-        float um[KCH];                              // 1 on the u half, 0 elsewhere (a multiply keeps the loops branch-free)
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) {
-            const int i = (c * 64 + lane) * 4;
-            um[c] = (i >= K1 && (FULL || i < K)) ? 1.f : 0.f;
-        }
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) s += um[c] * sum4(v[c]);
-        const float mean = wave_sum(s) * inv_n;
-        float q = 0.f;
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) q += um[c] * sq4(v[c], mean);
-        const float rstd = rsqrtf(wave_sum(q) * inv_n + p.eps);
+        const RowStats st = row_stats<true>(v, u_half, (float)(K - K1), p.eps);
+        const float mean = st.mean, rstd = st.rstd;
         __syncthreads();
+        // one half of the gated unit, folded: (raw - mu*g)*rstd + c
+        const auto fold = [&](float a, float g, float h) { return (a - mean * g) * rstd + h; };
 #pragma unroll
         for (int c = 0; c < KCH; ++c) {
-            const int i = (c * 64 + lane) * 4;
-            const int ic = FULL ? i : min(i, K - 4);
+            const int ic = chunk_col<FULL>(c, lane, K);
             const float4 g = ld4(gs + ic), h = ld4(gs + K + ic);
             // K1 is a multiple of 256 (checked by the launcher): a 256-column chunk lies on one side of it and the side is wave-uniform
             if (256 * c + 256 <= K1) {               // gated half: up * silu(gate)
                 if (c < GCH) {
                     const float4 g2 = ld4(gs + 2 * K + ic), h2 = ld4(gs + 2 * K + K1 + ic);
-                    const float ux = (v[c].x - mean * g.x) * rstd + h.x, uy = (v[c].y - mean * g.y) * rstd + h.y;
-                    const float uz = (v[c].z - mean * g.z) * rstd + h.z, uw = (v[c].w - mean * g.w) * rstd + h.w;
-                    const float tx = (gv[c].x - mean * g2.x) * rstd + h2.x, ty = (gv[c].y - mean * g2.y) * rstd + h2.y;
-                    const float tz = (gv[c].z - mean * g2.z) * rstd + h2.z, tw = (gv[c].w - mean * g2.w) * rstd + h2.w;
-                    v[c].x = ux * (tx / (1.0f + __expf(-tx))); v[c].y = uy * (ty / (1.0f + __expf(-ty)));
-                    v[c].z = uz * (tz / (1.0f + __expf(-tz))); v[c].w = uw * (tw / (1.0f + __expf(-tw)));
+                    const float ux = fold(v[c].x, g.x, h.x), uy = fold(v[c].y, g.y, h.y), uz = fold(v[c].z, g.z, h.z), uw = fold(v[c].w, g.w, h.w);
+                    const float tx = fold(gv[c].x, g2.x, h2.x), ty = fold(gv[c].y, g2.y, h2.y), tz = fold(gv[c].z, g2.z, h2.z), tw = fold(gv[c].w, g2.w, h2.w);
+                    v[c] = make_float4(ux * silu(tx), uy * silu(ty), uz * silu(tz), uw * silu(tw));
                 }
             } else {                                 // LayerNorm half: (u - mu)*rstd*gamma + beta
-                v[c].x = (v[c].x - mean) * rstd * g.x + h.x; v[c].y = (v[c].y - mean) * rstd * g.y + h.y;
-                v[c].z = (v[c].z - mean) * rstd * g.z + h.z; v[c].w = (v[c].w - mean) * rstd * g.w + h.w;
+                v[c] = ln4(v[c], mean, rstd, g, h);
             }
         }
     } else if (LN1) {
-        const float inv_k = 1.0f / (float)K;
 #pragma unroll
-        for (int pass = 0; pass < (PRO == 4 ? 2 : 1); ++pass) {
-            float s = 0.f;
+        for (int pass = 0; pass < (PRO == Pro::LayerNorm2 ? 2 : 1); ++pass) {
+            const RowStats st = row_stats<false>(v, in_row, (float)K, p.eps);
+            const bool second = PRO == Pro::LayerNorm2 && pass == 1;
 #pragma unroll
-            for (int c = 0; c < KCH; ++c) {
-                const int i = (c * 64 + lane) * 4;
-                if (FULL || i < K) s += sum4(v[c]);
-            }
-            const float mean = wave_sum(s) * inv_k;
-            float q = 0.f;
-#pragma unroll
-            for (int c = 0; c < KCH; ++c) {
-                const int i = (c * 64 + lane) * 4;
-                if (FULL || i < K) q += sq4(v[c], mean);
-            }
-            const float rstd = rsqrtf(wave_sum(q) * inv_k + p.eps);
-#pragma unroll
-            for (int c = 0; c < KCH; ++c) {
-                const float4 g = (PRO == 4 && pass == 1) ? g1[c] : g0[c], h = (PRO == 4 && pass == 1) ? h1[c] : h0[c];
-                v[c].x = (v[c].x - mean) * rstd * g.x + h.x; v[c].y = (v[c].y - mean) * rstd * g.y + h.y;
-                v[c].z = (v[c].z - mean) * rstd * g.z + h.z; v[c].w = (v[c].w - mean) * rstd * g.w + h.w;
-            }
+            for (int c = 0; c < KCH; ++c) v[c] = ln4(v[c], st.mean, st.rstd, second ? g1[c] : g0[c], second ? h1[c] : h0[c]);
         }
     }
-    if (PRO == 3) {
+    if (PRO == Pro::Glu) {
         const float um = p.glu_only ? 0.f : 1.f, uo = p.glu_only ? 1.f : 0.f;      // h = u * silu(g), or silu(g) alone
 #pragma unroll
         for (int c = 0; c < KCH; ++c) {
             // two-source rows [x * silu(gate) (K1 columns) | x2]: whole 256-column chunks on either side (checked by the launcher)
             if (p.x2 && 256 * c + 256 > K1) continue;
-            v[c].x = (v[c].x * um + uo) * (gv[c].x / (1.0f + __expf(-gv[c].x))); v[c].y = (v[c].y * um + uo) * (gv[c].y / (1.0f + __expf(-gv[c].y)));
-            v[c].z = (v[c].z * um + uo) * (gv[c].z / (1.0f + __expf(-gv[c].z))); v[c].w = (v[c].w * um + uo) * (gv[c].w / (1.0f + __expf(-gv[c].w)));
+            v[c] = glu4(v[c], gv[c], um, uo);
         }
     }
 #pragma unroll
     for (int c = 0; c < KCH; ++c) {
-        const int i = (c * 64 + lane) * 4;
+        const int i = chunk_col(c, lane);             // (the column kept in a local: through in_row() the Plain kernels take two VGPRs more)
         if (FULL || i < K) st4(xs + wave * LD + i, v[c]);    // (rows >= B hold a copy of row B-1; their outputs are never stored)
     }
     STAMP(2);
@@ -423,10 +441,10 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
             if (m0 + rr < p.B) p.xn[(size_t)(m0 + rr) * K + cb + c] = xs[rr * LD + cb + c];
     }
     // folded FFN: the LayerNorm half of the staged row is the residual of the low columns
-    if (PRO == 5 && live && !high) e_res = xs[(row - m0) * LD + K1 + n];
-    const float* fgs = smem + MT * LD;              // PRO 2: the per-column vectors and the rows' statistics
+    if (PRO == Pro::FoldedGlu && live && !high) e_res = xs[(row - m0) * LD + K1 + n];
+    const float* fgs = smem + MT * LD;              // FoldedFfn: the per-column vectors and the rows' statistics
     float f_mu = 0.f, f_rs = 0.f;
-    if (PRO == 2) {
+    if (PRO == Pro::FoldedFfn) {
         f_mu = fgs[2 * K + 2 * (lane & 15)]; f_rs = fgs[2 * K + 2 * (lane & 15) + 1];       // A-fragment row of this lane
         if (live && !high) {
             const float* sr = fgs + 2 * K + 2 * (row - m0);
@@ -436,6 +454,7 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
 
     // ---- main: 4 MFMAs per k-tile ----
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    constexpr bool FIX = PRO == Pro::FoldedFfn;
     if constexpr (PIPE) {
         // The wave index through readfirstlane: the compiler then knows that the first tile, the tile count and the side of K1 are
         // wave-uniform -- scalar branches (none at all for a wave that owns KCH tiles) and the uniform address parts in SGPRs.
@@ -446,48 +465,32 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
         const float f_nm = -f_mu * f_rs;
         if (nown == KCH) {
             // every wave of the high / unsplit column tiles at K = KCH * 256
-            if (PRO != 2 || (kt0s + KCH) * 16 <= K1) acc = tiles_pipelined<KCH, PRO, 0>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1);
+            if (!FIX || (kt0s + KCH) * 16 <= K1) acc = tiles_pipelined<KCH, PRO, 0>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1);
             else if (kt0s * 16 >= K1) acc = tiles_pipelined<KCH, PRO, 1>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1);
             else acc = tiles_pipelined<KCH, PRO, 2>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1);
         } else if (nown > 0) {
             // fewer tiles (low-column tiles of a split launch, ragged K)
-            if (PRO != 2 || (kt0s + nown) * 16 <= K1) acc = tiles_partial<KCH, PRO, 0>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1, nown);
+            if (!FIX || (kt0s + nown) * 16 <= K1) acc = tiles_partial<KCH, PRO, 0>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1, nown);
             else if (kt0s * 16 >= K1) acc = tiles_partial<KCH, PRO, 1>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1, nown);
             else acc = tiles_partial<KCH, PRO, 2>(xa, fg, K, wt, f_rs, f_nm, kt0s * 16, K1, nown);
         }
-    } else {                                         // the serial loop of rounds 2-4, kept as it was (indentation included)
-    const float* xa = xs + (lane & 15) * LD + kt0 * 16 + 4 * (lane >> 4);
+    } else {                                         // the serial loop: every tile behind its own (lane-level) guard, reads at their use
+        const float* xa = xs + (lane & 15) * LD + kt0 * 16 + 4 * (lane >> 4);
 #pragma unroll
-    for (int i = 0; i < KCH; ++i) {
-        if (i < tpw && kt0 + i < kt_n) {
-            float4 a0 = ld4(xa + i * 16);
-            if (PRO == 2) {
-                // the folded-FFN fix of this fragment.  It is VALU-bound (16 x 1536 elements per workgroup, every workgroup of the launch
-                // redoes them: with (a - mu*g)*rstd + c spelled as mul / sub / mul / add / max the fix cost 0.75 us of a 7.5 us launch),
-                // so each half is two fused multiply-adds per element, issued as packed pairs (v_pk_fma_f32), with mu*rstd per row:
-                //   raw half        relu(a*rstd + (c - mu*rstd*g))        LayerNorm half   (a*rstd - mu*rstd)*gamma + beta
-                // The side of K1 is wave-uniform (K1 % 16 == 0).
-                const int kc = (kt0 + i) * 16 + 4 * (lane >> 4);
-                const float4 g = ld4(fgs + kc), h = ld4(fgs + K + kc);
-                const f32x2 a_lo = {a0.x, a0.y}, a_hi = {a0.z, a0.w}, g_lo = {g.x, g.y}, g_hi = {g.z, g.w}, h_lo = {h.x, h.y}, h_hi = {h.z, h.w};
-                const f32x2 rs2 = {f_rs, f_rs}, nm2 = {-f_mu * f_rs, -f_mu * f_rs};
-                if ((kt0 + i) * 16 < K1) {
-                    const f32x2 t_lo = __builtin_elementwise_fma(a_lo, rs2, __builtin_elementwise_fma(nm2, g_lo, h_lo));
-                    const f32x2 t_hi = __builtin_elementwise_fma(a_hi, rs2, __builtin_elementwise_fma(nm2, g_hi, h_hi));
-                    a0 = make_float4(fmaxf(t_lo.x, 0.f), fmaxf(t_lo.y, 0.f), fmaxf(t_hi.x, 0.f), fmaxf(t_hi.y, 0.f));
-                } else {
-                    const f32x2 t_lo = __builtin_elementwise_fma(__builtin_elementwise_fma(a_lo, rs2, nm2), g_lo, h_lo);
-                    const f32x2 t_hi = __builtin_elementwise_fma(__builtin_elementwise_fma(a_hi, rs2, nm2), g_hi, h_hi);
-                    a0 = make_float4(t_lo.x, t_lo.y, t_hi.x, t_hi.y);
+        for (int i = 0; i < KCH; ++i) {
+            if (i < tpw && kt0 + i < kt_n) {
+                float4 a0 = ld4(xa + i * 16);
+                if (FIX) {
+                    // the folded-FFN fix of this fragment, in packed pairs.  The side of K1 is wave-uniform (K1 % 16 == 0).
+                    const int kc = (kt0 + i) * 16 + 4 * (lane >> 4);
+                    const float4 g = ld4(fgs + kc), h = ld4(fgs + K + kc);
+                    const float f_nm = -f_mu * f_rs;
+                    if ((kt0 + i) * 16 < K1) a0 = ffn_fix<0, true>(a0, g, h, f_rs, f_nm, true);
+                    else a0 = ffn_fix<1, true>(a0, g, h, f_rs, f_nm, false);
                 }
+                acc = mfma_tile(a0, wt[i], acc);
             }
-            const float4 w = wt[i];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, w.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, w.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, w.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, w.w, acc, 0, 0, 0);
         }
-    }
     }
     // ---- cross-wave reduction in fixed order ----
 #ifdef AMT_STAMPS
@@ -499,9 +502,7 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
     unsigned long long* wg_end = reinterpret_cast<unsigned long long*>(red + NW * 256);
     if (lane == 0) atomicMax(wg_end, st_[4]);
 #endif
-    float* rw = red + wave * 256;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) rw[rr * 64 + lane] = acc[rr];
+    store_partials(red + wave * 256, acc, lane);
     __syncthreads();
     STAMP(5);
 #ifdef AMT_STAMPS
@@ -515,11 +516,7 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
     }
 #endif
     float val = 0.f;
-    if (tid < 256) {
-#pragma unroll
-        for (int w = 0; w < NW; ++w) val += red[w * 256 + tid];
-        val += e_bias;
-    }
+    if (tid < 256) val = sum_partials(red, tid) + e_bias;
     if (p.rope) {
         // interleaved pairs sit in adjacent lanes of the same row (16-column tiles): even column y = x*c - x'*s, odd y = x*c + x'*s
         const float other = __shfl_xor(val, 1, 64);
@@ -562,26 +559,79 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
 #endif
 }
 
-template <int KCH, bool FULL, int PRO, bool PIPE>
-int32_t launch_one_loop(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
-    // > 64 KiB of dynamic LDS needs the opt-in (gfx950: 160 KiB per CU).  The attribute belongs to the (function, device)
-    // pair, so the flag is kept per device ordinal and per instantiation, under a lock (host threads may launch concurrently)
+int32_t device_ordinal(int* dev) {
+    AMT_HIP(hipGetDevice(dev));
+    AMT_CHECK_ARG(*dev >= 0 && *dev < 64, "decode_gemm: device ordinal %d out of range", *dev);
+    return 0;
+}
+
+// > 64 KiB of dynamic LDS needs the opt-in (gfx950: 160 KiB per CU).  The attribute belongs to the (function, device)
+// pair, so the flag is kept per device ordinal and per kernel, under a lock (host threads may launch concurrently)
+template <auto Kernel>
+int32_t allow_big_lds() {
     static bool attr_set[64] = {false};
     static std::mutex mu;
     int dev = 0;
-    AMT_HIP(hipGetDevice(&dev));
-    AMT_CHECK_ARG(dev >= 0 && dev < 64, "decode_gemm: device ordinal %d out of range", dev);
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            AMT_HIP(hipFuncSetAttribute((const void*)decode_gemm_kernel<KCH, FULL, PRO, PIPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set[dev] = true;
-        }
+    if (int32_t rc = device_ordinal(&dev)) return rc;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!attr_set[dev]) {
+        AMT_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set[dev] = true;
     }
+    return 0;
+}
+
+template <int KCH, bool FULL, Pro PRO, bool PIPE>
+int32_t launch_one_loop(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
+    if (int32_t rc = allow_big_lds<decode_gemm_kernel<KCH, FULL, PRO, PIPE>>()) return rc;
     hipLaunchKernelGGL((decode_gemm_kernel<KCH, FULL, PRO, PIPE>), dim3(cdiv(p.N, 16), cdiv(p.B, MT), p.n_groups > 1 ? p.n_groups : 1), dim3(NW * 64), lds, stream, p);
     AMT_LAUNCH_CHECK();
     return 0;
 }
+
+// The pipelined tile loop serves the plain and the folded-FFN prologue (every skinny GEMM of the folded decode chain); the other
+// prologues keep the serial loop (LayerNorm2 / FoldedGlu sit at 114 - 126 VGPRs of the 128 a 16-wave workgroup may use)
+template <int KCH, bool FULL, Pro PRO>
+int32_t launch_one(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
+    if constexpr (PRO == Pro::Plain || PRO == Pro::FoldedFfn) { if (!p.serial_loop) return launch_one_loop<KCH, FULL, PRO, true>(p, lds, stream); }
+    return launch_one_loop<KCH, FULL, PRO, false>(p, lds, stream);
+}
+
+// ---- parts shared by the two wide kernels below (K = KCH * 256, packed weights, Plain / LayerNorm / Glu) ----
+// all NTW x KCH weight tiles of a wave (surplus column tiles repeat the last one)
+template <int KCH, int NTW>
+__device__ __forceinline__ void wide_load_tiles(float4 (&wt)[NTW][KCH], const float* Wp, int nt0, int n_tiles, int kt0, int lane) {
+#pragma unroll
+    for (int j = 0; j < NTW; ++j) {
+        const float* wbase = Wp + (size_t)min(nt0 + j, n_tiles - 1) * (KCH * 16) * 256;
+#pragma unroll
+        for (int i = 0; i < KCH; ++i) wt[j][i] = ld4(wbase + ((size_t)(kt0 + i) * 64 + lane) * 4);
+    }
+}
+// the prologue of the row a wave holds
+template <int KCH, Pro PRO>
+__device__ __forceinline__ void wide_prologue(float4 (&v)[KCH], const float4* gv, const float4* g0, const float4* h0, float eps, int glu_only) {
+    if (PRO == Pro::LayerNorm) {
+        const RowStats st = row_stats<false>(v, [](int) { return true; }, (float)(KCH * 256), eps);
+#pragma unroll
+        for (int c = 0; c < KCH; ++c) v[c] = ln4(v[c], st.mean, st.rstd, g0[c], h0[c]);
+    }
+    if (PRO == Pro::Glu) {
+        const float um = glu_only ? 0.f : 1.f, uo = glu_only ? 1.f : 0.f;      // h = u * silu(g), or silu(g) alone
+#pragma unroll
+        for (int c = 0; c < KCH; ++c) v[c] = glu4(v[c], gv[c], um, uo);
+    }
+}
+// a full row into its LDS slot
+template <int KCH>
+__device__ __forceinline__ void wide_stage_row(float* xrow, const float4 (&v)[KCH], int lane) {
+#pragma unroll
+    for (int c = 0; c < KCH; ++c) st4(xrow + chunk_col(c, lane), v[c]);
+}
+// (The reduce-and-store epilogue of one output -- sum of the 16 partials, bias, paired gate | up or scale / residual / activation,
+// store -- stays written out in each wide kernel: as a shared helper it has to be handed the kernel's parameters, every field of them
+// is then read at the kernel's start instead of inside the branch that uses it, and MFMA, LDS and global loads of six instantiations
+// change places against each other.  glu_pair_value(), act() and, in the one-row-block kernel, sum_partials() are the shared parts.)
 
 // Wide products (N >= 4096: the stacked gate|up projection of a mixture-of-experts layer, 7 x 2 x dff columns): with one 16-column
 // tile per workgroup such a launch is 1792 workgroups of two weight tiles per wave each, i.e. several rounds of the fixed
@@ -589,19 +639,11 @@ int32_t launch_one_loop(const DecodeGemmParams& p, size_t lds, hipStream_t strea
 // and walks NTW column tiles: all NTW x KCH weight tiles of a wave are in flight before the prologue, the rows are staged and
 // normalised once, and every thread takes part in the final reduction (thread group j reduces tile j).  Same arithmetic per output
 // as decode_gemm_kernel (same k order inside a wave, same fixed wave order in the reduction): results are bit-identical.
-// Plain single-source products only: PRO 0 / 1, packed weights, mode 0, no column split, no rotary epilogue.
-// The pipelined tile loop serves the plain and the folded-FFN prologue (PRO 0 / 2: every skinny GEMM of the folded decode chain); the
-// other prologues keep the serial loop (PRO 4 / 5 sit at 114 - 126 VGPRs of the 128 a 16-wave workgroup may use)
-template <int KCH, bool FULL, int PRO>
-int32_t launch_one(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
-    if constexpr (PRO == 0 || PRO == 2) { if (!p.serial_loop) return launch_one_loop<KCH, FULL, PRO, true>(p, lds, stream); }
-    return launch_one_loop<KCH, FULL, PRO, false>(p, lds, stream);
-}
-
-template <int KCH, int PRO, int NTW>
+// Plain single-source products only: Plain / LayerNorm / Glu, packed weights, mode 0, no column split, no rotary epilogue.
+template <int KCH, Pro PRO, int NTW>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_wide_kernel(DecodeGemmParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int K = KCH * 256, LD = K + XPAD, kt_n = K / 16;
+    constexpr int K = KCH * 256, LD = K + XPAD;
     float* xs = smem;                               // [16][LD]
     float* red = smem + MT * LD;                    // [NTW][16 waves][256] partial tiles behind the staged rows (no barrier before they are stored)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -617,55 +659,20 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_wide_kernel(DecodeGemmPar
     const float* xr = p.x + (size_t)zg * p.x_group_off + (size_t)rc * p.ldx;
     float4 v[KCH];
 #pragma unroll
-    for (int c = 0; c < KCH; ++c) v[c] = ld4(xr + (c * 64 + lane) * 4);
-    float4 gv[PRO == 3 ? KCH : 1];
-    if (PRO == 3) {
+    for (int c = 0; c < KCH; ++c) v[c] = ld4(xr + chunk_col(c, lane));
+    float4 gv[PRO == Pro::Glu ? KCH : 1];
+    if (PRO == Pro::Glu) {
         const float* gr = p.glu_gate + (size_t)zg * p.x_group_off + (size_t)rc * p.ldx;
 #pragma unroll
-        for (int c = 0; c < KCH; ++c) gv[c] = ld4(gr + (c * 64 + lane) * 4);
+        for (int c = 0; c < KCH; ++c) gv[c] = ld4(gr + chunk_col(c, lane));
     }
-    float4 g0[PRO == 1 ? KCH : 1], h0[PRO == 1 ? KCH : 1];
-    if (PRO == 1) {
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) {
-            g0[c] = ld4(p.ln_w + (c * 64 + lane) * 4);
-            h0[c] = ld4(p.ln_b + (c * 64 + lane) * 4);
-        }
-    }
+    float4 g0[PRO == Pro::LayerNorm ? KCH : 1], h0[PRO == Pro::LayerNorm ? KCH : 1];
+    if constexpr (PRO == Pro::LayerNorm) load_ln<KCH, true>(g0, h0, p.ln_w, p.ln_b, lane, K);
     float4 wt[NTW][KCH];
-#pragma unroll
-    for (int j = 0; j < NTW; ++j) {
-        const float* wbase = p.Wp + (size_t)zg * p.sel_w_stride + (size_t)min(nt0 + j, n_tiles - 1) * kt_n * 256;      // surplus tiles repeat the last one
-#pragma unroll
-        for (int i = 0; i < KCH; ++i) wt[j][i] = ld4(wbase + ((size_t)(kt0 + i) * 64 + lane) * 4);
-    }
+    wide_load_tiles(wt, p.Wp + (size_t)zg * p.sel_w_stride, nt0, n_tiles, kt0, lane);
     __builtin_amdgcn_sched_barrier(0);
-    if (PRO == 1) {
-        const float inv_k = 1.0f / (float)K;
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) s += sum4(v[c]);
-        const float mean = wave_sum(s) * inv_k;
-        float q = 0.f;
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) q += sq4(v[c], mean);
-        const float rstd = rsqrtf(wave_sum(q) * inv_k + p.eps);
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) {
-            v[c].x = (v[c].x - mean) * rstd * g0[c].x + h0[c].x; v[c].y = (v[c].y - mean) * rstd * g0[c].y + h0[c].y;
-            v[c].z = (v[c].z - mean) * rstd * g0[c].z + h0[c].z; v[c].w = (v[c].w - mean) * rstd * g0[c].w + h0[c].w;
-        }
-    }
-    if (PRO == 3) {
-        const float um = p.glu_only ? 0.f : 1.f, uo = p.glu_only ? 1.f : 0.f;      // h = u * silu(g), or silu(g) alone
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) {
-            v[c].x = (v[c].x * um + uo) * (gv[c].x / (1.0f + __expf(-gv[c].x))); v[c].y = (v[c].y * um + uo) * (gv[c].y / (1.0f + __expf(-gv[c].y)));
-            v[c].z = (v[c].z * um + uo) * (gv[c].z / (1.0f + __expf(-gv[c].z))); v[c].w = (v[c].w * um + uo) * (gv[c].w / (1.0f + __expf(-gv[c].w)));
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < KCH; ++c) st4(xs + wave * LD + (c * 64 + lane) * 4, v[c]);
+    wide_prologue<KCH, PRO>(v, gv, g0, h0, p.eps, p.glu_only);
+    wide_stage_row(xs + wave * LD, v, lane);
     __syncthreads();
 
     // thread (jg, e) owns output e of tiles nt0 + jg, nt0 + jg + 4, ...
@@ -680,7 +687,7 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_wide_kernel(DecodeGemmPar
         const bool live = j < NTW && row < p.B && n < p.N;
         e_bias[q] = *((live && p.bias) ? p.bias + (size_t)zg * p.sel_b_stride + (p.glu_pair ? glu_pair_bias_col(n, p.N) : n) : p.zero);
         e_res[q] = *((live && p.resid) ? p.resid + (size_t)row * p.ldr + n : p.zero);
-        if (PRO == 1 && p.xn && j < NTW && (nt0 + j) * 16 < K) {
+        if (PRO == Pro::LayerNorm && p.xn && j < NTW && (nt0 + j) * 16 < K) {
             const int rr = e >> 4, c = e & 15;
             if (m0 + rr < p.B) p.xn[(size_t)(m0 + rr) * K + (nt0 + j) * 16 + c] = xs[rr * LD + (nt0 + j) * 16 + c];
         }
@@ -694,32 +701,19 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_wide_kernel(DecodeGemmPar
     for (int i = 0; i < KCH; ++i) {
         const float4 a0 = ld4(xa + i * 16);
 #pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-            const float4 w = wt[j][i];
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, w.x, acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, w.y, acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, w.z, acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, w.w, acc[j], 0, 0, 0);
-        }
+        for (int j = 0; j < NTW; ++j) acc[j] = mfma_tile(a0, wt[j][i], acc[j]);
     }
 #pragma unroll
-    for (int j = 0; j < NTW; ++j) {
-        float* rw = red + (j * NW + wave) * 256;
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) rw[rr * 64 + lane] = acc[j][rr];
-    }
+    for (int j = 0; j < NTW; ++j) store_partials(red + (j * NW + wave) * 256, acc[j], lane);
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < JN; ++q) {
         const int j = jg + 4 * q, n = (nt0 + j) * 16 + (el & 15);
         if (j < NTW) {
-            float val = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) val += red[(j * NW + w) * 256 + e];
-            val += e_bias[q];
+            float val = sum_partials(red + j * NW * 256, e) + e_bias[q];
             if (p.glu_pair) {                        // (j < NTW is uniform per 256-thread group: whole waves take the exchange)
                 val = glu_pair_value(val, n & 15);
-                if (row < p.B && n < p.N && (n & 8)) p.y[(size_t)row * p.ldy + (n >> 4) * 8 + (n & 7)] = val;
+                if (row < p.B && n < p.N && (n & 8)) p.y[(size_t)row * p.ldy + (n >> 4) * 8 + (n & 7)] = val;      // (never a grouped launch)
             } else if (row < p.B && n < p.N) {
                 if (n < p.scale_cols) val *= p.scale;
                 val += e_res[q];
@@ -737,10 +731,10 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_wide_kernel(DecodeGemmPar
 // process, profiles/r03_v2_ab.json).  Wave w stages rows w and 16 + w;
 // per k-tile a weight fragment feeds two MFMA chains; the partial tiles of the two row blocks go through the same LDS region one
 // after the other.  Same arithmetic per output as decode_gemm_wide_kernel (bit-identical results).  K = KCH * 256 <= 512.
-template <int KCH, int PRO, int NTW>
+template <int KCH, Pro PRO, int NTW>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_wide2_kernel(DecodeGemmParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int K = KCH * 256, LD = K + XPAD, kt_n = K / 16;
+    constexpr int K = KCH * 256, LD = K + XPAD;
     float* xs = smem;                               // [2][16][LD]
     float* red = smem + 2 * MT * LD;                // [NTW][16 waves][256] partial tiles of ONE row block at a time
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -754,47 +748,17 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_wide2_kernel(DecodeGemmPa
     for (int rb = 0; rb < 2; ++rb) {
         const float* xr = p.x + (size_t)min(rb * MT + wave, p.B - 1) * p.ldx;
 #pragma unroll
-        for (int c = 0; c < KCH; ++c) v[rb][c] = ld4(xr + (c * 64 + lane) * 4);
+        for (int c = 0; c < KCH; ++c) v[rb][c] = ld4(xr + chunk_col(c, lane));
     }
-    float4 g0[PRO == 1 ? KCH : 1], h0[PRO == 1 ? KCH : 1];
-    if (PRO == 1) {
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) {
-            g0[c] = ld4(p.ln_w + (c * 64 + lane) * 4);
-            h0[c] = ld4(p.ln_b + (c * 64 + lane) * 4);
-        }
-    }
+    float4 g0[PRO == Pro::LayerNorm ? KCH : 1], h0[PRO == Pro::LayerNorm ? KCH : 1];
+    if constexpr (PRO == Pro::LayerNorm) load_ln<KCH, true>(g0, h0, p.ln_w, p.ln_b, lane, K);
     float4 wt[NTW][KCH];
-#pragma unroll
-    for (int j = 0; j < NTW; ++j) {
-        const float* wbase = p.Wp + (size_t)min(nt0 + j, n_tiles - 1) * kt_n * 256;      // surplus tiles repeat the last one
-#pragma unroll
-        for (int i = 0; i < KCH; ++i) wt[j][i] = ld4(wbase + ((size_t)(kt0 + i) * 64 + lane) * 4);
-    }
+    wide_load_tiles(wt, p.Wp, nt0, n_tiles, kt0, lane);
     __builtin_amdgcn_sched_barrier(0);
-    if (PRO == 1) {
-        const float inv_k = 1.0f / (float)K;
 #pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-            float s = 0.f;
+    for (int rb = 0; rb < 2; ++rb) wide_prologue<KCH, PRO>(v[rb], nullptr, g0, h0, p.eps, p.glu_only);
 #pragma unroll
-            for (int c = 0; c < KCH; ++c) s += sum4(v[rb][c]);
-            const float mean = wave_sum(s) * inv_k;
-            float q = 0.f;
-#pragma unroll
-            for (int c = 0; c < KCH; ++c) q += sq4(v[rb][c], mean);
-            const float rstd = rsqrtf(wave_sum(q) * inv_k + p.eps);
-#pragma unroll
-            for (int c = 0; c < KCH; ++c) {
-                v[rb][c].x = (v[rb][c].x - mean) * rstd * g0[c].x + h0[c].x; v[rb][c].y = (v[rb][c].y - mean) * rstd * g0[c].y + h0[c].y;
-                v[rb][c].z = (v[rb][c].z - mean) * rstd * g0[c].z + h0[c].z; v[rb][c].w = (v[rb][c].w - mean) * rstd * g0[c].w + h0[c].w;
-            }
-        }
-    }
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int c = 0; c < KCH; ++c) st4(xs + (rb * MT + wave) * LD + (c * 64 + lane) * 4, v[rb][c]);
+    for (int rb = 0; rb < 2; ++rb) wide_stage_row(xs + (rb * MT + wave) * LD, v[rb], lane);
     __syncthreads();
 
     // thread (jg, e) owns output e of tiles nt0 + jg, nt0 + jg + 4, ... of each row block
@@ -807,7 +771,7 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_wide2_kernel(DecodeGemmPa
     for (int q = 0; q < JN; ++q) {
         const int j = jg + 4 * q, n = (nt0 + j) * 16 + (el & 15);
         e_bias[q] = *((j < NTW && n < p.N && p.bias) ? p.bias + (p.glu_pair ? glu_pair_bias_col(n, p.N) : n) : p.zero);
-        if (PRO == 1 && p.xn && j < NTW && (nt0 + j) * 16 < K) {
+        if (PRO == Pro::LayerNorm && p.xn && j < NTW && (nt0 + j) * 16 < K) {
             const int rr = e >> 4, c = e & 15;
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb)
@@ -826,32 +790,22 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_wide2_kernel(DecodeGemmPa
         const float4 a0 = ld4(xa + i * 16), a1 = ld4(xa + MT * LD + i * 16);
 #pragma unroll
         for (int j = 0; j < NTW; ++j) {
-            const float4 w = wt[j][i];
-            acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, w.x, acc[0][j], 0, 0, 0);
-            acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, w.y, acc[0][j], 0, 0, 0);
-            acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, w.z, acc[0][j], 0, 0, 0);
-            acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, w.w, acc[0][j], 0, 0, 0);
-            acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, w.x, acc[1][j], 0, 0, 0);
-            acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, w.y, acc[1][j], 0, 0, 0);
-            acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, w.z, acc[1][j], 0, 0, 0);
-            acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, w.w, acc[1][j], 0, 0, 0);
+            acc[0][j] = mfma_tile(a0, wt[j][i], acc[0][j]);
+            acc[1][j] = mfma_tile(a1, wt[j][i], acc[1][j]);
         }
     }
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
         if (rb) __syncthreads();                    // the first row block's partial tiles are consumed
 #pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-            float* rw = red + (j * NW + wave) * 256;
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) rw[rr * 64 + lane] = acc[rb][j][rr];
-        }
+        for (int j = 0; j < NTW; ++j) store_partials(red + (j * NW + wave) * 256, acc[rb][j], lane);
         __syncthreads();
         const int row = rb * MT + rloc;
 #pragma unroll
         for (int q = 0; q < JN; ++q) {
             const int j = jg + 4 * q, n = (nt0 + j) * 16 + (el & 15);
             if (j < NTW) {
+                // (written out, not sum_partials(): with the helper, in either indexing, three MFMAs and the LDS traffic next to them change places)
                 float val = 0.f;
 #pragma unroll
                 for (int w = 0; w < NW; ++w) val += red[(j * NW + w) * 256 + e];
@@ -861,7 +815,7 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_wide2_kernel(DecodeGemmPa
                     if (row < p.B && n < p.N && (n & 8)) p.y[(size_t)row * p.ldy + (n >> 4) * 8 + (n & 7)] = val;
                 } else if (row < p.B && n < p.N) {
                     if (n < p.scale_cols) val *= p.scale;
-                    if (p.resid) val += p.resid[(size_t)row * p.ldr + n];
+                    if (p.resid) val += p.resid[(size_t)row * p.ldr + n];      // (read late: not one more operand held across the MFMAs of two row blocks)
                     val = act(val, p.relu);
                     p.y[(size_t)row * p.ldy + n] = val;
                 }
@@ -870,20 +824,9 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_wide2_kernel(DecodeGemmPa
     }
 }
 
-template <int KCH, int PRO, int NTW>
+template <int KCH, Pro PRO, int NTW>
 int32_t launch_wide2(const DecodeGemmParams& p, hipStream_t stream) {
-    static bool attr_set[64] = {false};
-    static std::mutex mu;
-    int dev = 0;
-    AMT_HIP(hipGetDevice(&dev));
-    AMT_CHECK_ARG(dev >= 0 && dev < 64, "decode_gemm: device ordinal %d out of range", dev);
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            AMT_HIP(hipFuncSetAttribute((const void*)decode_gemm_wide2_kernel<KCH, PRO, NTW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set[dev] = true;
-        }
-    }
+    if (int32_t rc = allow_big_lds<decode_gemm_wide2_kernel<KCH, PRO, NTW>>()) return rc;
     constexpr size_t lds = (size_t)2 * MT * (KCH * 256 + XPAD) * sizeof(float) + (size_t)NTW * NW * 256 * sizeof(float);      // rows of both blocks | partial tiles
     static_assert(lds <= 160 * 1024, "rows + partial tiles must fit the 160 KiB of LDS");
     hipLaunchKernelGGL((decode_gemm_wide2_kernel<KCH, PRO, NTW>), dim3(cdiv(cdiv(p.N, 16), NTW)), dim3(NW * 64), lds, stream, p);
@@ -891,40 +834,31 @@ int32_t launch_wide2(const DecodeGemmParams& p, hipStream_t stream) {
     return 0;
 }
 
-template <int KCH, int PRO, int NTW>
+template <int KCH, Pro PRO, int NTW>
 int32_t launch_wide(const DecodeGemmParams& p, hipStream_t stream) {
-    static bool attr_set[64] = {false};
-    static std::mutex mu;
-    int dev = 0;
-    AMT_HIP(hipGetDevice(&dev));
-    AMT_CHECK_ARG(dev >= 0 && dev < 64, "decode_gemm: device ordinal %d out of range", dev);
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            AMT_HIP(hipFuncSetAttribute((const void*)decode_gemm_wide_kernel<KCH, PRO, NTW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set[dev] = true;
-        }
-    }
-    const size_t lds = (size_t)MT * (KCH * 256 + XPAD) * sizeof(float) + (size_t)NTW * NW * 256 * sizeof(float);      // rows | partial tiles
-    static_assert((size_t)MT * (KCH * 256 + XPAD) * sizeof(float) + (size_t)NTW * NW * 256 * sizeof(float) <= 160 * 1024, "rows + partial tiles must fit the 160 KiB of LDS");
+    if (int32_t rc = allow_big_lds<decode_gemm_wide_kernel<KCH, PRO, NTW>>()) return rc;
+    constexpr size_t lds = (size_t)MT * (KCH * 256 + XPAD) * sizeof(float) + (size_t)NTW * NW * 256 * sizeof(float);      // rows | partial tiles
+    static_assert(lds <= 160 * 1024, "rows + partial tiles must fit the 160 KiB of LDS");
     const int groups8 = cdiv(cdiv(cdiv(p.N, 16), NTW), 8) * 8;
     hipLaunchKernelGGL((decode_gemm_wide_kernel<KCH, PRO, NTW>), dim3(groups8 * cdiv(p.B, MT), p.n_groups > 1 ? p.n_groups : 1), dim3(NW * 64), lds, stream, p);
     AMT_LAUNCH_CHECK();
     return 0;
 }
 
+// The one place that maps DecodeGemmParams::pro (0 none, 1 folded FFN, 2 folded gated FFN), glu_gate and ln_w / ln2_w onto the prologue.
+// (The `if constexpr` guards only keep instantiations from being compiled that the launcher's checks rule out.)
 template <int KCH, bool FULL>
 int32_t launch_variant(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
 #ifdef AMT_EXPERIMENT
     // timing only (wrong values): what does the folded-FFN prologue cost?  exp_a = 1 launches the same product with the plain staging
-    if (p.pro == 1 && amt_tuning().exp_a == 1) return launch_one<KCH, FULL, 0>(p, lds, stream);
+    if (p.pro == 1 && amt_tuning().exp_a == 1) return launch_one<KCH, FULL, Pro::Plain>(p, lds, stream);
 #endif
-    if (p.pro == 1) return launch_one<KCH, FULL, 2>(p, lds, stream);
-    if (p.pro == 2) { if constexpr (FULL && KCH >= 2) return launch_one<KCH, FULL, 5>(p, lds, stream); }
-    if (p.glu_gate) return launch_one<KCH, FULL, 3>(p, lds, stream);
-    if (p.ln_w && p.ln2_w) { if constexpr (KCH <= 4) return launch_one<KCH, FULL, 4>(p, lds, stream); }
-    if (p.ln_w) { if constexpr (KCH <= 4) return launch_one<KCH, FULL, 1>(p, lds, stream); }
-    return launch_one<KCH, FULL, 0>(p, lds, stream);
+    if (p.pro == 1) return launch_one<KCH, FULL, Pro::FoldedFfn>(p, lds, stream);
+    if (p.pro == 2) { if constexpr (FULL && KCH >= 2) return launch_one<KCH, FULL, Pro::FoldedGlu>(p, lds, stream); }
+    if (p.glu_gate) return launch_one<KCH, FULL, Pro::Glu>(p, lds, stream);
+    if (p.ln_w && p.ln2_w) { if constexpr (KCH <= 4) return launch_one<KCH, FULL, Pro::LayerNorm2>(p, lds, stream); }
+    if (p.ln_w) { if constexpr (KCH <= 4) return launch_one<KCH, FULL, Pro::LayerNorm>(p, lds, stream); }
+    return launch_one<KCH, FULL, Pro::Plain>(p, lds, stream);
 }
 
 }  // namespace
@@ -942,8 +876,7 @@ static int32_t zero_words(const float** out) {
     static float* buf[64] = {nullptr};
     static std::mutex mu;                            // several host threads may launch concurrently (one stream each)
     int dev = 0;
-    AMT_HIP(hipGetDevice(&dev));
-    AMT_CHECK_ARG(dev >= 0 && dev < 64, "decode_gemm: device ordinal %d out of range", dev);
+    if (int32_t rc = device_ordinal(&dev)) return rc;
     std::lock_guard<std::mutex> lock(mu);
     if (!buf[dev]) {
         AMT_HIP(hipMalloc((void**)&buf[dev], 256));
@@ -991,20 +924,20 @@ int32_t amt_launch_decode_gemm(const DecodeGemmParams& p_in, hipStream_t stream)
     const int wide_grp = amt_tuning().wide_grouped;
     if (wide_grp > 0 && p.n_groups > 1 && !p.ln_w && p.pro == 0 && !p.rope && !p.x2 && p.mode == 0 && p.ldw == 0 && !p.sel &&
         (p.K == 512 || p.K == 1024) && cdiv(p.N, 16) * cdiv(p.B, MT) * p.n_groups > 256) {
-        if (p.glu_gate) return p.K == 512 ? launch_wide<2, 3, 2>(p, stream) : launch_wide<4, 3, 2>(p, stream);
-        return p.K == 512 ? launch_wide<2, 0, 2>(p, stream) : launch_wide<4, 0, 2>(p, stream);      // (gated already: the producer's paired epilogue)
+        if (p.glu_gate) return p.K == 512 ? launch_wide<2, Pro::Glu, 2>(p, stream) : launch_wide<4, Pro::Glu, 2>(p, stream);
+        return p.K == 512 ? launch_wide<2, Pro::Plain, 2>(p, stream) : launch_wide<4, Pro::Plain, 2>(p, stream);      // (gated already: the producer's paired epilogue)
     }
     const int wide_ntw = amt_tuning().wide_ntw;
     if (wide_ntw > 0 && p.N >= 4096 && !p.x2 && p.n_split == 0 && !p.sel && p.n_groups <= 1 && p.mode == 0 && !p.rope && !p.glu_gate && p.pro == 0 &&
         p.ldw == 0 && (p.K == 512 || p.K == 1024) && (!p.ln_w || p.ln_b) && !p.ln2_w) {
         const bool ln = p.ln_w != nullptr;
         // 17 .. 32 rows: both row blocks in one workgroup (half the workgroups, the weights through L1 once)
-        if (p.K == 512 && p.B > MT && p.B <= 2 * MT && amt_tuning().wide_rb2) return ln ? launch_wide2<2, 1, 4>(p, stream) : launch_wide2<2, 0, 4>(p, stream);
+        if (p.K == 512 && p.B > MT && p.B <= 2 * MT && amt_tuning().wide_rb2) return ln ? launch_wide2<2, Pro::LayerNorm, 4>(p, stream) : launch_wide2<2, Pro::Plain, 4>(p, stream);
         if (p.K == 512) {
-            if (wide_ntw == 7) return ln ? launch_wide<2, 1, 7>(p, stream) : launch_wide<2, 0, 7>(p, stream);
-            return ln ? launch_wide<2, 1, 4>(p, stream) : launch_wide<2, 0, 4>(p, stream);
+            if (wide_ntw == 7) return ln ? launch_wide<2, Pro::LayerNorm, 7>(p, stream) : launch_wide<2, Pro::Plain, 7>(p, stream);
+            return ln ? launch_wide<2, Pro::LayerNorm, 4>(p, stream) : launch_wide<2, Pro::Plain, 4>(p, stream);
         }
-        return ln ? launch_wide<4, 1, 4>(p, stream) : launch_wide<4, 0, 4>(p, stream);
+        return ln ? launch_wide<4, Pro::LayerNorm, 4>(p, stream) : launch_wide<4, Pro::Plain, 4>(p, stream);
     }
     // staged rows | folded-FFN vectors | the waves' partial tiles
     const size_t lds = (size_t)MT * (p.K + XPAD) * sizeof(float) + (p.pro == 1 ? (size_t)(2 * p.K + 2 * MT) * sizeof(float) : 0) +
