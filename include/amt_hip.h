@@ -36,8 +36,9 @@
 #define AMT_HIP_H
 #include <stdint.h>
 
-#define AMT_ABI_VERSION 3    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
-                                3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights */
+#define AMT_ABI_VERSION 4    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
+                                3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights;
+                                4: amt_chord_metrics_fwd */
 
 #ifdef __cplusplus
 extern "C" {
@@ -443,6 +444,28 @@ int32_t amt_linear_ex_fwd(const float* x, int32_t ldx, const float* w, int32_t l
 /* y = LayerNorm(x (+ resid)) + post : the "norm2(x_b + x) then x_f + x_b" step of bimamba.py:183-188 in one pass. */
 int32_t amt_layernorm_post_fwd(const float* x, const float* resid, const float* w, const float* b, const float* post,
                                float* y, int32_t rows, int32_t dim, float eps, void* stream);
+
+/* ---- evaluation: the test-split metrics of evaluate.py (utilities/run_model_vevo.py:198-452) from teacher-forced logits ---- */
+/* Replaces compute_vevo_accuracy / compute_hits_k / compute_vevo_correspondence (dataset/vevo_dataset.py:653-701,747-810) and the two
+ * losses of eval_model (CrossEntropyLoss(ignore_index=CHORD_PAD), BCEWithLogitsLoss against the emotion rows of :461-515) for the
+ * single 159-way head.  logits: (B*L) rows of 159, row stride ld >= 159 floats (any ld: rows are read as dwords); tgt (B*L) int64
+ * chord ids, CHORD_PAD = ignored (an id outside 0..158 is treated as CHORD_PAD); emo_class (B*L) the arg-max emotion class of the
+ * target's second, 0..5 (5 = neutral; anything else counts as neutral); emo_prob (B*L) that class's probability.  Per row:
+ *   pred  = arg-max, the lowest index among equal maxima;
+ *   rank  = #{j: y[j] > y[tgt]} + #{j < tgt: y[j] == y[tgt]}  (the target is in the top k iff rank < k; exact);
+ *   ce    = logsumexp(y) - y[tgt];
+ *   bce   = sum over the 159 classes of max(y,0) - y*t + log1p(exp(-|y|)), t the emotion row: one-hot 157 / 158 for a target END /
+ *           PAD, else t[j] = Q[emo_class][(j-1) % 13] for 1 <= j <= 156 with the 6 x 13 quality table of :461-475;
+ *   counted = tgt is a chord (< CHORD_END), emo_class != 5, !(emo_prob < emo_threshold);
+ *   right   = counted, pred is a chord, Q[emo_class][q-1] == 1 with q = 1 for pred == 0 ("N" reads as maj, :790-792), else
+ *           (pred-1) % 13 + 1.
+ * clip_out (B, 10) fp32, the two correspondence counts as separate floats: {n_valid (tgt != PAD), n_top1 (pred == tgt, valid rows),
+ * n_hit1, n_hit3, n_hit5, ce_sum over valid rows, bce_sum over all L rows, n_counted, n_right, L}.  Counts are exact (L <= 2^24).
+ * The sums are deterministic: a wave tree inside a row, then the rows of a clip added in row order; one launch, no atomics on
+ * floats.  pred_out / rank_out / ce_out: (B*L) each, optional (null = not written); ce_out is 0 on ignored rows. */
+int32_t amt_chord_metrics_fwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, const float* emo_prob,
+                              float emo_threshold, int32_t B, int32_t L, float* clip_out,
+                              int32_t* pred_out, int32_t* rank_out, float* ce_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -148,11 +148,30 @@ def key_from_emotion(emotion):
     return 1.0 if int(np.argmax(np.asarray(emotion, dtype=np.float32).reshape(-1))) in (1, 2, 3) else 0.0
 
 
+def eval_targets(clip, max_seq_chord):
+    """The target side of one `load_clip` result, as `evaluate.py` consumes it (`:317-328,448-451,515-516`): tgt / tgt_root /
+    tgt_attr = the chord arrays shifted by one (with the END that `read_chords` leaves after a short file's last chord), and for
+    target position i the arg-max class (first maximum) and maximum of emotion row i + 1 -- the two facts the reference's
+    `tgt_emotion` rows and `tgt_emotion_prob` carry beyond the target id itself.  All (max_seq_chord - 1,)."""
+    n = max_seq_chord
+    emo = clip["emotion"]
+    if emo.shape[0] < n:
+        raise ValueError(f"{emo.shape[0]} emotion rows for {n} chord positions: evaluation needs max_seq_video >= max_seq_chord")
+    return {"tgt": clip["chord"][1:n].copy(), "tgt_root": clip["chord_root"][1:n].copy(), "tgt_attr": clip["chord_attr"][1:n].copy(),
+            "emo_class": np.argmax(emo[1:n], axis=1).astype(np.int32), "emo_prob": np.max(emo[1:n], axis=1).astype(np.float32)}
+
+
 def load_clips(dataset_root, ids, **kw):
     """Stacks `load_clip` over ids in the layout of `synthetic.synthetic_features`: semantic (B,S,768), key (B,1),
-    scene_offset (B,S), motion (B,S,·) / (B,S), emotion (B,S,6), plus chord / chord_root / chord_attr (B,Tc)."""
+    scene_offset (B,S), motion (B,S,·) / (B,S), emotion (B,S,6), plus chord / chord_root / chord_attr (B,Tc) and, where the
+    video stream is at least as long as the chord stream, the `eval_targets` (B,Tc-1)."""
     clips = [load_clip(dataset_root, fid, **kw) for fid in ids]
-    return {k: np.stack([c[k] for c in clips]) for k in clips[0]}
+    out = {k: np.stack([c[k] for c in clips]) for k in clips[0]}
+    n = out["chord"].shape[1]
+    if out["emotion"].shape[1] >= n:
+        tg = [eval_targets(c, n) for c in clips]
+        out.update({k: np.stack([t[k] for t in tg]) for k in tg[0]})
+    return out
 
 
 def read_split(dataset_root, split="test", split_ver="v1"):

@@ -378,6 +378,16 @@ class VideoMusicTransformer_V2(nn.Module):
         # mask other than True: tgt_mask=None (:440-443), the decoder self-attention sees every position
         return self._decode(x_root, x_attr, feature_key, memory, B, S, causal=mask is True)
 
+    def forward_clips(self, x, x_root, x_attr, feature_semantic_list, feature_key, feature_scene_offset, feature_motion,
+                      feature_emotion, mask=True):
+        """`forward` for B independent clips in one pass: row b is what `forward` returns for clip b alone.  (In a batch, the
+        reference's raw RoPE view ties the clips together; the reference evaluates with batches of one.)"""
+        memory, B, S = self._encode_memory(feature_semantic_list, feature_scene_offset, feature_motion, feature_emotion, clips=True)
+        assert x_root.shape[0] == B, f"{x_root.shape[0]} chord sequences but {B} clips of video features"
+        if self.chord_embed:
+            x_root, x_attr = x, torch.zeros_like(x)
+        return self._decode(x_root, x_attr, feature_key, memory, B, S, clips=True, causal=mask is True)
+
     def _generate_clip_by_clip(self, sem, key, scene, motion, emotion, primer, primer_root, primer_attr, **kw):
         """The options whose reference semantics are per call and host-side (top-k branch with beam > 1 or beam_chance < 1:
         python's `random` per step; dropTokenRate: a fresh torch.rand mask per forward): the clips run one after the other

@@ -161,3 +161,25 @@ def selective_scan(xc, draw, dt_bias, A_log, dbc, R, D, xz, B, L, version=1, rev
     _lib.call("amt_selective_scan_fwd", p(xc), ED, p(draw), ED, p(dt_bias), p(A_log), _off(dbc, R), _off(dbc, R + N), dbc.shape[1],
               p(D), _off(xz, ED), xz.shape[1], p(y), ED, B, L, ED, N, int(version), int(reverse), _st())
     return y
+
+
+CLIP_METRIC_FIELDS = ("n_valid", "n_top1", "n_hit1", "n_hit3", "n_hit5", "ce_sum", "bce_sum", "n_counted", "n_right", "n_rows")
+
+
+def chord_metrics(logits, tgt, emo_class, emo_prob, threshold, return_rows=False):
+    """amt_chord_metrics_fwd on logits (B, L, >=159) whose last dimension is contiguous and whose rows are evenly strided;
+    tgt (B, L) int64, emo_class (B, L) int32, emo_prob (B, L) fp32.  Returns the (B, 10) per-clip rows in the order of
+    CLIP_METRIC_FIELDS, and with return_rows also pred (B, L) int32, rank (B, L) int32 and ce (B, L) fp32."""
+    B, L = tgt.shape
+    assert logits.dtype == torch.float32 and logits.shape[:2] == (B, L) and logits.stride(2) == 1
+    ld = logits.stride(1) if L > 1 else max(logits.stride(0), logits.shape[2])
+    assert B == 1 or logits.stride(0) == L * ld, "rows of logits must be evenly strided"
+    clip = torch.empty(B, len(CLIP_METRIC_FIELDS), device=logits.device, dtype=torch.float32)
+    pred = rank = ce = None
+    if return_rows:
+        pred = torch.empty(B, L, device=logits.device, dtype=torch.int32)
+        rank = torch.empty(B, L, device=logits.device, dtype=torch.int32)
+        ce = torch.empty(B, L, device=logits.device, dtype=torch.float32)
+    _lib.call("amt_chord_metrics_fwd", C.c_void_p(logits.data_ptr()), ld, p(tgt), p(emo_class), p(emo_prob), float(threshold), B, L,
+              p(clip), p(pred), p(rank), p(ce), _st())
+    return (clip, pred, rank, ce) if return_rows else clip

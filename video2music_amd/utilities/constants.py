@@ -24,6 +24,11 @@ CHORD_ATTR_SIZE = CHORD_ATTR_PAD + 1
 
 SCENE_OFFSET_MAX = 300
 
+# evaluation (utilities/constants.py:21,23 of the reference): total = LOSS_LAMBDA * chord + (1 - LOSS_LAMBDA) * emotion; a
+# second enters the emotion-chord correspondence when its strongest emotion reaches EMOTION_THRESHOLD
+LOSS_LAMBDA = 0.4
+EMOTION_THRESHOLD = 0.8
+
 # the reference trains/generates with a single 159-way head (utilities/constants.py:11)
 IS_SEPERATED = False
 RPR = True
