@@ -36,9 +36,10 @@
 #define AMT_HIP_H
 #include <stdint.h>
 
-#define AMT_ABI_VERSION 4    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
+#define AMT_ABI_VERSION 5    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
                                 3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights;
-                                4: amt_chord_metrics_fwd */
+                                4: amt_chord_metrics_fwd;
+                                5: amt_reg_metrics_fwd */
 
 #ifdef __cplusplus
 extern "C" {
@@ -466,6 +467,24 @@ int32_t amt_layernorm_post_fwd(const float* x, const float* resid, const float* 
 int32_t amt_chord_metrics_fwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, const float* emo_prob,
                               float emo_threshold, int32_t B, int32_t L, float* clip_out,
                               int32_t* pred_out, int32_t* rank_out, float* ce_out, void* stream);
+
+/* Test-split sums of the regression head (reference utilities/run_model_regression.py:70-125): both heads of VideoRegression applied
+ * to the encoder output and reduced against the targets, one launch, nothing synchronised.
+ * feat (B*S, W) fp32 with row stride ld >= W; W a positive multiple of 8, at most 1024.  w_heads (W + 1, 64) fp32, the packed heads:
+ * row k < W = {classifier.weight[0..39][k], regressor.weight[0][k], regressor.weight[1][k], 22 zeros}, row W the biases in the same
+ * order.  note_density, loudness (B*S), instrument (B*S, 40): fp32 targets.  Per row, in fp32:
+ *   nd = feat . Wr[0] + br[0],  ld = feat . Wr[1] + br[1],  z_j = feat . Wc[j] + bc[j]  (one fp32 fma chain per output on the
+ *         matrix pipe, k in a fixed order, the bias added last);
+ *   p_j = 1 / (1 + exp(-z_j));
+ *   bce = sum over j of -(t_j max(log p_j, -100) + (1 - t_j) max(log(1 - p_j), -100)): torch's binary_cross_entropy on the fp32
+ *         probability, NOT the logits form -- where p rounds to 1 or 0 the term is exactly 100 (or 0), as in the reference.
+ * clip_out (B, 4) fp32 = {sum (nd - note_density)^2, sum (ld - loudness)^2, sum bce, S} over ALL S rows of the clip (padded seconds
+ * count, as the reference averages over max_sequence_video rows).  Deterministic: a fixed 40-term tree inside a row, then the rows of a clip
+ * added in row order; no atomics on floats; the optional outputs do not change the sums.
+ * ln_nd_out (B*S, 2) = {nd, ld} and inst_out (B*S, 40) = p: optional (null = not written). */
+int32_t amt_reg_metrics_fwd(const float* feat, int32_t ld, int32_t W, const float* w_heads, const float* note_density,
+                            const float* loudness, const float* instrument, int32_t B, int32_t S, float* clip_out,
+                            float* ln_nd_out, float* inst_out, void* stream);
 
 #ifdef __cplusplus
 }

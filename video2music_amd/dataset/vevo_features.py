@@ -1,9 +1,10 @@
 """MuVi-Sync ("vevo") feature files -> the tensors `VideoMusicTransformer.forward/generate` take.
 
 Host-side reader for the on-disk layout the reference's `VevoDataset.createSample` consumes
-(`dataset/vevo_dataset.py:58-236` for the directory tree, `:241-554` for the parsing rules).  Only the
-inputs of the chord model are read (chords, key, semantic, scene offset, motion, emotion); the
-regression targets (loudness, note density, instrument) belong to SURVEY.md §8 row f2.
+(`dataset/vevo_dataset.py:58-236` for the directory tree, `:241-554` for the parsing rules).  By default only
+the inputs of the chord model are read (chords, key, semantic, scene offset, motion, emotion); the targets of the
+regression head (loudness, note density, instrument) are read on request
+(`read_regression_targets`, or `regression_targets=True` on `load_clip` / `load_clips`) for `evaluate_regression`.
 
     <root>/vevo_chord/lab_v2_norm/origin/<id>.lab     "key C major" then "<t> <chord>" per second
     <root>/vevo_semantic/origin/<p1>/<p2>/<id>.npy    (n, 768) float            (vis_models "p1/p2")
@@ -11,6 +12,9 @@ regression targets (loudness, note density, instrument) belong to SURVEY.md §8 
     <root>/vevo_motion/origin/<id>.lab                "<t> <motion>"             (motion_type 0)
     <root>/vevo_motion/option1|option2/<id>.npy       (n, 512|768) float         (motion_type 1|2)
     <root>/vevo_emotion/<emo_model>/origin/<id>.lab   "time ..." header, then "<t> p1 .. p6|p5"
+    <root>/vevo_loudness/origin/<id>.lab              "<t> <loudness>"           (regression targets)
+    <root>/vevo_note_density/origin/<id>.lab          "<t> <note density>"
+    <root>/vevo_instrument/thresholding/<id>.csv      a header line, then 40 comma-separated 0/1 per second
 
 Quirks kept on purpose (they decide what the model sees):
   * every per-second text stream stops at the first line whose time is >= max_seq_**chord**
@@ -20,7 +24,10 @@ Quirks kept on purpose (they decide what the model sees):
   * a plain-root chord ("G") gets attribute id 1 = "maj", "N" gets (0, 0) (`:270-286`);
   * a chord file that ends before max_seq_chord leaves END (not PAD) right after its last chord: the reference sets
     END in the shifted target *view*, which aliases the chord tensor (`:318-330`);
-  * key = 0 iff the normalised chord file's key line contains "major" (`:291-294`).
+  * key = 0 iff the normalised chord file's key line contains "major" (`:291-294`);
+  * the regression targets are max_seq_**video** rows of PAD, but the two text streams stop at the first time
+    >= max_seq_**chord** and the instrument rows are cut at max_seq_chord (`:381-413,453-459`); the first line of the
+    instrument csv is a header whatever it holds.
 """
 import os
 
@@ -110,10 +117,29 @@ def clip_paths(dataset_root, fid, vis_models="2d/clip_l14p", emo_model="6c_l14p"
     }
 
 
+def read_regression_targets(dataset_root, fid, max_seq_video=300, max_seq_chord=300):
+    """The regression head's targets of one clip (`dataset/vevo_dataset.py:381-413,453-459`): note_density (S,), loudness (S,),
+    instrument (S, 40), fp32, S = max_seq_video rows of PAD filled from the files up to max_seq_chord seconds."""
+    S, Tc = max_seq_video, max_seq_chord
+    out = {"note_density": read_series(os.path.join(dataset_root, "vevo_note_density", "origin", fid + ".lab"), S, Tc, pad=C.NOTE_DENSITY_PAD),
+           "loudness": read_series(os.path.join(dataset_root, "vevo_loudness", "origin", fid + ".lab"), S, Tc, pad=C.LOUDNESS_PAD)}
+    path = os.path.join(dataset_root, "vevo_instrument", "thresholding", fid + ".csv")
+    with open(path, encoding="utf-8") as fh:
+        lines = [line.strip() for line in fh if line.strip()][1:]            # the first line is the header
+    data = np.array([[float(v) for v in line.split(",")] for line in lines[:Tc]], dtype=np.float64).reshape(-1, C.INSTRUMENT_SIZE)
+    if data.shape[0] > S:
+        raise ValueError(f"{path}: {data.shape[0]} instrument rows for max_seq_video = {S} (the reference fails here too)")
+    inst = np.full((S, C.INSTRUMENT_SIZE), C.INSTRUMENT_PAD, dtype=np.float32)
+    inst[:data.shape[0]] = data
+    out["instrument"] = inst
+    return out
+
+
 def load_clip(dataset_root, fid, vis_models="2d/clip_l14p", emo_model="6c_l14p", motion_type=1,
-              max_seq_video=300, max_seq_chord=300):
+              max_seq_video=300, max_seq_chord=300, regression_targets=False):
     """One clip as numpy arrays: semantic (S,768), scene_offset (S,), motion (Tc,512|768) or (S,), emotion (S,6|5),
-    key (1,), chord/chord_root/chord_attr (Tc,) int64 (PAD where the file has no chord; all PAD without a file)."""
+    key (1,), chord/chord_root/chord_attr (Tc,) int64 (PAD where the file has no chord; all PAD without a file); with
+    `regression_targets` also note_density (S,), loudness (S,), instrument (S,40)."""
     if len(vis_models.split(" ")) != 1:
         raise NotImplementedError("one semantic model per run, as in the reference's defaults (vis_models='2d/clip_l14p')")
     p = clip_paths(dataset_root, fid, vis_models, emo_model, motion_type)
@@ -137,6 +163,8 @@ def load_clip(dataset_root, fid, vis_models="2d/clip_l14p", emo_model="6c_l14p",
         key = None
     out.update(chord=chord, chord_root=root, chord_attr=attr)
     out["key"] = np.array([key_from_emotion(out["emotion"]) if key is None else key], dtype=np.float32)
+    if regression_targets:
+        out.update(read_regression_targets(dataset_root, fid, S, Tc))
     return out
 
 

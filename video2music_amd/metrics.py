@@ -5,6 +5,10 @@ The per-token work (arg-max, rank of the target, cross-entropy, BCE against the 
 ``amt_chord_metrics_fwd`` (``csrc/metrics.hip``), which returns ten numbers per clip; ``summarize`` forms the reference's per-clip
 ratios from them on the host and averages over clips the way ``eval_model`` does at its default ``batch_size`` 1 (one clip per
 "batch": ``compute_hits_k`` only squeezes a batch of one, ``dataset/vevo_dataset.py:682``).
+
+The regression head's figures (``evaluate_regression.py``, ``utilities/run_model_regression.py:70-125``: total loss, RMSE note
+density, RMSE loudness, BCE instrument) come the same way: ``amt_reg_metrics_fwd`` (``csrc/reg_metrics.hip``) applies both heads to the
+encoder output and returns four numbers per clip; ``regression_clip_figures`` / ``summarize_regression`` form the figures.
 """
 import numpy as np
 import torch
@@ -96,3 +100,49 @@ def confusion_matrix(true, pred, labels):
     m = np.zeros((len(labels), len(labels)), dtype=np.int64)
     np.add.at(m, (i[keep], j[keep]), 1)
     return m
+
+
+REG_FIELDS = ops.REG_METRIC_FIELDS
+
+
+def regression_metrics(model, feat, note_density, loudness, instrument, return_rows=False):
+    """Per-clip sums of the regression evaluation.  model: a `VideoRegression` on the GPU; feat (B, S, W): its `get_feature` output;
+    note_density / loudness (B, S), instrument (B, S, 40): the targets.  Returns {field: (B,) fp32 tensor} for the fields of
+    ``REG_FIELDS``; with ``return_rows`` also "ln_nd" (B, S, 2) = (note density, loudness) and "inst" (B, S, 40), what the model's
+    `forward` returns.  No host synchronisation."""
+    dev = feat.device
+    if feat.dim() != 3:
+        raise ValueError(f"feat must be (B, S, W), got {tuple(feat.shape)}")
+    B, S = feat.shape[:2]
+    f32 = lambda t, shape: torch.as_tensor(t).to(device=dev, dtype=torch.float32).reshape(shape).contiguous()
+    out = ops.reg_metrics(feat, model.packed_heads(), f32(note_density, (B, S)), f32(loudness, (B, S)),
+                          f32(instrument, (B, S, C.INSTRUMENT_SIZE)), return_rows=return_rows)
+    clip = out[0] if return_rows else out
+    res = {k: clip[:, i] for i, k in enumerate(REG_FIELDS)}
+    if return_rows:
+        res.update(ln_nd=out[1], inst=out[2])
+    return res
+
+
+def regression_clip_figures(per_clip):
+    """The per-clip figures ``eval_model`` accumulates at its batch size of 1 (:106-118), as float64 arrays over clips:
+    rmse_note_density = sqrt(sse_nd / S), rmse_loudness = sqrt(sse_l / S), bce_instrument = bce_sum / (40 S) and
+    total_loss = sqrt((sse_nd + sse_l) / (2 S)) + bce_instrument (the mse_loss over both columns at once)."""
+    c = {k: np.asarray(per_clip[k].detach().cpu() if torch.is_tensor(per_clip[k]) else per_clip[k], dtype=np.float64).reshape(-1)
+         for k in REG_FIELDS}
+    S = c["n_rows"]
+    out = {"rmse_note_density": np.sqrt(c["sse_note_density"] / S), "rmse_loudness": np.sqrt(c["sse_loudness"] / S),
+           "bce_instrument": c["bce_sum"] / (C.INSTRUMENT_SIZE * S)}
+    out["total_loss"] = np.sqrt((c["sse_note_density"] + c["sse_loudness"]) / (2 * S)) + out["bce_instrument"]
+    return out
+
+
+def summarize_regression(per_clip):
+    """The four averages ``eval_model`` returns (:120-125): the per-clip figures -- each clip's own square root taken first --
+    added as running Python sums in clip order and divided by the number of clips."""
+    r = regression_clip_figures(per_clip)
+
+    def mean(a):
+        return sum(a.tolist()) / len(a) if len(a) else float("nan")
+    return {"avg_total_loss": mean(r["total_loss"]), "avg_rmse_note_density": mean(r["rmse_note_density"]),
+            "avg_rmse_loudness": mean(r["rmse_loudness"]), "avg_bce_instrument": mean(r["bce_instrument"])}

@@ -206,6 +206,16 @@ class VideoRegression(nn.Module):
                 self._Wx.append(t)
             self._derived_sig = sig
 
+    def packed_heads(self):
+        """Both heads as the one packed, transposed tensor `ops.reg_metrics` reads (`ops.pack_reg_heads`); rebuilt when a head
+        parameter changes."""
+        ps = (self.regressor.weight, self.regressor.bias, self.classifier[0].weight, self.classifier[0].bias)
+        sig = tuple((q.data_ptr(), q._version) for q in ps)
+        cache = self.__dict__.setdefault("_heads_cache", (None, None))
+        if cache[0] != sig:
+            cache = self.__dict__["_heads_cache"] = (sig, ops.pack_reg_heads(*ps))
+        return cache[1]
+
     def _conv7_silu(self, x, B, S):
         """CNN_GRU's Conv1d(d, d, kernel 7, padding 3) + SiLU over time (:88-91, :97-100) as seven accumulating GEMMs: the clips
         are laid end to end with 3 zero frames on each side, tap j of output row r reads row r + j; the SiLU rides on the last one."""

@@ -183,3 +183,41 @@ def chord_metrics(logits, tgt, emo_class, emo_prob, threshold, return_rows=False
     _lib.call("amt_chord_metrics_fwd", C.c_void_p(logits.data_ptr()), ld, p(tgt), p(emo_class), p(emo_prob), float(threshold), B, L,
               p(clip), p(pred), p(rank), p(ce), _st())
     return (clip, pred, rank, ce) if return_rows else clip
+
+
+REG_METRIC_FIELDS = ("sse_note_density", "sse_loudness", "bce_sum", "n_rows")
+REG_HEADS_LD = 64           # row stride of the packed heads amt_reg_metrics_fwd reads: one dword per lane
+
+
+def pack_reg_heads(reg_w, reg_b, cls_w, cls_b):
+    """(W + 1, 64) packed, transposed heads of amt_reg_metrics_fwd: row k = {classifier.weight[:, k], regressor.weight[:, k], zeros},
+    row W the biases in the same order."""
+    W = reg_w.shape[1]
+    n = cls_w.shape[0]
+    t = torch.zeros(W + 1, REG_HEADS_LD, device=reg_w.device, dtype=torch.float32)
+    t[:W, :n] = cls_w.detach().t()
+    t[:W, n:n + 2] = reg_w.detach().t()
+    t[W, :n] = cls_b.detach()
+    t[W, n:n + 2] = reg_b.detach()
+    return t
+
+
+def reg_metrics(feat, w_heads, note_density, loudness, instrument, return_rows=False):
+    """amt_reg_metrics_fwd on feat (B, S, W) fp32 whose last dimension is contiguous and whose rows are evenly strided; w_heads from
+    pack_reg_heads; note_density / loudness (B, S), instrument (B, S, 40) contiguous fp32.  Returns the (B, 4) per-clip rows in the
+    order of REG_METRIC_FIELDS, and with return_rows also ln_nd (B, S, 2) and inst (B, S, 40)."""
+    B, S = note_density.shape
+    W = feat.shape[2]
+    assert feat.dtype == torch.float32 and feat.shape[:2] == (B, S) and feat.stride(2) == 1
+    assert w_heads.shape == (W + 1, REG_HEADS_LD) and w_heads.is_contiguous() and w_heads.dtype == torch.float32
+    assert loudness.shape == (B, S) and instrument.shape == (B, S, 40)
+    ld = feat.stride(1) if S > 1 else max(feat.stride(0), W)
+    assert B == 1 or feat.stride(0) == S * ld, "rows of feat must be evenly strided"
+    clip = torch.empty(B, len(REG_METRIC_FIELDS), device=feat.device, dtype=torch.float32)
+    ln_nd = inst = None
+    if return_rows:
+        ln_nd = torch.empty(B, S, 2, device=feat.device, dtype=torch.float32)
+        inst = torch.empty(B, S, 40, device=feat.device, dtype=torch.float32)
+    _lib.call("amt_reg_metrics_fwd", C.c_void_p(feat.data_ptr()), ld, W, p(w_heads), p(note_density), p(loudness), p(instrument), B, S,
+              p(clip), p(ln_nd), p(inst), _st())
+    return (clip, ln_nd, inst) if return_rows else clip

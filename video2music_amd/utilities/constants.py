@@ -29,6 +29,12 @@ SCENE_OFFSET_MAX = 300
 LOSS_LAMBDA = 0.4
 EMOTION_THRESHOLD = 0.8
 
+# regression targets (utilities/constants.py:77-85)
+NOTE_DENSITY_PAD = 0.0
+LOUDNESS_PAD = 0.0
+INSTRUMENT_SIZE = 40
+INSTRUMENT_PAD = 0
+
 # the reference trains/generates with a single 159-way head (utilities/constants.py:11)
 IS_SEPERATED = False
 RPR = True
