@@ -36,10 +36,11 @@
 #define AMT_HIP_H
 #include <stdint.h>
 
-#define AMT_ABI_VERSION 5    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
+#define AMT_ABI_VERSION 6    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
                                 3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights;
                                 4: amt_chord_metrics_fwd;
-                                5: amt_reg_metrics_fwd */
+                                5: amt_reg_metrics_fwd;
+                                6: amt_rnn_seq_train_fwd, amt_rnn_seq_bwd, amt_reg_loss_fwd_bwd */
 
 #ifdef __cplusplus
 extern "C" {
@@ -374,6 +375,23 @@ int32_t amt_v2_step(const void* const* tab, int32_t n_layers, int32_t H, int32_t
 int32_t amt_rnn_seq_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
                         int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, void* stream);
 
+/* amt_rnn_seq_fwd that also keeps what the backward needs: y is computed by the same arithmetic, bit for bit.
+ * reserve (B*L, ldr), ldr >= n_dirs * C * d, row b*L + t, direction dir at columns [dir*C*d, (dir+1)*C*d), in blocks of d:
+ *   LSTM (C = 5): i, f, g, o (activated), c_t            GRU (C = 4): r, z, n (activated), W_hn h_{t-1} + b_hn */
+int32_t amt_rnn_seq_train_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
+                              float* reserve, int32_t ldr, int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse,
+                              int32_t n_dirs, void* stream);
+/* Backpropagation through time of one layer (one workgroup per clip and direction, W_hh^T in registers, no atomics: the same
+ * inputs give the same bits).  dy (B*L, lddy): gradient of y, this layer's n_dirs*d columns; reserve / y as amt_rnn_seq_train_fwd
+ * left them; w_hh as there.  dxproj (B*L, ldxp), n_dirs*gates*d columns laid out like xproj: the gradient with respect to the
+ * pre-activations as the input side sees them (dW_ih = dxproj^T x, db_ih = column sums, dx = dxproj W_ih), written once per step.
+ * LSTM: the hidden side sees the same values (dW_hh = dxproj^T h_prev, db_hh = db_ih); dhn is not used (may be null).
+ * GRU: the hidden side's n block is r * (the input side's); it goes to dhn (B*L, lddhn), n_dirs*d columns, required.
+ * h_prev is y shifted by one step in the direction's order, zero at its start.  Shapes and caps as amt_rnn_seq_fwd. */
+int32_t amt_rnn_seq_bwd(const float* dy, int32_t lddy, const float* reserve, int32_t ldr, const float* y, int32_t ldy,
+                        const float* w_hh, float* dxproj, int32_t ldxp, float* dhn, int32_t lddhn, int32_t B, int32_t L,
+                        int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, void* stream);
+
 /* The same step for B independent clips in lockstep (all at one position): projections are one launch over B rows (weights
  * read once per step, not once per clip), the caches carry a leading clip dimension (self K/V: B, H, max_seq, hd; cross K/V:
  * B, H, S, hd), a mixture layer evaluates all experts on all rows and combines each row's routed pair in expert-index
@@ -485,6 +503,20 @@ int32_t amt_chord_metrics_fwd(const float* logits, int32_t ld, const int64_t* tg
 int32_t amt_reg_metrics_fwd(const float* feat, int32_t ld, int32_t W, const float* w_heads, const float* note_density,
                             const float* loudness, const float* instrument, int32_t B, int32_t S, float* clip_out,
                             float* ln_nd_out, float* inst_out, void* stream);
+
+/* Training loss of the regression head (reference utilities/run_model_regression.py:33-39) and its gradient, one launch:
+ *   SmoothL1Loss()(ln_nd, [note_density | loudness]) + binary_cross_entropy(inst, instrument)
+ * ln_nd (rows, 2) = {nd, ld}; inst (rows, 40) the fp32 probabilities; note_density / loudness (rows); instrument (rows, 40).
+ * loss[3] = {total, SmoothL1 part, BCE part}; d_ln_nd (rows, 2); d_logit (rows, 40): the BCE gradient with respect to the
+ * classifier's LOGITS (torch's BCE backward times the sigmoid's: (p - t) / (40 rows) for 0 < p < 1, exactly 0 at a saturated p).
+ * Logs clamped at -100.  ws: AMT_REG_LOSS_WS_FLOATS floats of scratch, 16-byte aligned, used by this call alone until it has finished
+ * (a ticket counter, zeroed by the call, and two partial sums per workgroup).  min(256, ceil(40 rows / 4096)) workgroups of 1024
+ * threads; the order of every addition is a function of `rows` alone and no floating-point atomic is used: the same inputs give the
+ * same bits. */
+#define AMT_REG_LOSS_WS_FLOATS 516
+int32_t amt_reg_loss_fwd_bwd(const float* ln_nd, const float* inst, const float* note_density, const float* loudness,
+                             const float* instrument, int32_t rows, float* loss, float* d_ln_nd, float* d_logit, float* ws,
+                             void* stream);
 
 #ifdef __cplusplus
 }

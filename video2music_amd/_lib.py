@@ -113,12 +113,15 @@ SIGNATURES = {
     "amt_v2_step_batch": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "amt_chord_metrics_fwd": [_P, _I, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P],
     "amt_reg_metrics_fwd": [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "amt_rnn_seq_train_fwd": [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "amt_rnn_seq_bwd": [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "amt_reg_loss_fwd_bwd": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
 }
 _RESTYPES = {"amt_last_error": C.c_char_p, "amt_decode_step_bytes": C.c_int64, "amt_moe_scratch_floats": C.c_int64, "amt_moe_topk_scratch_floats": C.c_int64,
              "amt_v2_step_ws_floats": C.c_int64, "amt_v2_step_batch_ws_floats": C.c_int64, "amt_moe_ep_expert_scratch_floats": C.c_int64}
 _NO_STATUS = set(_RESTYPES) | {"amt_abi_version", "amt_v2_last_step_launches"}
 
-ABI_VERSION = 5         # AMT_ABI_VERSION of include/amt_hip.h these prototypes were written against
+ABI_VERSION = 6         # AMT_ABI_VERSION of include/amt_hip.h these prototypes were written against
 
 _lib = None
 

@@ -1,0 +1,173 @@
+"""`torch.autograd.Function`s over the library calls: what `VideoRegression` is built from in the training state
+(regModel 'lstm' / 'bilstm' / 'gru' / 'bigru'), so that `loss.backward()` and any torch optimiser work on the module's own parameters.
+
+    LinearFn          y = act(x w^T + b), act 0 none / 2 sigmoid      amt_linear_ex_fwd; backward: two GEMMs
+    SigmoidHeadFn     the classifier head; hands out a second, empty-storage output that stands for its logits, so that the
+                      fused loss can send its logit gradient straight to the head's GEMMs (losses.regression_train_loss)
+    RnnLayerFn        one nn.LSTM / nn.GRU layer, all its directions    amt_linear_ex_fwd + amt_rnn_seq_train_fwd;
+                      backward: amt_rnn_seq_bwd + GEMMs
+    RegLossFn         SmoothL1 + BCE and both gradients                 amt_reg_loss_fwd_bwd
+
+Every dense product of the backward runs on `amt_linear_ex_fwd` (y = x w^T, K a multiple of 32): `a b` and `a^T b` go there as
+transposed, zero-padded copies made by torch (`mm_nt`, `mm_tn`).  A bias gradient is the column of ones appended to the right
+operand of its weight's product.  Nothing here uses a floating-point atomic: the same inputs give the same gradients, bit for bit.
+"""
+import torch
+
+from . import ops
+
+
+def _ceil32(n):
+    return (n + 31) // 32 * 32
+
+
+def _padded(t, cols):
+    """t (rows, k) as a contiguous (rows, cols) tensor, zeros past k; t itself when it already is one."""
+    if t.shape[1] == cols and t.is_contiguous():
+        return t
+    out = torch.zeros(t.shape[0], cols, device=t.device, dtype=torch.float32)
+    out[:, :t.shape[1]] = t
+    return out
+
+
+def mm_nt(a, b, bias=None, act=0):
+    """act(a (M, K) . b (N, K)^T + bias) on the library's GEMM; K is padded to a multiple of 32 where it is not one."""
+    Kp = _ceil32(a.shape[1])
+    return ops.linear_ex(_padded(a, Kp), _padded(b, Kp), bias, act=act)
+
+
+def mm_tn(a, b, ones=False):
+    """a (M, P)^T . b (M, Q) -> (P, Q); with ones=True b gets a column of ones: (P, Q + 1), the last column the column sums of a."""
+    M, Q = b.shape
+    Mp = _ceil32(M)
+    at = torch.zeros(a.shape[1], Mp, device=a.device, dtype=torch.float32)
+    at[:, :M] = a.t()
+    bt = torch.zeros(Q + int(ones), Mp, device=a.device, dtype=torch.float32)
+    bt[:Q, :M] = b.t()
+    if ones:
+        bt[Q, :M] = 1.0
+    return ops.linear_ex(at, bt)
+
+
+def _linear_backward(ctx, dz, x, w, need_x):
+    """(dx, dw, db) of z = x w^T + b from dz; w (N, K) may be narrower than x (the zero-padded in-projection): dw keeps w's width."""
+    dx = mm_nt(dz, w.t()) if need_x else None
+    if dx is not None and dx.shape[1] != x.shape[1]:
+        dx = _padded(dx, x.shape[1])
+    dwb = mm_tn(dz, x, ones=True)
+    return dx, dwb[:, :w.shape[1]].contiguous(), dwb[:, x.shape[1]].contiguous()
+
+
+class LinearFn(torch.autograd.Function):
+    """y = act(x w^T + b); x (M, K), K a multiple of 32; w (N, K0 <= K) with `w_fwd` its zero-padded (N, K) copy when K0 < K."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, act=0, w_fwd=None):
+        assert act in (0, 2)
+        y = ops.linear_ex(x, (w if w_fwd is None else w_fwd).detach(), b.detach(), act=act)
+        ctx.act = act
+        ctx.save_for_backward(x, w, y if act == 2 else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        dz = dy.contiguous() if ctx.act == 0 else (dy * y * (1.0 - y)).contiguous()      # the sigmoid's derivative from its output
+        dx, dw, db = _linear_backward(ctx, dz, x, w.detach(), ctx.needs_input_grad[0])
+        return dx, dw, db, None, None
+
+
+class SigmoidHeadFn(torch.autograd.Function):
+    """The classifier head: p = sigmoid(x w^T + b) and `logits`, an output without storage of its own (a zero expanded to p's shape)
+    that stands for x w^T + b in the graph.  A gradient that arrives at p is taken through the sigmoid's derivative; one that arrives
+    at `logits` (RegLossFn's) is used as it is."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        p = ops.linear_ex(x, w.detach(), b.detach(), act=2)
+        ctx.save_for_backward(x, w, p)
+        ctx.set_materialize_grads(False)
+        return p, p.new_zeros(()).expand(p.shape)
+
+    @staticmethod
+    def backward(ctx, dp, dlogits):
+        x, w, p = ctx.saved_tensors
+        dz = None if dp is None else dp * p * (1.0 - p)
+        if dlogits is not None:
+            dz = dlogits if dz is None else dz + dlogits
+        if dz is None:
+            return None, None, None
+        return _linear_backward(ctx, dz.contiguous(), x, w.detach(), ctx.needs_input_grad[0])
+
+
+class RnnLayerFn(torch.autograd.Function):
+    """One layer of nn.LSTM (gates 4) / nn.GRU (gates 3) over rows x (B*L, in): y (B*L, n_dirs*d).
+
+    apply(x, B, L, gates, reverse, stacked, *params): `params` the layer's nn.Parameters, per direction weight_ih, bias_ih, weight_hh,
+    bias_hh (they receive the gradients); `stacked` = (W_ih, b_ih, W_hh, b_hh) with the directions stacked along the rows, the
+    tensors the kernels read.  reverse applies to a single direction only (two directions: forward, then reversed)."""
+
+    @staticmethod
+    def forward(ctx, x, B, L, gates, reverse, stacked, *params):
+        wi, bi, wh, bh = stacked
+        n_dirs, d = len(params) // 4, wh.shape[1]
+        M = B * L
+        xproj = mm_nt(x, wi, bi)
+        y = torch.empty(M, n_dirs * d, device=x.device, dtype=torch.float32)
+        reserve = torch.empty(M, n_dirs * ops.rnn_reserve_cols(gates) * d, device=x.device, dtype=torch.float32)
+        ops.rnn_seq_train(xproj, wh, bh, y, 0, reserve, B, L, d, gates, reverse=reverse, n_dirs=n_dirs)
+        ctx.dims = (B, L, d, gates, bool(reverse), n_dirs)
+        ctx.save_for_backward(x, y, reserve, wi, wh)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, reserve, wi, wh = ctx.saved_tensors
+        B, L, d, gates, reverse, n_dirs = ctx.dims
+        M, R = B * L, gates * d
+        dy = dy.contiguous()
+        dxp = torch.empty(M, n_dirs * R, device=x.device, dtype=torch.float32)
+        dhn = torch.empty(M, n_dirs * d, device=x.device, dtype=torch.float32) if gates == 3 else None
+        ops.rnn_seq_bwd(dy, 0, reserve, y, 0, wh, dxp, dhn, B, L, d, gates, reverse=reverse, n_dirs=n_dirs)
+        dx = mm_nt(dxp, wi.t()) if ctx.needs_input_grad[0] else None
+        dwi = mm_tn(dxp, x, ones=True)                                   # (n_dirs*R, in + 1): dW_ih | db_ih
+        y3 = y.view(B, L, n_dirs * d)
+        grads = []
+        for r in range(n_dirs):
+            back = reverse if n_dirs == 1 else r == 1
+            # h_prev: y one step earlier in the direction's own order, zeros where the walk starts
+            hp = torch.zeros(B, L, d, device=x.device, dtype=torch.float32)
+            if L > 1:
+                if back:
+                    hp[:, :-1] = y3[:, 1:, r * d:(r + 1) * d]
+                else:
+                    hp[:, 1:] = y3[:, :-1, r * d:(r + 1) * d]
+            dah = dxp[:, r * R:(r + 1) * R]
+            if gates == 3:                                               # the hidden side's n block
+                dah = torch.cat([dah[:, :2 * d], dhn[:, r * d:(r + 1) * d]], dim=1)
+            dwh = mm_tn(dah, hp.view(M, d), ones=True)                   # (R, d + 1): dW_hh | db_hh
+            blk = dwi[r * R:(r + 1) * R]
+            grads += [blk[:, :x.shape[1]].contiguous(), blk[:, x.shape[1]].contiguous(), dwh[:, :d].contiguous(), dwh[:, d].contiguous()]
+        return (dx, None, None, None, None, None, *grads)
+
+
+class RegLossFn(torch.autograd.Function):
+    """apply(ln_nd (rows, 2), logits (rows, 40; SigmoidHeadFn's stand-in), p (rows, 40), note_density, loudness, instrument) ->
+    the scalar training loss; its backward hands the kernel's two gradients on, scaled by the incoming one."""
+
+    @staticmethod
+    def forward(ctx, ln_nd, logits, p, note_density, loudness, instrument):
+        loss, d_ln_nd, d_logit = ops.reg_loss(ln_nd.contiguous(), p.contiguous(), note_density, loudness, instrument)
+        ctx.save_for_backward(d_ln_nd, d_logit)
+        ctx.parts = loss
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        d_ln_nd, d_logit = ctx.saved_tensors
+        return d_ln_nd * g, d_logit * g, None, None, None, None
+
+
+def dropout_mask(shape, p, device):
+    """The multiplier of nn.Dropout(p) in training: 0 with probability p, else 1 / (1 - p); drawn by torch on the device."""
+    return (torch.rand(shape, device=device) >= p).to(torch.float32) / (1.0 - p)

@@ -17,6 +17,11 @@ library's kernels; no torch arithmetic runs in `forward`:
     LSTM / GRU recurrence     amt_rnn_seq_fwd (both directions of a layer in one launch)
 
 The backward Mamba block runs with `reverse=1` instead of `torch.flip` before and after (bimamba.py:171-185).
+
+Training: for 'lstm' / 'bilstm' / 'gru' / 'bigru', `forward` / `get_feature` called in the training state with gradients enabled build
+their result through the autograd Functions of `video2music_amd/autograd.py` on the module's own parameters (amt_rnn_seq_train_fwd,
+amt_rnn_seq_bwd, the same GEMMs), so `loss.backward()` and a torch optimiser work; every other state and regModel runs the inference
+path above on detached parameters.
 """
 import math
 
@@ -171,6 +176,7 @@ class VideoRegression(nn.Module):
         self.regressor = nn.Linear(width, 2)
         self.classifier = nn.Sequential(nn.Linear(width, INSTRUMENT_SIZE), nn.Sigmoid())
         self._derived_sig = None
+        self.dropout_masks = None       # training state: multipliers to use in place of drawn ones (see _get_feature_train)
 
     # zero-padded copies of the weights whose K (or row count) does not fit the GEMM's steps (rebuilt when they change)
     def _derived(self):
@@ -261,6 +267,39 @@ class VideoRegression(nn.Module):
                                version=self._version, reverse=reverse)
         return ops.linear_ex(g, m.out_proj.weight.detach(), m.out_proj.bias.detach(), resid=resid)
 
+    def _train_path(self):
+        """The state in which the four recurrent regModels build an autograd graph (video2music_amd/autograd.py); every other state
+        and regModel runs the inference kernels on detached parameters."""
+        return self.training and torch.is_grad_enabled() and self.regModel in ("lstm", "bilstm", "gru", "bigru")
+
+    def _get_feature_train(self, vf, B, S):
+        """get_feature's recurrent branch through the autograd Functions, on the module's own parameters.  Dropout sits where the
+        reference has it: after in_proj (:169) and between the recurrent layers, not after the last (nn.LSTM / nn.GRU).  The
+        multipliers (0 or 1 / (1 - p), shape (B*S, width)) are drawn by torch on the device, or taken in this order from
+        `self.dropout_masks` when that is a list; the ones used are kept in `self.last_dropout_masks`."""
+        from .. import autograd as AG
+        given = list(self.dropout_masks) if self.dropout_masks is not None else None
+        used = []
+
+        def drop(x, p):
+            if p <= 0.0:
+                return x
+            mask = given.pop(0) if given is not None else AG.dropout_mask(x.shape, p, x.device)
+            used.append(mask)
+            return x * mask
+
+        lin = self.in_proj[0]
+        x = drop(AG.LinearFn.apply(vf, lin.weight, lin.bias, 0, self._Win), self.in_proj[1].p)
+        gates = 4 if isinstance(self._rnn_mod, nn.LSTM) else 3
+        for l in range(self.n_layers):
+            names = [n + f"_l{l}" + sfx for sfx in (("", "_reverse") if self._dirs == 2 else ("",))
+                     for n in ("weight_ih", "bias_ih", "weight_hh", "bias_hh")]
+            x = AG.RnnLayerFn.apply(x, B, S, gates, False, self._rnn_layer(l), *[getattr(self._rnn_mod, n) for n in names])
+            if l < self.n_layers - 1:
+                x = drop(x, self._rnn_mod.dropout)
+        self.__dict__["last_dropout_masks"] = used
+        return x.view(B, S, self._dirs * self.d_model)
+
     def get_feature(self, feature_semantic_list, feature_scene_offset, feature_motion, feature_emotion):
         """video_regression.py:199-238: (B, S, d_model) encoder output.  Scene offset and motion are not used."""
         self._derived()
@@ -273,6 +312,8 @@ class VideoRegression(nn.Module):
         if sem.shape[2] + emo.shape[2] != self.total_vf_dim:
             raise ValueError(f"semantic ({sem.shape[2]}) + emotion ({emo.shape[2]}) features != total_vf_dim ({self.total_vf_dim})")
         vf = ops.concat2(sem.view(B * S, -1), emo.view(B * S, -1), self._Fpad)
+        if self._train_path():
+            return self._get_feature_train(vf, B, S)
         x = ops.linear_ex(vf, self._Win, self.in_proj[0].bias.detach())
         if self._rnn:                                   # nn.LSTM / nn.GRU (:124-135): per layer and direction, input GEMM + recurrence
             gates, d = (4 if isinstance(self._rnn_mod, nn.LSTM) else 3), self.d_model
@@ -321,6 +362,13 @@ class VideoRegression(nn.Module):
         out = self.get_feature(feature_semantic_list, feature_scene_offset, feature_motion, feature_emotion).contiguous()
         B, S, d = out.shape
         rows = out.view(B * S, d)
+        if self._train_path():                          # the heads on the graph; `inst` carries the stand-in for its logits
+            from .. import autograd as AG
+            ln_nd = AG.LinearFn.apply(rows, self.regressor.weight, self.regressor.bias)
+            inst, logits = AG.SigmoidHeadFn.apply(rows, self.classifier[0].weight, self.classifier[0].bias)
+            inst = inst.view(B, S, INSTRUMENT_SIZE)
+            inst._amt_logits = logits
+            return ln_nd.view(B, S, 2), inst
         ln_nd = ops.linear_ex(rows, self.regressor.weight.detach(), self.regressor.bias.detach())
         inst = ops.linear_ex(rows, self.classifier[0].weight.detach(), self.classifier[0].bias.detach(), act=2)
         return ln_nd.view(B, S, 2), inst.view(B, S, INSTRUMENT_SIZE)

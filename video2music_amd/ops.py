@@ -153,6 +153,45 @@ def rnn_seq(xproj, w_hh, b_hh, y, col, B, L, d, gates, reverse=False, n_dirs=1):
     return y
 
 
+def rnn_reserve_cols(gates):
+    """Reserve columns per direction in units of d (include/amt_hip.h, amt_rnn_seq_train_fwd): LSTM i, f, g, o, c; GRU r, z, n, W_hn h + b_hn."""
+    return 5 if gates == 4 else 4
+
+
+def rnn_seq_train(xproj, w_hh, b_hh, y, col, reserve, B, L, d, gates, reverse=False, n_dirs=1):
+    """`rnn_seq` that also fills reserve (B*L, >= n_dirs * rnn_reserve_cols(gates) * d) for `rnn_seq_bwd`; y is the same bits."""
+    _lib.call("amt_rnn_seq_train_fwd", p(xproj), xproj.shape[1], p(w_hh), p(b_hh), _off(y, col), y.shape[1], p(reserve), reserve.shape[1],
+              B, L, d, gates, int(reverse), n_dirs, _st())
+    return y
+
+
+def rnn_seq_bwd(dy, dy_col, reserve, y, y_col, w_hh, dxproj, dhn, B, L, d, gates, reverse=False, n_dirs=1):
+    """Backpropagation through time of one layer: dy (B*L, lddy) from column dy_col, reserve / y (from column y_col) as `rnn_seq_train`
+    left them -> dxproj (B*L, >= n_dirs*gates*d), and for a GRU dhn (B*L, >= n_dirs*d), the hidden side's n block."""
+    _lib.call("amt_rnn_seq_bwd", _off(dy, dy_col), dy.shape[1], p(reserve), reserve.shape[1], _off(y, y_col), y.shape[1], p(w_hh),
+              p(dxproj), dxproj.shape[1], p(dhn), 0 if dhn is None else dhn.shape[1], B, L, d, gates, int(reverse), n_dirs, _st())
+    return dxproj, dhn
+
+
+REG_LOSS_WS_FLOATS = 516        # AMT_REG_LOSS_WS_FLOATS of include/amt_hip.h
+
+
+def reg_loss(ln_nd, inst, note_density, loudness, instrument):
+    """amt_reg_loss_fwd_bwd on ln_nd (rows, 2), inst (rows, 40) probabilities and the targets (rows) / (rows) / (rows, 40), all
+    contiguous fp32.  Returns loss (3,) = {total, SmoothL1 part, BCE part}, d_ln_nd (rows, 2), d_logit (rows, 40)."""
+    rows = ln_nd.shape[0]
+    assert ln_nd.shape == (rows, 2) and inst.shape == (rows, 40) and instrument.shape == (rows, 40)
+    assert note_density.numel() == rows and loudness.numel() == rows
+    for t in (ln_nd, inst, note_density, loudness, instrument):
+        assert t.dtype == torch.float32
+    loss = torch.empty(3, device=ln_nd.device, dtype=torch.float32)
+    d_ln_nd, d_logit = torch.empty_like(ln_nd), torch.empty_like(inst)
+    ws = torch.empty(REG_LOSS_WS_FLOATS, device=ln_nd.device, dtype=torch.float32)          # a call's own scratch (stream-ordered reuse)
+    _lib.call("amt_reg_loss_fwd_bwd", p(ln_nd), p(inst), p(note_density), p(loudness), p(instrument), rows, p(loss), p(d_ln_nd), p(d_logit),
+              p(ws), _st())
+    return loss, d_ln_nd, d_logit
+
+
 def selective_scan(xc, draw, dt_bias, A_log, dbc, R, D, xz, B, L, version=1, reverse=False):
     """Selective scan + gate.  xc, draw (B*L, ED); dbc (B*L, R+2N) = x_proj output (B at column R, C at R+N);
     xz (B*L, 2*ED) = in_proj output (gate branch z at column ED)."""
