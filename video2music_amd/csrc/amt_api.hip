@@ -97,6 +97,8 @@ struct amt_handle {
     float *pf_s = nullptr, *vs = nullptr, *lraw = nullptr;
     // layer-0 q/k/v as table sums: rows of (root, attr, key column, position) projected through layer 0's in-proj
     float *tab_r = nullptr, *tab_a = nullptr, *tab_k = nullptr, *tab_p = nullptr, *tab_cb = nullptr;
+    // their k / v columns again, sliced by head (pure copies, rebuilt with them): tab_p0 [H][Tcap][k hd | v hd], tab_ra0 [H][n_root + 16][k hd | v hd]
+    float *tab_p0 = nullptr, *tab_ra0 = nullptr;
     int* pos = nullptr;
     float* unif = nullptr;               // [Tcap][maxB] uniforms of the device-side categorical draw (amt_generate_set_uniforms)
     int use_unif = 0;
@@ -111,6 +113,7 @@ struct amt_handle {
     bool fuse_head = true;               // amt_set_option("fuse_sampling_head"): inside a captured graph the head rides in the next step's first attention
     bool short_attn = true;              // amt_set_option("short_context_attn"): graphs whose every step fits one K/V batch use the short-context self-attention
     bool step_short = false;             // set by get_graph while it captures such a graph (eager steps keep the long kernels)
+    bool l0_tables = true;               // amt_set_option("layer0_kv_from_tables"): 0 = the attention that carries the sampling head streams layer 0's keys from the cache
     bool gemm_pipe = true;               // amt_set_option("gemm_tile_pipeline"): 0 = the skinny GEMMs of the decode step run the serial tile loop (DecodeGemmParams::serial_loop)
     bool plain_chain = false;            // amt_set_option("decode_chain_plain"), before the first amt_finalize: the 49-launch chain without folded LayerNorms
     bool gen_active = false;
@@ -234,6 +237,7 @@ SampleParams sample_params(amt_handle* h, float* logits_out, float* probs_out, i
         p.tab_r = h->tab_r; p.tab_a = h->tab_a; p.tab_k = h->tab_k; p.tab_p = h->tab_p;
         p.q0 = h->qb; p.kc0 = h->KVc; p.vc0 = h->KVc + h->kvc_part; p.H = h->H; p.hd = h->hd; p.cap = h->kv_rows;
         p.q_scale = 1.0f / sqrtf((float)h->hd);
+        p.tab_p0 = h->tab_p0; p.tab_ra0 = h->tab_ra0; p.tab_T = h->Tcap; p.n_root = h->n_root;
     }
     return p;
 }
@@ -287,6 +291,8 @@ int32_t enqueue_decoder_step_folded(amt_handle* h, hipStream_t s, int step, Step
         a.pos = l == 0 && fused_sp ? fused_sp->pos : pos_slot(h, step); a.Er = L.Er; a.er_len = h->Tcap; a.short_ctx = h->step_short;
         if (l == 0 && fused_sp) {
             a.k_new = Kc; a.v_new = Vc; a.new_kv = 1;      // q / k / v of the new position are summed from the projected tables in the kernel
+            // ... and, in the long graphs, the keys of the earlier positions too (shapes the kernel does not stage keep the cache stream)
+            a.l0_tables = h->l0_tables && !h->chord_embed && amt_attn_decode_tables_fit(hd, h->kv_rows, h->n_root + 16);
         } else if (l == 0) {
             a.q = h->qb;          // written, with this position's K/V rows, by the previous sampling head / embed_step (table sums)
         } else {
@@ -436,7 +442,7 @@ int32_t get_graph(amt_handle* h, int first_pos, int nsteps, float* logits_out, h
     // of keys, every self-attention of the graph is the short-context instantiation (a graph that straddles the limit keeps the long one)
     const bool short_ctx = h->short_attn && first_pos + nsteps <= amt_attn_decode_stride(h->hd);
     amt_handle::GraphKey key{h->genB, h->genT, h->genP, h->beam, h->mcN, h->mcC, h->encS, nsteps, h->skip_mask | (h->fuse_head ? 4 : 0), h->use_unif,
-                             short_ctx ? 1 : 0, first_pos & 1, h->gemm_pipe ? 1 : 0, 0, logits_out};
+                             short_ctx ? 1 : 0, first_pos & 1, h->gemm_pipe ? 1 : 0, h->l0_tables ? 1 : 0, logits_out};
     for (auto& g : h->graphs)
         if (memcmp(&g.key, &key, sizeof(key)) == 0) { *out = g.exec; return 0; }
     hipGraph_t graph;
@@ -648,6 +654,8 @@ extern "C" int32_t amt_finalize(amt_handle* h) {
             if ((rc = dev_alloc(h, &h->tab_k, (size_t)3 * d))) return rc;
             if ((rc = dev_alloc(h, &h->tab_cb, (size_t)3 * d))) return rc;
             if ((rc = dev_alloc(h, &h->tab_p, (size_t)h->Tcap * 3 * d))) return rc;
+            if ((rc = dev_alloc(h, &h->tab_p0, (size_t)h->Tcap * 2 * d))) return rc;
+            if ((rc = dev_alloc(h, &h->tab_ra0, (size_t)(h->n_root + 16) * 2 * d))) return rc;
         }
         if ((rc = dev_alloc(h, &h->keyb, mb))) return rc;
         if ((rc = dev_alloc(h, &h->pos, (size_t)4))) return rc;
@@ -703,6 +711,19 @@ extern "C" int32_t amt_finalize(amt_handle* h) {
         GemmParams gp = gemm_params(h->pe, (int)d, D0.sa_w, (int)d, h->tab_p, d3, h->Tcap, d3, (int)d, D0.sa_b);
         gp.rowadd = h->tab_cb; gp.rowadd_period = 1;
         if ((rc = amt_launch_gemm(gp, s))) return rc;
+        // the k / v columns of TP, TR and TA once more with the head outermost (the table-sourced layer-0 key stream of attn_decode_sample):
+        // head hh of dst [H][rows][k hd | v hd] takes columns d + hh*hd .. and 2d + hh*hd .. of src [rows][3d]; no arithmetic
+        auto head_slices = [&](const float* src, int rows, float* dst, int dst_rows, int row0) -> int32_t {
+            for (int hh = 0; hh < h->H; ++hh)
+                for (int part = 0; part < 2; ++part)
+                    AMT_HIP(hipMemcpy2DAsync(dst + ((size_t)hh * dst_rows + row0) * 2 * hd + (size_t)part * hd, (size_t)2 * hd * sizeof(float),
+                                             src + (size_t)(1 + part) * d + (size_t)hh * hd, (size_t)d3 * sizeof(float), (size_t)hd * sizeof(float),
+                                             rows, hipMemcpyDeviceToDevice, s));
+            return 0;
+        };
+        if ((rc = head_slices(h->tab_p, h->Tcap, h->tab_p0, h->Tcap, 0))) return rc;
+        if ((rc = head_slices(h->tab_r, h->n_root, h->tab_ra0, h->n_root + 16, 0))) return rc;
+        if ((rc = head_slices(h->tab_a, 16, h->tab_ra0, h->n_root + 16, h->n_root))) return rc;
         // output head folded through norm3 of the last layer and decoder.norm (see SampleParams::lraw)
         const DecLayer& DL = h->dec[h->nl - 1];
         if ((rc = amt_launch_scale_cols(Wout, dnw, h->tWs2, V, (int)d, s))) return rc;                 // Wout o gf
@@ -753,6 +774,10 @@ extern "C" int32_t amt_set_option(amt_handle* h, const char* name, int32_t value
     }
     if (strcmp(name, "gemm_tile_pipeline") == 0) {           // 0: the decode step's skinny GEMMs keep the serial tile loop (A/B and bit-identity tests); part of the graph key
         h->gemm_pipe = value != 0;
+        return 0;
+    }
+    if (strcmp(name, "layer0_kv_from_tables") == 0) {        // 0: layer 0's self-attention always streams its keys from the K/V cache (A/B and bit-identity tests); part of the graph key
+        h->l0_tables = value != 0;
         return 0;
     }
     if (strcmp(name, "profile_skip") == 0) {                 // measurement hook of bench.py: leave a kernel class out of the captured step

@@ -35,13 +35,14 @@ __device__ __forceinline__ float4 ld4_stream(const float* p, bool nt) {
 
 // kb / vb / eb are wave-uniform bases (SGPR pairs); the lane part is a 32-bit element offset, so a load is
 // `global_load_dwordx4 v, v_off, s[base]` with one address VGPR and no 64-bit lane arithmetic
-template <int HD, bool NT>
+// (RS = floats between two rows: HD in the cache, 2 * HD in the head-sliced position table, whose rows are [k | v])
+template <int HD, bool NT, int RS = HD>
 __device__ __forceinline__ void load_kv(Batch<HD>& bt, const float* kb, const float* vb, int j0, int sub, int c4, int n_keys) {
     constexpr int KPW = 64 / (HD / 4);
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
         const int j = j0 + u * NW * KPW + sub;
-        const unsigned off = (unsigned)((j < n_keys ? j : 0) * HD + c4);
+        const unsigned off = (unsigned)((j < n_keys ? j : 0) * RS + c4);
         bt.k[u] = ld4_stream(kb + off, NT);
         bt.v[u] = ld4_stream(vb + off, NT);
     }
@@ -55,20 +56,55 @@ __device__ __forceinline__ void load_er(Batch<HD>& bt, const float* eb, int j0, 
         bt.e[u] = ld4(eb + (unsigned)((j < n_keys ? j : 0) * HD + c4));
     }
 }
-template <int HD, bool RPR, bool NT>
+template <int HD, bool RPR, bool NT, int RS = HD>
 __device__ __forceinline__ void load_batch(Batch<HD>& bt, const float* kb, const float* vb, const float* eb,
                                            int j0, int sub, int c4, int n_keys) {
-    load_kv<HD, NT>(bt, kb, vb, j0, sub, c4, n_keys);
+    load_kv<HD, NT, RS>(bt, kb, vb, j0, sub, c4, n_keys);
     if (RPR) load_er<HD>(bt, eb, j0, sub, c4, n_keys);
 }
 
-template <int HD, bool RPR>
+// TAB (layer 0 behind the sampling head, long graphs): the batch holds rows of the position table TP, shared by every clip of the head;
+// the key / value of position j is the table sum the cache row holds, re-formed from the head's TR / TA rows in LDS (picked by the
+// clip's ids of position j, staged as bytes) and the key column in registers
+struct TabCtx {
+    const float* rows;           // LDS: [TR rows | TA rows][k hd | v hd] of this head
+    const uchar2* ids;           // LDS: (root, n_root + attr) of positions 0 .. t-1 of this clip
+    float kv; float4 tkk, tkv;   // the clip's key scalar, the lane's four k / v columns of tk
+    int c4;
+};
+
+template <int HD, bool RPR, bool TAB = false>
 __device__ __forceinline__ void consume_batch(const Batch<HD>& bt, const float4 q4, int j0, int sub, int n_keys,
-                                              float& m, float& l, float4& o) {
+                                              float& m, float& l, float4& o, const TabCtx& tc = TabCtx{}) {
     constexpr int LPK = HD / 4, KPW = 64 / LPK;
+    float4 tk4[TAB ? UNROLL : 1], tv4[TAB ? UNROLL : 1];
+    if constexpr (TAB) {
+        // the whole batch's ids, then its sixteen table rows, then the sums, in front of the softmax chain: read key by key inside it,
+        // every key pays three serial LDS round trips (id, k rows, v rows under the key's guard)
+        uchar2 id[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const int j = j0 + u * NW * KPW + sub;
+            id[u] = tc.ids[j < n_keys ? j : 0];
+        }
+        float4 rk[UNROLL], ak[UNROLL], rv[UNROLL], av[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const float* r = tc.rows + (int)id[u].x * 2 * HD + tc.c4;
+            const float* a = tc.rows + (int)id[u].y * 2 * HD + tc.c4;
+            rk[u] = ld4(r); ak[u] = ld4(a); rv[u] = ld4(r + HD); av[u] = ld4(a + HD);
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            tk4[u] = table_sum4(rk[u], ak[u], tc.kv, tc.tkk, bt.k[u]);
+            tv4[u] = table_sum4(rv[u], av[u], tc.kv, tc.tkv, bt.v[u]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
-        float4 k4 = bt.k[u];
+        float4 k4 = bt.k[u], v4 = make_float4(0.f, 0.f, 0.f, 0.f);      // (v4: TAB only)
+        if constexpr (TAB) { k4 = tk4[u]; v4 = tv4[u]; }
         if (RPR) { k4.x += bt.e[u].x; k4.y += bt.e[u].y; k4.z += bt.e[u].z; k4.w += bt.e[u].w; }
         float s = q4.x * k4.x + q4.y * k4.y + q4.z * k4.z + q4.w * k4.w;
         s = group_sum<LPK>(s);
@@ -76,8 +112,13 @@ __device__ __forceinline__ void consume_batch(const Batch<HD>& bt, const float4 
             const float mn = fmaxf(m, s);
             const float alpha = __expf(m - mn), pj = __expf(s - mn);
             l = l * alpha + pj;
-            o.x = o.x * alpha + pj * bt.v[u].x; o.y = o.y * alpha + pj * bt.v[u].y;
-            o.z = o.z * alpha + pj * bt.v[u].z; o.w = o.w * alpha + pj * bt.v[u].w;
+            if constexpr (TAB) {
+                o.x = o.x * alpha + pj * v4.x; o.y = o.y * alpha + pj * v4.y;
+                o.z = o.z * alpha + pj * v4.z; o.w = o.w * alpha + pj * v4.w;
+            } else {
+                o.x = o.x * alpha + pj * bt.v[u].x; o.y = o.y * alpha + pj * bt.v[u].y;
+                o.z = o.z * alpha + pj * bt.v[u].z; o.w = o.w * alpha + pj * bt.v[u].w;
+            }
             m = mn;
         }
     }
@@ -88,22 +129,29 @@ __device__ __forceinline__ void consume_batch(const Batch<HD>& bt, const float4 
 // hides the number of outstanding loads from the compiler, which then waits for *all* of them (vmcnt(0)) before the batch
 // in hand is consumed, i.e. the double buffer degenerates to one batch in flight per wave.  The scheduling fence keeps the
 // consumer's first instruction (which needs a wait) from being hoisted in front of the next batch's load instructions.
-template <int HD, bool RPR, bool NT>
+template <int HD, bool RPR, bool NT, bool TAB = false>
 __device__ __forceinline__ void stream_keys(Batch<HD>& cur, Batch<HD>& nxt, const float* kb, const float* vb, const float* eb,
-                                            const float4 q4, int j0, int sub, int c4, int n_keys, float& m, float& l, float4& o) {
-    constexpr int STRIDE = NW * (64 / (HD / 4)) * UNROLL;
+                                            const float4 q4, int j0, int sub, int c4, int n_keys, float& m, float& l, float4& o,
+                                            const TabCtx& tc = TabCtx{}) {
+    constexpr int STRIDE = NW * (64 / (HD / 4)) * UNROLL, RS = TAB ? 2 * HD : HD;
     while (j0 < n_keys) {
-        load_batch<HD, RPR, NT>(nxt, kb, vb, eb, j0 + STRIDE, sub, c4, n_keys);
+        load_batch<HD, RPR, NT, RS>(nxt, kb, vb, eb, j0 + STRIDE, sub, c4, n_keys);
         __builtin_amdgcn_sched_barrier(0);
-        consume_batch<HD, RPR>(cur, q4, j0, sub, n_keys, m, l, o);
+        consume_batch<HD, RPR, TAB>(cur, q4, j0, sub, n_keys, m, l, o, tc);
         j0 += STRIDE;
         if (j0 >= n_keys) break;
-        load_batch<HD, RPR, NT>(cur, kb, vb, eb, j0 + STRIDE, sub, c4, n_keys);
+        load_batch<HD, RPR, NT, RS>(cur, kb, vb, eb, j0 + STRIDE, sub, c4, n_keys);
         __builtin_amdgcn_sched_barrier(0);
-        consume_batch<HD, RPR>(nxt, q4, j0, sub, n_keys, m, l, o);
+        consume_batch<HD, RPR, TAB>(nxt, q4, j0, sub, n_keys, m, l, o, tc);
         j0 += STRIDE;
     }
 }
+
+// table-sourced layer-0 stream: the seven waves that do not take the decision stage the head's TR / TA rows and the clip's ids
+constexpr int STAGE_T = (NW - 1) * 64;    // staging threads
+constexpr int TAB_ROWS_MAX = 32;          // TR and TA rows together (15 roots + 16 attributes in the base model)
+constexpr int TAB_ID_IT = 3;              // id loads per staging thread: positions up to TAB_ID_IT * STAGE_T = 1344
+__host__ __device__ constexpr int tab_ra_it(int hd) { return (TAB_ROWS_MAX * 2 * hd / 4 + STAGE_T - 1) / STAGE_T; }
 
 constexpr int UCH_MAX = 4;       // folded prologue: the pre-LN row has at most UCH*256 floats (UCH = 2 or 4 by the model's width)
 
@@ -125,9 +173,14 @@ constexpr int UCH_MAX = 4;       // folded prologue: the pre-LN row has at most 
 // row 0 from cache instead of streaming cap rows nobody consumes) and no second batch is requested, so nothing waits for a dead HBM
 // round trip.  Wave -> key mapping, consumption order and both merges are those of the long path: the output is bit-identical.  At
 // more than STRIDE keys it is still correct (further batches follow one at a time).
-template <int HD, bool RPR, bool NT, int FOLD, int UCH, bool SHORT = false>
+// TAB (FOLD 5, long): the cached keys 0 .. t-1 come from the head-sliced tables instead of the cache (TabCtx above).  A template flag,
+// not a run-time branch: one guarded load in the stream turns the later waits into vmcnt(0).  The per-clip HBM stream becomes one
+// [t][2 hd] run per head that the 32 clips of the head share in L2.  Row t of the cache is still written: the graph's first step, the
+// short graphs, the eager path and amt_kv_cache_io keep reading the cache.
+template <int HD, bool RPR, bool NT, int FOLD, int UCH, bool SHORT = false, bool TAB = false>
 __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, const SampleParams* sp) {
     static_assert(!SHORT || (RPR && (FOLD == 0 || FOLD == 2 || FOLD == 5)), "the short-context order exists for the base model's self-attention");
+    static_assert(!TAB || (FOLD == 5 && RPR && !SHORT && !NT), "the table-sourced stream exists for the long layer-0 launch behind the sampling head");
 #ifdef AMT_STAMPS
     unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -142,8 +195,14 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = lane % LPK, sub = lane / LPK;
     const int c4 = c * 4;
-    const float* kb = p.k + ((size_t)b * p.H + h) * p.cap * HD;      // wave-uniform
-    const float* vb = p.v + ((size_t)b * p.H + h) * p.cap * HD;
+    constexpr int RS = TAB ? 2 * HD : HD;
+    const float* kb = TAB ? sp->tab_p0 + (size_t)h * sp->tab_T * RS : p.k + ((size_t)b * p.H + h) * p.cap * HD;      // wave-uniform
+    const float* vb = TAB ? kb + HD : p.v + ((size_t)b * p.H + h) * p.cap * HD;
+    extern __shared__ __attribute__((aligned(16))) float tab_lds[];     // TAB: [ra_rows][2 hd] floats, then cap uchar2
+    constexpr int RA_IT = TAB ? tab_ra_it(HD) : 1;
+    float4 ra4[RA_IT];
+    long long ri[TAB_ID_IT], ai[TAB_ID_IT];
+    TabCtx tc{};
 
     // wave w takes key groups w, w+NW, ...; two batches are kept in flight (load i+1 before using i).
     // The first K/V batch and q do not depend on the step position: they are issued before `pos` is
@@ -190,9 +249,24 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
                 attr = (int)q.attrs[(size_t)b * q.T + (live ? t : 0)];
             }
             if (lane == 0) { s_ra[0] = root; s_ra[1] = attr; }
+        } else if constexpr (TAB) {
+            // meanwhile the other waves request what the stream adds to the shared rows: this head's TR / TA slice and the clip's ids
+            // of positions 0 .. t-1, in front of their K/V batches (small L2 loads; clamped, never guarded) -- in LDS at the barrier
+            // that publishes the decision
+            const int st = threadIdx.x - 64, n4 = (sp->n_root + 16) * (RS / 4);
+            const float* ra = sp->tab_ra0 + (size_t)h * n4 * 4;
+#pragma unroll
+            for (int i = 0; i < RA_IT; ++i) ra4[i] = ld4(ra + (unsigned)(min(i * STAGE_T + st, n4 - 1) * 4));
+#pragma unroll
+            for (int i = 0; i < TAB_ID_IT; ++i) {
+                const int j = i * STAGE_T + st;
+                ri[i] = sp->roots[(size_t)b * sp->T + (j < n_keys ? j : 0)];
+                ai[i] = sp->attrs[(size_t)b * sp->T + (j < n_keys ? j : 0)];
+            }
         }
     }
-    if (!F1 && !SHORT) load_kv<HD, NT>(b0, kb, vb, j0, sub, c4, p.cap);
+    // (TAB clamps the first batch to the length: the position table has tab_T >= T rows, not the cache's cap)
+    if (!F1 && !SHORT) load_kv<HD, NT, RS>(b0, kb, vb, j0, sub, c4, TAB ? n_keys : p.cap);
     if (!FOLD) {
         q4 = ld4(p.q + ((size_t)b * p.H + h) * HD + c * 4);
         if (SHORT) load_kv<HD, NT>(b0, kb, vb, j0, sub, c4, n_keys);
@@ -203,8 +277,22 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
         // (SHORT: the one batch there is, clamped to the length, and nothing behind it in front of the table rows)
         if (SHORT) load_kv<HD, NT>(b0, kb, vb, j0, sub, c4, n_keys);
         if (RPR) load_er<HD>(b0, eb, j0, sub, c4, n_keys);
-        if (!SHORT) load_batch<HD, RPR, NT>(b1, kb, vb, eb, j0 + STRIDE, sub, c4, n_keys);
+        if (!SHORT) load_batch<HD, RPR, NT, RS>(b1, kb, vb, eb, j0 + STRIDE, sub, c4, n_keys);
         const SampleParams& q = *sp;
+        if constexpr (TAB) {
+            if (wave != 0) {
+                const int st = threadIdx.x - 64, n4 = (q.n_root + 16) * (RS / 4);
+                uchar2* ids = reinterpret_cast<uchar2*>(tab_lds + n4 * 4);
+#pragma unroll
+                for (int i = 0; i < RA_IT; ++i)
+                    if (i * STAGE_T + st < n4) st4(tab_lds + (i * STAGE_T + st) * 4, ra4[i]);
+#pragma unroll
+                for (int i = 0; i < TAB_ID_IT; ++i) {
+                    const int j = i * STAGE_T + st;
+                    if (j < n_keys) ids[j] = make_uchar2((unsigned char)ri[i], (unsigned char)(q.n_root + (int)ai[i]));
+                }
+            }
+        }
         __syncthreads();
         const int root = s_ra[0], attr = s_ra[1];
         // this head's q / k / v of position t: the decoder input is a sum of table rows, so its projection is one too (the
@@ -220,12 +308,14 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
         const float4 r2 = ld4(tr + 2 * d), a2 = ld4(ta + 2 * d), k2 = ld4(tk + 2 * d), p2 = ld4(tp + 2 * d);
         if (own_er) e_own = ld4(p.Er + (size_t)(p.er_len - 1) * HD + c4);
         __builtin_amdgcn_sched_barrier(0);
-        q4.x = (((r0.x + a0.x) + kv * k0.x) + p0.x) * q.q_scale; q4.y = (((r0.y + a0.y) + kv * k0.y) + p0.y) * q.q_scale;
-        q4.z = (((r0.z + a0.z) + kv * k0.z) + p0.z) * q.q_scale; q4.w = (((r0.w + a0.w) + kv * k0.w) + p0.w) * q.q_scale;
-        kn4.x = ((r1.x + a1.x) + kv * k1.x) + p1.x; kn4.y = ((r1.y + a1.y) + kv * k1.y) + p1.y;
-        kn4.z = ((r1.z + a1.z) + kv * k1.z) + p1.z; kn4.w = ((r1.w + a1.w) + kv * k1.w) + p1.w;
-        vn4.x = ((r2.x + a2.x) + kv * k2.x) + p2.x; vn4.y = ((r2.y + a2.y) + kv * k2.y) + p2.y;
-        vn4.z = ((r2.z + a2.z) + kv * k2.z) + p2.z; vn4.w = ((r2.w + a2.w) + kv * k2.w) + p2.w;
+        q4 = table_sum4(r0, a0, kv, k0, p0);
+        q4.x *= q.q_scale; q4.y *= q.q_scale; q4.z *= q.q_scale; q4.w *= q.q_scale;
+        kn4 = table_sum4(r1, a1, kv, k1, p1);
+        vn4 = table_sum4(r2, a2, kv, k2, p2);
+        if constexpr (TAB) {
+            tc.rows = tab_lds; tc.ids = reinterpret_cast<const uchar2*>(tab_lds + (q.n_root + 16) * RS);
+            tc.kv = kv; tc.tkk = k1; tc.tkv = k2; tc.c4 = c4;
+        }
         if (h == 0 && live) {                         // the next input row x[t] (the residual stream layer 0 starts from)
             for (int cc = threadIdx.x * 4; cc < d; cc += NW * 64 * 4) {
                 const float4 pr = ld4(q.PR + (size_t)root * d + cc), pa = ld4(q.PA + (size_t)attr * d + cc);
@@ -348,9 +438,9 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
         }
     } else if constexpr (FOLD == 5) {
         // both batches are in flight since the prologue
-        consume_batch<HD, RPR>(b0, q4, j0, sub, n_keys, m, l, o);
+        consume_batch<HD, RPR, TAB>(b0, q4, j0, sub, n_keys, m, l, o, tc);
         j0 += STRIDE;
-        stream_keys<HD, RPR, NT>(b1, b0, kb, vb, eb, q4, j0, sub, c4, n_keys, m, l, o);
+        stream_keys<HD, RPR, NT, TAB>(b1, b0, kb, vb, eb, q4, j0, sub, c4, n_keys, m, l, o, tc);
     } else if (!RPR) {
         // cross-attention (fixed key count, always several batches): the first half-iteration is peeled, which keeps the
         // wait counts of the loop exact on both halves (measured 7.0 -> 6.8 us); for the self-attention the extra
@@ -450,9 +540,9 @@ void attn_decode_kernel(AttnDecodeParams p) {
 // layer 0 of the base model's folded chain with the previous step's decision in front (FOLD 5).  No 128-VGPR bound here: with the
 // first K/V batch in flight the decision and the twelve table rows need more (the bound spilled 36 registers); at 32 clips the launch is
 // one workgroup per CU either way, above that this ONE launch of the step's six self-attentions takes two rounds
-template <int HD, bool RPR, bool NT, int UCH, bool SHORT = false>
+template <int HD, bool RPR, bool NT, int UCH, bool SHORT = false, bool TAB = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_sample_kernel(AttnDecodeParams p, SampleParams sp) {
-    attn_decode_body<HD, RPR, NT, 5, UCH, SHORT>(p, &sp);
+    attn_decode_body<HD, RPR, NT, 5, UCH, SHORT, TAB>(p, &sp);
 }
 
 template <int HD, int FOLD, int UCH>
@@ -493,7 +583,12 @@ void launch_decode_sample(const AttnDecodeParams& p, const SampleParams& sp, hip
     const bool nt = (amt_tuning().nt_mask & 1) != 0;
 #define AMT_LAUNCH_DS(RPR, NTV, UCHV) hipLaunchKernelGGL((attn_decode_sample_kernel<HD, RPR, NTV, UCHV>), grid, dim3(NW * 64), 0, stream, p, sp)
 #define AMT_LAUNCH_DSS(NTV, UCHV) hipLaunchKernelGGL((attn_decode_sample_kernel<HD, true, NTV, UCHV, true>), grid, dim3(NW * 64), 0, stream, p, sp)
-    if (p.Er && p.short_ctx) {
+    if (p.Er && p.l0_tables && !p.short_ctx) {
+        // shared table rows are meant to stay in L2: plain loads whatever nt_mask says.  LDS: the head's TR / TA rows, then the ids
+        const size_t lds = (size_t)(sp.n_root + 16) * 2 * HD * sizeof(float) + (size_t)p.cap * 2;
+        if (sp.d <= 512) hipLaunchKernelGGL((attn_decode_sample_kernel<HD, true, false, 2, false, true>), grid, dim3(NW * 64), lds, stream, p, sp);
+        else hipLaunchKernelGGL((attn_decode_sample_kernel<HD, true, false, 4, false, true>), grid, dim3(NW * 64), lds, stream, p, sp);
+    } else if (p.Er && p.short_ctx) {
         if (sp.d <= 512) { if (nt) AMT_LAUNCH_DSS(true, 2); else AMT_LAUNCH_DSS(false, 2); }
         else { if (nt) AMT_LAUNCH_DSS(true, 4); else AMT_LAUNCH_DSS(false, 4); }
     } else if (sp.d <= 512) {
@@ -512,6 +607,11 @@ void launch_decode_sample(const AttnDecodeParams& p, const SampleParams& sp, hip
 // keys one workgroup takes per batch: the limit below which a step qualifies for the short-context instantiations
 int amt_attn_decode_stride(int hd) { return NW * (64 / (hd / 4)) * UNROLL; }
 
+// the table-sourced layer-0 stream stages at most TAB_ROWS_MAX table rows and TAB_ID_IT * STAGE_T ids per workgroup (35 KB of LDS at most)
+bool amt_attn_decode_tables_fit(int hd, int cap, int ra_rows) {
+    return (hd == 16 || hd == 32 || hd == 64 || hd == 128) && ra_rows > 0 && ra_rows <= TAB_ROWS_MAX && cap > 0 && cap <= TAB_ID_IT * STAGE_T;
+}
+
 // The base model's layer-0 self-attention of a decode step with the previous step's sampling decision in its prologue (FOLD 5):
 // p as for the plain layer-0 launch (k / v the cache, pos the device position) plus k_new / v_new; sp as amt_launch_sample takes it
 // (folded head: lraw, h1..h4, projected tables).  *pos must hold the position the previous step processed; this step's goes to *pos_next.
@@ -522,6 +622,9 @@ int32_t amt_launch_attn_decode_sample(const AttnDecodeParams& p, const SamplePar
                   "attn_decode_sample: needs the folded head, the projected input tables and a device-side decision");
     AMT_CHECK_ARG(sp.B == p.B && sp.d == p.H * p.hd && sp.d % 4 == 0 && sp.d <= UCH_MAX * 256, "attn_decode_sample: shapes of the two halves differ");
     AMT_CHECK_ARG(p.Er == nullptr || p.er_len + 1 >= p.cap, "attn_decode_sample: er_len=%d smaller than the key capacity %d", p.er_len, p.cap);
+    AMT_CHECK_ARG(!p.l0_tables || (sp.tab_p0 && sp.tab_ra0 && !sp.chord_embed && sp.T <= sp.tab_T && sp.T <= p.cap &&
+                                   amt_attn_decode_tables_fit(p.hd, p.cap, sp.n_root + 16)),
+                  "attn_decode_sample: the table-sourced key stream needs the head-sliced tables and a shape it stages (cap=%d)", p.cap);
     switch (p.hd) {
         case 16: launch_decode_sample<16>(p, sp, stream); break;
         case 32: launch_decode_sample<32>(p, sp, stream); break;

@@ -97,9 +97,15 @@ struct AttnDecodeParams {
     // instantiation (prologue first, one K/V batch clamped to the length).  Same result at any length; faster only while the
     // length stays within amt_attn_decode_stride(hd) keys, which is when the caller sets it
     int short_ctx;
+    // attn_decode_sample only (the long launch): 1 = keys 0 .. t-1 of layer 0 are re-summed from the head-sliced projected tables
+    // (SampleParams::tab_p0 / tab_ra0 and the id sequences) instead of read back from the cache -- the same bits, see table_sum4;
+    // the caller sets it only where amt_attn_decode_tables_fit() holds
+    int l0_tables;
 };
 int32_t amt_launch_attn_decode(const AttnDecodeParams& p, hipStream_t stream);
 int amt_attn_decode_stride(int hd);
+// whether the table-sourced layer-0 key stream (AttnDecodeParams::l0_tables) takes this shape: ra_rows = rows of TR and TA together
+bool amt_attn_decode_tables_fit(int hd, int cap, int ra_rows);
 
 // ---------------- decode-step skinny GEMM (decode_gemm.hip) ----------------
 // packed weight: tiles of 16(n) x 16(k): P[((nt*(K/16)+kt)*64 + lane)*4 + e] = W[nt*16+(lane&15)][kt*16+4*(lane>>4)+e]
@@ -247,6 +253,10 @@ struct SampleParams {
     const float* tab_r; const float* tab_a; const float* tab_k; const float* tab_p;
     float* q0; float* kc0; float* vc0; int H, hd, cap; float q_scale;
     int chord_embed;                 // 1: the chosen chord id feeds back as the "root" index (table = chord embedding), attr = 0
+    // The k / v columns of those tables once more, sliced by head (built with them at weight load, pure copies): tab_p0
+    // [H][tab_T][k hd | v hd] and tab_ra0 [H][n_root + 16][k hd | v hd] (TR's rows, then TA's).  One head's position table is a
+    // contiguous run shared by every clip, which the layer-0 key stream of attn_decode_sample reads instead of per-clip cache rows
+    const float* tab_p0; const float* tab_ra0; int tab_T, n_root;
 };
 int32_t amt_launch_sample(const SampleParams& p, hipStream_t stream);
 // the base model's layer-0 self-attention with the previous step's sampling decision in its prologue (attn_decode.hip, FOLD 5)

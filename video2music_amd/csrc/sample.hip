@@ -37,9 +37,7 @@ __device__ __forceinline__ void write_next_input(const SampleParams& p, int b, i
         for (int c = threadIdx.x * 4; c < d3; c += blockDim.x * 4) {
             const float4 tr = ld4(p.tab_r + (size_t)root * d3 + c), ta = ld4(p.tab_a + (size_t)attr * d3 + c);
             const float4 tk = ld4(p.tab_k + c), tp = ld4(p.tab_p + (size_t)cur * d3 + c);
-            float4 o;
-            o.x = ((tr.x + ta.x) + kv * tk.x) + tp.x; o.y = ((tr.y + ta.y) + kv * tk.y) + tp.y;
-            o.z = ((tr.z + ta.z) + kv * tk.z) + tp.z; o.w = ((tr.w + ta.w) + kv * tk.w) + tp.w;
+            float4 o = table_sum4(tr, ta, kv, tk, tp);
             if (c < d) {
                 o.x *= p.q_scale; o.y *= p.q_scale; o.z *= p.q_scale; o.w *= p.q_scale;
                 st4(p.q0 + (size_t)b * d + c, o);

@@ -18,6 +18,18 @@ __device__ __forceinline__ void feedback_of(const SampleParams& p, int tok, int&
     else { root = ROOT_PAD; attr = ATTR_PAD; }
 }
 
+// Layer 0's q / k / v of one position: the decoder input is a sum of embedding-table rows, so its in-projection is the sum of the
+// projected rows, ((TR[root] + TA[attr]) + key * tk) + TP[pos].  The ONE spelling of that sum: the stand-alone head (write_next_input,
+// sample.hip) stores it into layer 0's cache, the attention that carries the head (attn_decode.hip, FOLD 5) forms its own position's
+// q / k / v with it and, sourcing the cached keys from the tables, every earlier position's k / v again -- those must be the bits the
+// cache holds, so nobody re-associates it (the library is built with -ffp-contract=off: a multiply and an add at every site).
+__device__ __forceinline__ float4 table_sum4(const float4 tr, const float4 ta, float kv, const float4 tk, const float4 tp) {
+    float4 o;
+    o.x = ((tr.x + ta.x) + kv * tk.x) + tp.x; o.y = ((tr.y + ta.y) + kv * tk.y) + tp.y;
+    o.z = ((tr.z + ta.z) + kv * tk.z) + tp.z; o.w = ((tr.w + ta.w) + kv * tk.w) + tp.w;
+    return o;
+}
+
 // The decision of one clip by one wave: pr[k] = (masked, un-normalised) probability of token lane + 64k, ps their sum.
 // Arg-max of pr / ps (ties -> lowest id), or, with uniforms, the inverse-CDF draw: the first token whose cumulative
 // probability reaches u * ps (tokens are ordered lane-major inside k = 0, 1, 2).
