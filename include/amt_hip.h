@@ -36,11 +36,13 @@
 #define AMT_HIP_H
 #include <stdint.h>
 
-#define AMT_ABI_VERSION 6    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
+#define AMT_ABI_VERSION 7    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
                                 3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights;
                                 4: amt_chord_metrics_fwd;
                                 5: amt_reg_metrics_fwd;
-                                6: amt_rnn_seq_train_fwd, amt_rnn_seq_bwd, amt_reg_loss_fwd_bwd */
+                                6: amt_rnn_seq_train_fwd, amt_rnn_seq_bwd, amt_reg_loss_fwd_bwd;
+                                7: amt_attn_train_fwd, amt_attn_bwd, amt_attn_bwd_ws_floats, amt_layernorm_bwd, amt_chord_loss_fwd_bwd,
+                                   amt_chord_loss_ws_floats */
 
 #ifdef __cplusplus
 extern "C" {
@@ -517,6 +519,73 @@ int32_t amt_reg_metrics_fwd(const float* feat, int32_t ld, int32_t W, const floa
 int32_t amt_reg_loss_fwd_bwd(const float* ln_nd, const float* inst, const float* note_density, const float* loudness,
                              const float* instrument, int32_t rows, float* loss, float* d_ln_nd, float* d_logit, float* ws,
                              void* stream);
+
+/* ---- training of the chord model (reference train.py, utilities/run_model_vevo.py:73-119) ---- */
+/* amt_attn_fwd that keeps what a backward needs.  Arguments as amt_attn_fwd, plus
+ *   Er (er_len, hd), null = no relative term; with Er the call must be causal with Lq == Lk <= er_len and kv_group 1 (as the backward);
+ *   keep (B, H, Lq, Lk) contiguous bytes, 1 = kept, null = no dropout; keep_scale = 1 / (1 - p);
+ *   lse (B, H, Lq): the row's log-sum-exp of the scores as the kernel forms them.
+ * With qs = q q_scale:  S_ij = qs_i . k_j (+ qs_i . Er[er_len-1-(i-j)] for j <= i),  P = softmax_j(S) under the mask,
+ * O = (P o keep keep_scale) V; the normaliser is that of the undropped P, as torch drops after the softmax (rpr.py:409-412).
+ * The TRAIN instantiations of the prefill kernels, chosen by shape exactly as the inference calls choose theirs: with keep null, O
+ * equals amt_rpr_attn_fwd / amt_cross_attn_fwd / amt_attn_fwd bit for bit.  Head dims 32, 64, 128 (16 is refused: the backward
+ * has no instantiation for it). */
+int32_t amt_attn_train_fwd(const float* q, const float* k, const float* v, float* o, const int64_t* strides,
+                           int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t causal, int32_t kv_group,
+                           float q_scale, const float* Er, int32_t er_len, const uint8_t* keep, float keep_scale, float* lse,
+                           void* stream);
+/* Backward of amt_attn_train_fwd: from dO (o's strides) and the forward's q, k, v, o, lse, Er, keep the gradients with respect to
+ * the tensors as passed: dq (q's strides; includes q_scale), dk, dv (k's / v's strides; with kv_group > 1 the sum over the group's
+ * query heads, in head order), dEr (er_len, hd) contiguous, optional.  With D_i = sum_d dO_id O_id:
+ *   dP = (dO V^T) o keep keep_scale,  dS = P o (dP - D_i),  dv = (P o keep keep_scale)^T dO,  dk = dS^T qs,
+ *   dqs = dS k (+ sum_j dS_ij Er[er_len-1-(i-j)]),  dEr[r] = sum over b, h and the pairs with i - j = er_len-1-r of dS_ij qs_i;
+ * rows of Er no pair reaches get exactly 0.  A row whose keep is all zero has O = 0 and finite (zero) gradients.
+ * Pass A, one workgroup per 128 queries, recomputes P tile by tile from lse in the forward's layout and forms dq; it leaves dS and
+ * P o keep keep_scale in two (B H, Lq, ceil32(Lk)) scratches from which pass B, one wave per 32 keys, forms dk and dv.  With Er the dS
+ * scratch is un-skewed (key j of query i in column L-1-(i-j)): dq's second term is one product of it with Er's last L rows on the
+ * library's GEMM, dEr one MFMA chain per (clip, head) into a slab each, the slabs added in (clip, head) order.  No atomics: the order
+ * of every addition is a function of the shapes alone.  With Er: kv_group 1.  Head dims 32, 64, 128.
+ * ws: amt_attn_bwd_ws_floats(B, H, Lq, Lk, hd, Er != null) floats of scratch, 16-byte aligned, this call's alone until it finishes
+ * (184 MB at 32 clips x 8 heads x 299 x 299, 226 MB with Er). */
+int64_t amt_attn_bwd_ws_floats(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t rpr);
+int32_t amt_attn_bwd(const float* dO, const float* q, const float* k, const float* v, const float* o, const float* lse,
+                     const float* Er, int32_t er_len, const uint8_t* keep, float keep_scale, float* dq, float* dk, float* dv,
+                     float* dEr, const int64_t* strides, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd,
+                     int32_t causal, int32_t kv_group, float q_scale, float* ws, void* stream);
+
+/* Backward of y = LayerNorm(x (+ resid)) * w + b (amt_layernorm_fwd; torch.nn.LayerNorm).  dy, x, resid (null = none), dx: (rows, dim);
+ * w, dw, db: (dim).  x / resid are the forward's inputs: the row statistics are formed again from them as the forward formed them.
+ *   dx = rstd (g - mean(g) - xh mean(g xh)),  g = dy w,  xh = (x (+ resid) - mean) rstd      (the gradient of x and of resid alike)
+ *   dw = sum over rows of dy xh,   db = sum over rows of dy
+ * dim a multiple of 4, at most 1024; any rows > 0.  ws: AMT_LAYERNORM_BWD_WS_FLOATS(dim) floats of scratch, 16-byte aligned, used by
+ * this call alone until it has finished (a ticket counter, zeroed by the call, and one [dw | db] slab per workgroup).
+ * min(128, ceil(rows / 16)) workgroups of 4 waves, one wave per row; a workgroup adds its rows per wave in row order, its waves in
+ * wave order, and the last workgroup to finish adds the slabs in workgroup order: the order of every addition is a function of
+ * (rows, dim) alone and no floating-point atomic is used, so the same inputs give the same bits. */
+#define AMT_LAYERNORM_BWD_WS_FLOATS(dim) (4 + 256 * (dim))
+int32_t amt_layernorm_bwd(const float* dy, const float* x, const float* resid, const float* w, float* dx, float* dw, float* db,
+                          float* ws, int32_t rows, int32_t dim, float eps, void* stream);
+
+/* Training loss of the chord model (reference utilities/run_model_vevo.py:101-119) and its gradient, one launch:
+ *   total = lambda CrossEntropyLoss(ignore_index=CHORD_PAD, label_smoothing=smoothing)(y, tgt)
+ *           + (1 - lambda) BCEWithLogitsLoss()(y, tgt_emotion)
+ * logits, ld, tgt, emo_class: as amt_chord_metrics_fwd takes them, and the emotion row t of a target is built exactly as that call
+ * documents (an id outside 0..158 is ignored like CHORD_PAD; an emo_class outside 0..4 accepts no quality).  Per row, with p the
+ * softmax of the row and eps = smoothing (0 = none):
+ *   ce  = (1 - eps) (logsumexp(y) - y[tgt]) + eps (-sum_c log p_c) / 159        (valid rows: tgt != CHORD_PAD)
+ *   bce = sum over the 159 classes of max(y,0) - y t + log1p(exp(-|y|))         (all rows)
+ * loss[3] = {total, chord, emotion}: chord = sum_b clip ce / sum_b n_valid, emotion = sum bce / (159 B L), total = lambda chord +
+ * (1 - lambda) emotion.  A batch without a valid target gives chord = NaN, as torch does.
+ * clip_out (B, 4) = {n_valid, sum of ce over the clip's valid rows, sum of bce over its L rows, L}.
+ * dlogits (B L, 159) contiguous, optional (null = forward only; loss and clip_out are the same bits either way):
+ *   lambda (p - (1 - eps) onehot(tgt) - eps / 159) valid / n_valid_total + (1 - lambda) (sigmoid(y) - t) / (159 B L)
+ * ws: amt_chord_loss_ws_floats(B, L) floats of scratch, 16-byte aligned, used by this call alone until it has finished (a ticket
+ * counter, zeroed by the call, and three sums per workgroup).  B ceil(L / 64) workgroups of 16 waves, one wave per row: a wave tree
+ * inside a row, the rows of a workgroup added in row order, the workgroups of a clip in order, the clips in order; no floating-point
+ * atomic, so the same inputs give the same bits.  159 B L <= 2^24. */
+int64_t amt_chord_loss_ws_floats(int32_t B, int32_t L);
+int32_t amt_chord_loss_fwd_bwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, int32_t B, int32_t L,
+                               float lambda, float smoothing, float* loss, float* clip_out, float* dlogits, float* ws, void* stream);
 
 #ifdef __cplusplus
 }

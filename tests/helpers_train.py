@@ -1,0 +1,185 @@
+"""Chord-model training test infrastructure: the fixture's two small models and one batch, and a torch restatement of the training
+forward of `VideoMusicTransformer` (reference model/video_music_transformer.py:978-1044, model/rpr.py:37-69, :387-455 with the skew
+written out, torch's post-norm ReLU encoder layer) that runs on the CPU in fp64 or fp32 and takes injected dropout masks.  Nothing
+under video2music_amd/ imports it."""
+import functools
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from tests import helpers_eval as HE
+from tests.helpers import amt_named_shapes
+from video2music_amd import synthetic
+from video2music_amd.utilities import constants as C
+
+U = 2.0 ** -24
+LAM = 0.4                                  # the reference's LAMBDA weighting of the chord part is a flag; the fixture uses this one
+SMOOTHING = 0.1
+S_VIDEO, L_CHORD, B_CLIPS = 300, 299, 2     # the reference's train_epoch pairs the logits with 299 emotion rows: no shorter sequence runs
+CFG = dict(n_layers=2, num_heads=2, d_model=64, dim_feedforward=128, max_sequence_chord=300, max_sequence_video=300,
+           total_vf_dim=24 + 1 + 1 + 6)     # the miniature dataset's 24 semantic features, scene offset, scalar motion, 6 emotions
+MODELS = {"rpr": dict(CFG, rpr=True), "plain": dict(CFG, rpr=False)}
+UNUSED = ("embedding.weight", "condition_linear.weight", "condition_linear.bias", "Wout_root.weight", "Wout_root.bias",
+          "Wout_attr.weight", "Wout_attr.bias")
+SGD_LR, SGD_STEPS = 0.05, 3
+ADAM_LR, ADAM_STEPS = 1e-3, 3
+LOGIT_ROWS = (0, 1, 38, 39, 40, 298)         # the logits rows g_train.npz records: the first, around END of "003", the last
+FIGURES = ("avg_total_loss", "avg_loss_chord", "avg_loss_emotion", "avg_h1", "avg_h3", "avg_h5")
+# the keys whose fp64 gradient g_train_rpr64.npz records in full: Er, one whole decoder layer, one encoder layer, Linear_chord, both
+# embeddings, Wout (everything else fp64 is recorded where it has at most 5000 values)
+FULL64 = ("transformer.decoder.layers.0.self_attn.Er", "transformer.decoder.layers.1.", "transformer.encoder.layers.0.", "Linear_chord.",
+          "embedding_root.weight", "embedding_attr.weight", "Wout.weight", "Wout.bias")
+
+
+def named_shapes(cfg):
+    shapes = amt_named_shapes(**cfg)
+    return [(k, s) for k, s in shapes if cfg["rpr"] or not k.endswith(".Er")]
+
+
+def state_dict(cfg, seed=0):
+    return synthetic.synthetic_state_dict(named_shapes(cfg), seed=seed)
+
+
+def write_dataset(root):
+    """The miniature dataset of tests/helpers_eval.py as files under `root`; returns its clip ids."""
+    from tests.helpers_features import write_mini_dataset
+    content = HE.eval_dataset_content()
+    write_mini_dataset(root, content, with_targets=True)
+    return list(content["ids"])
+
+
+@functools.lru_cache(maxsize=None)
+def batch():
+    """Both clips of the miniature dataset as the project's reader returns them (motion_type 0, 300 seconds, 299 chord positions:
+    "003" ends in END and PAD, "017" is cut), in the restatement's names.  Numpy arrays; treat them as read-only."""
+    import tempfile
+    from video2music_amd.dataset import vevo_features as VF
+    with tempfile.TemporaryDirectory(prefix="vevo_train_") as root:
+        f = VF.load_clips(root, write_dataset(root), motion_type=0, max_seq_video=S_VIDEO, max_seq_chord=S_VIDEO)
+    return {"x": f["chord"][:, :L_CHORD], "x_root": f["chord_root"][:, :L_CHORD], "x_attr": f["chord_attr"][:, :L_CHORD], "tgt": f["tgt"],
+            "emo_class": f["emo_class"], "emo_prob": f["emo_prob"], "semantic": f["semantic"], "scene_offset": f["scene_offset"],
+            "motion": f["motion"].reshape(B_CLIPS, S_VIDEO), "emotion": f["emotion"], "key": f["key"]}
+
+
+def skew(qe):
+    """model/rpr.py:439-455 written out: qe (N, L, L) -> srel[n][i][j] = qe[n][i][L-1-(i-j)] for j <= i, 0 above the diagonal."""
+    L = qe.shape[1]
+    i, j = torch.arange(L, device=qe.device)[:, None], torch.arange(L, device=qe.device)[None, :]
+    idx = (L - 1 - (i - j)).clamp(0, L - 1)
+    return torch.where(j <= i, torch.gather(qe, 2, idx.expand(qe.shape[0], L, L)), torch.zeros((), dtype=qe.dtype, device=qe.device))
+
+
+def mha(P, pre, xq, xkv, H, causal, masks):
+    """torch's / rpr.py's multi-head attention on (B, L, d) tensors; P[pre + 'Er'] adds the relative term."""
+    B, Lq, d = xq.shape
+    Lk, hd = xkv.shape[1], d // H
+    W, b = P[pre + "in_proj_weight"], P[pre + "in_proj_bias"]
+    q = F.linear(xq, W[:d], b[:d]) * hd ** -0.5
+    k, v = F.linear(xkv, W[d:2 * d], b[d:2 * d]), F.linear(xkv, W[2 * d:], b[2 * d:])
+    q, k, v = (t.view(B, -1, H, hd).transpose(1, 2) for t in (q, k, v))
+    S = q @ k.transpose(2, 3)
+    if pre + "Er" in P:
+        Er = P[pre + "Er"]
+        Er = Er[max(0, Er.shape[0] - Lq):]
+        S = S + skew((q @ Er.t()).reshape(B * H, Lq, Lq)).view(B, H, Lq, Lq)
+    if causal:
+        S = S + torch.triu(torch.full((Lq, Lk), float("-inf"), dtype=S.dtype, device=S.device), diagonal=1)
+    A = torch.softmax(S, dim=-1)
+    if masks is not None:
+        A = A * masks.pop(0).to(A.device, A.dtype) / (1.0 - masks.p)
+    o = (A @ v).transpose(1, 2).reshape(B, Lq, d)
+    return F.linear(o, P[pre + "out_proj.weight"], P[pre + "out_proj.bias"])
+
+
+class Masks(list):
+    """The dropout masks in use order with their rate: element-wise ones are float multipliers, attention ones uint8 keeps."""
+    def __init__(self, items, p):
+        super().__init__(torch.as_tensor(np.asarray(m)) for m in items)
+        self.p = p
+
+
+def forward(P, cfg, bt, masks=None, causal=True):
+    """Logits (B, L, 159) from parameters P {key: tensor} (any float dtype and device; they may require grad) and a `batch`."""
+    dt, dev = P["Wout.weight"].dtype, P["Wout.weight"].device
+    H = cfg["num_heads"]
+    t = lambda a: torch.as_tensor(np.asarray(a)).to(dev, dt)
+
+    def drop(x):
+        return x if masks is None else x * masks.pop(0).to(dev, dt).view(x.shape)
+
+    def ln(pre, x):
+        return F.layer_norm(x, (x.shape[-1],), P[pre + ".weight"], P[pre + ".bias"], 1e-5)
+
+    def pe(n, d):
+        pos = torch.arange(n, dtype=torch.float32)[:, None]
+        div = torch.exp(torch.arange(0, d, 2).float() * (-np.log(10000.0) / d))
+        out = torch.zeros(n, d)
+        out[:, 0::2], out[:, 1::2] = torch.sin(pos * div), torch.cos(pos * div)
+        return out.to(dev, dt)                                 # the fp32 table of the module's buffer, as every path reads it
+
+    B, L = bt["x_root"].shape
+    d = cfg["d_model"]
+    x = P["embedding_root.weight"][torch.as_tensor(bt["x_root"]).to(dev)] + P["embedding_attr.weight"][torch.as_tensor(bt["x_attr"]).to(dev)]
+    x = torch.cat([x, t(bt["key"]).view(B, 1, 1).expand(B, L, 1)], dim=-1)
+    xf = F.linear(x, P["Linear_chord.weight"], P["Linear_chord.bias"])
+    vfc = bt["_vfc"] if "_vfc" in bt else torch.cat([t(bt["semantic"]), t(bt["scene_offset"]).unsqueeze(-1), t(bt["motion"]).unsqueeze(-1),
+                                                     t(bt["emotion"])], dim=-1)          # _vfc: feature rows a caller has concatenated
+    vf = F.linear(vfc, P["Linear_vis.weight"], P["Linear_vis.bias"])
+    vf = drop(vf + pe(vf.shape[1], d))
+    xf = drop(xf + pe(L, d))
+    mem = vf
+    for i in range(cfg["n_layers"]):
+        pre = f"transformer.encoder.layers.{i}."
+        mem = ln(pre + "norm1", mem + drop(mha(P, pre + "self_attn.", mem, mem, H, False, masks)))
+        h = drop(torch.relu(F.linear(mem, P[pre + "linear1.weight"], P[pre + "linear1.bias"])))
+        mem = ln(pre + "norm2", mem + drop(F.linear(h, P[pre + "linear2.weight"], P[pre + "linear2.bias"])))
+    mem = ln("transformer.encoder.norm", mem)
+    y = xf
+    for i in range(cfg["n_layers"]):
+        pre = f"transformer.decoder.layers.{i}."
+        y = ln(pre + "norm1", y + drop(mha(P, pre + "self_attn.", y, y, H, causal, masks)))
+        y = ln(pre + "norm2", y + drop(mha(P, pre + "multihead_attn.", y, mem, H, False, masks)))
+        h = drop(torch.relu(F.linear(y, P[pre + "linear1.weight"], P[pre + "linear1.bias"])))
+        y = ln(pre + "norm3", y + drop(F.linear(h, P[pre + "linear2.weight"], P[pre + "linear2.bias"])))
+    y = ln("transformer.decoder.norm", y)
+    assert masks is None or not masks
+    return F.linear(y, P["Wout.weight"], P["Wout.bias"])
+
+
+def loss(logits, bt, smoothing=SMOOTHING, lam=LAM):
+    """The two loss expressions of train_epoch (utilities/run_model_vevo.py:101-119) on (B, L, 159) logits: total, chord, emotion."""
+    tgt = torch.as_tensor(bt["tgt"]).reshape(-1).to(logits.device)
+    rows = torch.as_tensor(HE.emotion_rows(bt["tgt"], bt["emo_class"])).to(logits.device, logits.dtype)
+    chord = torch.nn.CrossEntropyLoss(ignore_index=C.CHORD_PAD, label_smoothing=smoothing)(logits.reshape(-1, C.CHORD_SIZE), tgt)
+    emotion = torch.nn.BCEWithLogitsLoss()(logits, rows)
+    return lam * chord + (1 - lam) * emotion, chord, emotion
+
+
+def grads(sd, cfg, bt, dtype, masks=None, smoothing=SMOOTHING):
+    """(losses (3,), logits, {key: gradient or None}) of the restatement in `dtype`."""
+    P = {k: torch.as_tensor(np.asarray(v)).to(dtype).requires_grad_(True) for k, v in sd.items()}
+    logits = forward(P, cfg, bt, masks)
+    total, chord, emotion = loss(logits, bt, smoothing)
+    total.backward()
+    return (np.array([float(total.detach()), float(chord.detach()), float(emotion.detach())]), logits.detach().numpy(),
+            {k: None if p.grad is None else p.grad.numpy() for k, p in P.items()})
+
+
+def rel_err(got, want):
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    return float(np.abs(got - want).max() / np.abs(want).max())
+
+
+def draw_masks(cfg, p, seed, B=B_CLIPS, L=L_CHORD, S=S_VIDEO):
+    """A mask for every dropout site, in the order of `VideoMusicTransformer._forward_train`, as numpy arrays."""
+    rng = np.random.default_rng(seed)
+    d, ff, H = cfg["d_model"], cfg["dim_feedforward"], cfg["num_heads"]
+    el = lambda rows, w: ((rng.random((rows, w)) >= p) / (1.0 - p)).astype(np.float32)
+    at = lambda Lq, Lk: (rng.random((B, H, Lq, Lk)) >= p).astype(np.uint8)
+    m = [el(B * S, d), el(B * L, d)]
+    for _ in range(cfg["n_layers"]):
+        m += [at(S, S), el(B * S, d), el(B * S, ff), el(B * S, d)]
+    for _ in range(cfg["n_layers"]):
+        m += [at(L, L), el(B * L, d), at(L, S), el(B * L, d), el(B * L, ff), el(B * L, d)]
+    return m

@@ -1,12 +1,20 @@
 """`torch.autograd.Function`s over the library calls: what `VideoRegression` is built from in the training state
 (regModel 'lstm' / 'bilstm' / 'gru' / 'bigru'), so that `loss.backward()` and any torch optimiser work on the module's own parameters.
 
-    LinearFn          y = act(x w^T + b), act 0 none / 2 sigmoid      amt_linear_ex_fwd; backward: two GEMMs
+    LinearFn          y = act(x w^T + b), act 0 none / 1 ReLU / 2 sigmoid   amt_linear_ex_fwd; backward: two GEMMs
     SigmoidHeadFn     the classifier head; hands out a second, empty-storage output that stands for its logits, so that the
                       fused loss can send its logit gradient straight to the head's GEMMs (losses.regression_train_loss)
     RnnLayerFn        one nn.LSTM / nn.GRU layer, all its directions    amt_linear_ex_fwd + amt_rnn_seq_train_fwd;
                       backward: amt_rnn_seq_bwd + GEMMs
     RegLossFn         SmoothL1 + BCE and both gradients                 amt_reg_loss_fwd_bwd
+
+and the pieces of the chord model's training that do not depend on the model (losses.chord_train_loss):
+
+    AttentionFn       softmax(q k^T (+ relative term) (+ mask)) v with an optional keep mask on the probabilities
+                                                                          amt_attn_train_fwd; backward: amt_attn_bwd
+    LayerNormFn       LayerNorm(x (+ resid)); gradients of both addends   amt_layernorm_fwd; backward: amt_layernorm_bwd
+    ChordLossFn       smoothed cross-entropy + BCE-with-logits            amt_chord_loss_fwd_bwd
+    EmbeddingFn       rows of a table; the table's gradient is a one-hot product on the GEMM (deterministic), not index_add_
 
 Every dense product of the backward runs on `amt_linear_ex_fwd` (y = x w^T, K a multiple of 32): `a b` and `a^T b` go there as
 transposed, zero-padded copies made by torch (`mm_nt`, `mm_tn`).  A bias gradient is the column of ones appended to the right
@@ -63,16 +71,21 @@ class LinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, act=0, w_fwd=None):
-        assert act in (0, 2)
+        assert act in (0, 1, 2)
         y = ops.linear_ex(x, (w if w_fwd is None else w_fwd).detach(), b.detach(), act=act)
         ctx.act = act
-        ctx.save_for_backward(x, w, y if act == 2 else None)
+        ctx.save_for_backward(x, w, y if act else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
-        dz = dy.contiguous() if ctx.act == 0 else (dy * y * (1.0 - y)).contiguous()      # the sigmoid's derivative from its output
+        if ctx.act == 0:
+            dz = dy.contiguous()
+        elif ctx.act == 1:
+            dz = (dy * (y > 0)).contiguous()                    # the ReLU's derivative from its output, 0 at 0 as torch's
+        else:
+            dz = (dy * y * (1.0 - y)).contiguous()              # the sigmoid's derivative from its output
         dx, dw, db = _linear_backward(ctx, dz, x, w.detach(), ctx.needs_input_grad[0])
         return dx, dw, db, None, None
 
@@ -166,6 +179,97 @@ class RegLossFn(torch.autograd.Function):
     def backward(ctx, g):
         d_ln_nd, d_logit = ctx.saved_tensors
         return d_ln_nd * g, d_logit * g, None, None, None, None
+
+
+def blh_strides(Lq, Lk, H, hd, kv_group=1):
+    """The twelve strides of (B, L, heads * hd) row-major q / k / v / o as amt_attn_fwd takes them."""
+    E, Ek = H * hd, (H // kv_group) * hd
+    return (Lq * E, hd, E, Lk * Ek, hd, Ek, Lk * Ek, hd, Ek, Lq * E, hd, E)
+
+
+class AttentionFn(torch.autograd.Function):
+    """apply(q (B, Lq, H hd), k, v (B, Lk, (H / kv_group) hd), Er (er_len, hd) or None, keep (B, H, Lq, Lk) uint8 or None, H, causal,
+    q_scale, keep_scale, kv_group) -> O (B, Lq, H hd).  Saves q, k, v, O, the rows' log-sum-exp and the keep mask; the backward
+    returns the gradients of q (q_scale included), k, v and Er."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, Er, keep, H, causal, q_scale, keep_scale=1.0, kv_group=1):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        B, Lq, E = q.shape
+        Lk, hd = k.shape[1], E // H
+        strides = blh_strides(Lq, Lk, H, hd, kv_group)
+        Er_ = None if Er is None else Er.detach().contiguous()
+        o, lse = ops.attention_train(q, k, v, strides, B, H, Lq, Lk, hd, causal, q_scale, torch.empty_like(q), kv_group=kv_group,
+                                     Er=Er_, keep=keep, keep_scale=keep_scale)
+        ctx.args = (strides, B, H, Lq, Lk, hd, bool(causal), float(q_scale), float(keep_scale), kv_group)
+        ctx.save_for_backward(q, k, v, o, lse, Er_, keep)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        q, k, v, o, lse, Er, keep = ctx.saved_tensors
+        strides, B, H, Lq, Lk, hd, causal, q_scale, keep_scale, kv_group = ctx.args
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        dEr = ops.attention_bwd(dO.contiguous(), q, k, v, o, lse, strides, B, H, Lq, Lk, hd, causal, q_scale, dq, dk, dv, kv_group=kv_group,
+                                Er=Er, keep=keep, keep_scale=keep_scale, need_dEr=Er is not None and ctx.needs_input_grad[3])
+        return dq, dk, dv, dEr, None, None, None, None, None, None
+
+
+class LayerNormFn(torch.autograd.Function):
+    """apply(x, resid, w, b, eps) -> LayerNorm(x (+ resid)) * w + b over rows x (rows, dim); resid may be None.  The forward's inputs
+    are what is saved; the backward forms the row statistics again and hands the same gradient to both addends."""
+
+    @staticmethod
+    def forward(ctx, x, resid, w, b, eps=1e-5):
+        x = x.contiguous()
+        resid = None if resid is None else resid.contiguous()
+        y = ops.layernorm(x, w.detach(), b.detach(), resid=resid, eps=eps)
+        ctx.eps = eps
+        ctx.save_for_backward(x, resid, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, resid, w = ctx.saved_tensors
+        dx, dw, db = ops.layernorm_bwd(dy.contiguous(), x, w.detach(), resid=resid, eps=ctx.eps)
+        return (dx if ctx.needs_input_grad[0] else None, dx if resid is not None and ctx.needs_input_grad[1] else None, dw, db, None)
+
+
+class EmbeddingFn(torch.autograd.Function):
+    """apply(table (n, d), idx (rows,) int64) -> table[idx]; backward: onehot(idx)^T dy on `mm_tn`, a fixed order of additions."""
+
+    @staticmethod
+    def forward(ctx, table, idx):
+        ctx.n = table.shape[0]
+        ctx.save_for_backward(idx)
+        return table.detach().index_select(0, idx)
+
+    @staticmethod
+    def backward(ctx, dy):
+        idx, = ctx.saved_tensors
+        onehot = torch.zeros(idx.numel(), ctx.n, device=dy.device, dtype=torch.float32)
+        onehot[torch.arange(idx.numel(), device=dy.device), idx] = 1.0
+        return mm_tn(onehot, dy.contiguous()), None
+
+
+class ChordLossFn(torch.autograd.Function):
+    """apply(logits (B, L, >=159), tgt (B, L) int64, emo_class (B, L) int32, lambda, smoothing) -> the scalar training loss of the
+    chord model; its backward hands the kernel's gradient on, scaled by the incoming one."""
+
+    @staticmethod
+    def forward(ctx, logits, tgt, emo_class, lam, smoothing):
+        loss, clip, dlogits = ops.chord_loss(logits, tgt, emo_class, lam, smoothing, backward=ctx.needs_input_grad[0])
+        ctx.save_for_backward(dlogits)
+        ctx.width = logits.shape[2]
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dlogits, = ctx.saved_tensors
+        d = dlogits * g
+        if ctx.width > d.shape[2]:                              # columns past the 159 classes take no part
+            d = torch.nn.functional.pad(d, (0, ctx.width - d.shape[2]))
+        return d, None, None, None, None
 
 
 def dropout_mask(shape, p, device):

@@ -26,11 +26,13 @@ constexpr int KT = 32;       // keys per tile
 
 // NOMASK: relative positions WITHOUT the causal mask (forward(mask=False)); a separate instantiation so that the causal kernel
 // of the hot path keeps its exact instruction stream
-template <int HD, bool RPR, bool NOMASK = false>
+// TRAIN: the training forward (amt_attn_train_fwd): a keep mask applied to P after the row sums (torch drops after the softmax,
+// model/rpr.py:409-412) and the row's log-sum-exp written out for the backward; separate instantiations for the same reason
+template <int HD, bool RPR, bool NOMASK = false, bool TRAIN = false>
 // without the relative-position term (cross-attention, the encoder, GQA) and head_dim <= 64 the kernel is held at 168 registers = THREE
 // waves per SIMD (three 51 KB workgroups per CU): two resident workgroups drift into lockstep -- both in their MFMA phases, then both in
 // their softmax -- and the matrix pipe idles meanwhile; a third one fills the gaps
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((!RPR && HD <= 64) ? 3 : 1, (!RPR && HD <= 64) ? 3 : 8)))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((!RPR && HD <= 64 && !TRAIN) ? 3 : 1, (!RPR && HD <= 64 && !TRAIN) ? 3 : 8)))
 void attn_prefill_kernel(AttnParams p) {
     constexpr int HDP = HD < 32 ? 32 : HD;   // head_dim 16: the O^T tile is still 32 rows of d; V columns 16..31 are zeros in LDS
     constexpr int LD = HDP + 4;
@@ -220,6 +222,15 @@ void attn_prefill_kernel(AttnParams p) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) oacc[dt][e] *= alpha;
 
+        if constexpr (TRAIN) if (p.keep) {                  // dropped probabilities leave the product, not the normaliser
+            const uint8_t* kr = p.keep + ((size_t)bh * p.Lq + min(iq, p.Lq - 1)) * p.Lk;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int j = j0 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+                sacc[e] *= (j < p.Lk && kr[j]) ? p.keep_scale : 0.f;
+            }
+        }
+
         // ---- O^T += V^T . P^T : k-step e pairs key krow(e,0) (lanes 0-31) with krow(e,1) ----
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -235,6 +246,7 @@ void attn_prefill_kernel(AttnParams p) {
     // ---- normalise, transpose through the wave's scratch, store rows coalesced ----
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
+    if constexpr (TRAIN) if (lh == 0 && iq < p.Lq) p.lse[(size_t)bh * p.Lq + iq] = m_run + logf(l_tot);
     __syncthreads();                     // all waves are done with their scratch as R band
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt)
@@ -257,7 +269,7 @@ void attn_prefill_kernel(AttnParams p) {
 // in the loop --, and the 4 partial softmax states (m, l, O) are merged through LDS at the end.  Grid = 4x the blocks of the
 // 128-row kernel and a critical path 4x shorter; K/V tiles are read once per 32 query rows instead of once per 128 (L2
 // traffic the large-grid shapes would not want).  No relative-position term.
-template <int HD>
+template <int HD, bool TRAIN = false>
 __global__ __launch_bounds__(256) void attn_prefill_splitk_kernel(AttnParams p) {
     constexpr int LD = HD + 4, NS = HD / 8, ND = HD / 32;
     constexpr int TILE = KT * LD;
@@ -356,6 +368,14 @@ __global__ __launch_bounds__(256) void attn_prefill_splitk_kernel(AttnParams p) 
         for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
             for (int e = 0; e < 16; ++e) oacc[dt][e] *= alpha;
+        if constexpr (TRAIN) if (p.keep) {
+            const uint8_t* kr = p.keep + ((size_t)bh * p.Lq + min(iq, p.Lq - 1)) * p.Lk;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int j = j0 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+                sacc[e] *= (j < p.Lk && kr[j]) ? p.keep_scale : 0.f;
+            }
+        }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int krow = (e & 3) + 8 * (e >> 2) + 4 * lh;
@@ -394,15 +414,21 @@ __global__ __launch_bounds__(256) void attn_prefill_splitk_kernel(AttnParams p) 
             den += a * KV[w][32 * (HD + 1) + 32 + r];
         }
         op[(size_t)(i0 + r) * p.o_ls + c] = den > 0.f ? num / den : 0.f;
+        if constexpr (TRAIN) if (c == 0) p.lse[(size_t)bh * p.Lq + i0 + r] = mx + logf(den);
     }
 }
 
-template <int HD>
+template <int HD, bool TRAIN>
 int32_t launch_hd(const AttnParams& p, hipStream_t stream) {
     dim3 grid(cdiv(p.Lq, QB) * p.H * p.B);
     // fewer than two 128-row blocks per CU and a long key range: one 32-row block per workgroup, keys split over its waves
     if (!p.Er && HD >= 32 && HD <= 64 && grid.x < 512 && p.Lk >= 256) {
-        hipLaunchKernelGGL((attn_prefill_splitk_kernel<(HD >= 32 && HD <= 64 ? HD : 64)>), dim3(cdiv(p.Lq, 32) * p.H * p.B), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((attn_prefill_splitk_kernel<(HD >= 32 && HD <= 64 ? HD : 64), TRAIN>), dim3(cdiv(p.Lq, 32) * p.H * p.B), dim3(256), 0, stream, p);
+        return 0;
+    }
+    if constexpr (TRAIN) {                  // relative positions in training: causal only (checked by the caller)
+        if (p.Er) hipLaunchKernelGGL((attn_prefill_kernel<HD, true, false, true>), grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((attn_prefill_kernel<HD, false, false, true>), grid, dim3(256), 0, stream, p);
         return 0;
     }
     if (p.Er && !p.causal) hipLaunchKernelGGL((attn_prefill_kernel<HD, true, true>), grid, dim3(256), 0, stream, p);
@@ -411,21 +437,32 @@ int32_t launch_hd(const AttnParams& p, hipStream_t stream) {
     return 0;
 }
 
-}  // namespace
-
-int32_t amt_launch_attn_prefill(const AttnParams& p, hipStream_t stream) {
+template <bool TRAIN>
+int32_t launch_checked(const AttnParams& p, hipStream_t stream) {
     AMT_CHECK_ARG(p.B > 0 && p.H > 0 && p.Lq > 0 && p.Lk > 0, "attn_prefill: bad shape");
     AMT_CHECK_ARG(p.kv_group >= 1 && p.H % p.kv_group == 0, "attn_prefill: bad kv_group %d", p.kv_group);
     AMT_CHECK_ARG(p.Er == nullptr || (p.Lq == p.Lk && p.Lq <= p.er_len),
                   "attn_prefill: relative positions need self-attention with L=%d <= er_len=%d", p.Lq, p.er_len);
     AMT_CHECK_ARG(p.q_ls % 4 == 0 && p.k_ls % 4 == 0 && p.v_ls % 4 == 0, "attn_prefill: row strides must be multiples of 4 floats");
     switch (p.hd) {
-        case 16: launch_hd<16>(p, stream); break;
-        case 32: launch_hd<32>(p, stream); break;
-        case 64: launch_hd<64>(p, stream); break;
-        case 128: launch_hd<128>(p, stream); break;
+        case 16: launch_hd<16, TRAIN>(p, stream); break;
+        case 32: launch_hd<32, TRAIN>(p, stream); break;
+        case 64: launch_hd<64, TRAIN>(p, stream); break;
+        case 128: launch_hd<128, TRAIN>(p, stream); break;
         default: AMT_CHECK_ARG(false, "attn_prefill: head_dim %d not in {16,32,64,128}", p.hd);
     }
     AMT_LAUNCH_CHECK();
     return 0;
+}
+
+}  // namespace
+
+int32_t amt_launch_attn_prefill(const AttnParams& p, hipStream_t stream) { return launch_checked<false>(p, stream); }
+
+// the training forward: p.lse is written, p.keep (optional) applied; the same kernel choice as the inference call makes for the shape,
+// so that O without a keep mask is the inference call's, bit for bit
+int32_t amt_launch_attn_train(const AttnParams& p, hipStream_t stream) {
+    AMT_CHECK_ARG(p.lse != nullptr, "attn_train: null lse");
+    AMT_CHECK_ARG(p.Er == nullptr || p.causal, "attn_train: relative positions need the causal mask");
+    return launch_checked<true>(p, stream);
 }

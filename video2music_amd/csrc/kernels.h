@@ -67,8 +67,23 @@ struct AttnParams {
     int kv_group;               // query head h uses kv head h / kv_group (GQA); 1 for MHA
     float mask_value;           // -inf (additive mask semantics) or finfo.min (masked_fill semantics)
     float q_scale;              // multiplies Q on load (0 = unset = 1): torch MHA scales q by hd^-0.5 after the in-projection
+    // training forward only (amt_launch_attn_train): keep (B,H,Lq,Lk) bytes, 1 = kept, or null; P * keep * keep_scale enters the
+    // product with V, the normaliser stays that of the undropped P; lse (B,H,Lq) = log-sum-exp of the row's scores
+    const uint8_t* keep; float keep_scale; float* lse;
 };
 int32_t amt_launch_attn_prefill(const AttnParams& p, hipStream_t stream);
+int32_t amt_launch_attn_train(const AttnParams& p, hipStream_t stream);
+
+// ---------------- attention, backward (attn_bwd.hip) ----------------
+struct AttnBwdParams {
+    AttnParams f;               // the forward's arguments: q, k, v, o (the forward's output), strides, shape, Er, keep, lse
+    const float* dO;            // o's strides
+    float* dq; float* dk; float* dv;   // q's / k's / v's strides
+    float* dEr;                 // (er_len, hd) or null
+    float* ws;                  // amt_attn_bwd_ws_floats
+};
+int64_t amt_attn_bwd_ws_floats_of(int B, int H, int Lq, int Lk, int hd, int rpr);
+int32_t amt_launch_attn_bwd(const AttnBwdParams& p, hipStream_t stream);
 
 // ---------------- attention, decode (attn_decode.hip) ----------------
 struct AttnDecodeParams {

@@ -9,37 +9,13 @@
 // timing (no floating-point atomics; the integer counts are exact in any order).  HBM-bound: 636 bytes per row.
 #include "../../include/amt_hip.h"
 #include "amt_common.h"
+#include "chord_rows.h"
 
 namespace {
 
-constexpr int NC = 159, ID_END = 157, ID_PAD = 158;     // utilities/constants.py:50-52
 constexpr int CHUNK = 1024;                             // rows whose sums wait in LDS for the ordered pass
 constexpr int MAX_WAVES = 16;
 constexpr int N_NEUTRAL = 5;
-
-// emotion class -> chord qualities it accepts (dataset/vevo_dataset.py:461-475), bit q-1 for quality q = 1..13 in the order
-// maj dim sus4 min7 min sus2 aug dim7 maj6 hdim7 7 min6 maj7
-constexpr uint32_t qrow(const char (&s)[14]) {
-    uint32_t m = 0;
-    for (int i = 0; i < 13; ++i) m |= (s[i] == '1' ? 1u : 0u) << i;
-    return m;
-}
-constexpr uint32_t Q_EXCITING = qrow("1010000000100"), Q_FEARFUL = qrow("0101000101000"), Q_TENSE = qrow("0111000000100"),
-                   Q_SAD = qrow("0001110000000"), Q_RELAXING = qrow("1000000010001");
-__device__ __forceinline__ uint32_t quality_mask(int emo) {
-    return emo == 0 ? Q_EXCITING : emo == 1 ? Q_FEARFUL : emo == 2 ? Q_TENSE : emo == 3 ? Q_SAD : emo == 4 ? Q_RELAXING : 0u;
-}
-
-__device__ __forceinline__ void load_row(const float* __restrict__ p, int lane, float& y0, float& y1, float& y2) {
-    y0 = p[lane];
-    y1 = p[lane + 64];
-    y2 = lane < NC - 128 ? p[lane + 128] : -INFINITY;
-}
-
-// max(y,0) - y*t + log1p(exp(-|y|)): torch's binary_cross_entropy_with_logits
-__device__ __forceinline__ float bce_term(float y, bool t) {
-    return (fmaxf(y, 0.0f) - (t ? y : 0.0f)) + log1pf(expf(-fabsf(y)));
-}
 
 enum { C_VALID, C_TOP1, C_HIT1, C_HIT3, C_HIT5, C_COUNTED, C_RIGHT, N_COUNTS };
 

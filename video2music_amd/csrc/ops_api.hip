@@ -109,6 +109,48 @@ extern "C" int32_t amt_attn_fwd(const float* q, const float* k, const float* v, 
     return amt_launch_attn_prefill(a, (hipStream_t)stream);
 }
 
+static AttnParams strided_params(const float* q, const float* k, const float* v, float* o, const int64_t* strides, int B, int H, int Lq,
+                                 int Lk, int hd, int causal, int kv_group, float q_scale) {
+    AttnParams a{};
+    a.q = q; a.k = k; a.v = v; a.o = o;
+    a.q_bs = strides[0]; a.q_hs = strides[1]; a.q_ls = strides[2];
+    a.k_bs = strides[3]; a.k_hs = strides[4]; a.k_ls = strides[5];
+    a.v_bs = strides[6]; a.v_hs = strides[7]; a.v_ls = strides[8];
+    a.o_bs = strides[9]; a.o_hs = strides[10]; a.o_ls = strides[11];
+    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.hd = hd; a.causal = causal; a.kv_group = kv_group > 0 ? kv_group : 1; a.q_scale = q_scale;
+    return a;
+}
+
+extern "C" int32_t amt_attn_train_fwd(const float* q, const float* k, const float* v, float* o, const int64_t* strides,
+                                      int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t causal, int32_t kv_group,
+                                      float q_scale, const float* Er, int32_t er_len, const uint8_t* keep, float keep_scale, float* lse,
+                                      void* stream) {
+    AMT_CHECK_ARG(q && k && v && o && strides && lse, "amt_attn_train_fwd: null pointer");
+    AMT_CHECK_ARG(hd != 16, "amt_attn_train_fwd: head_dim 16 is not built for training (amt_attn_bwd has no instantiation for it)");
+    AMT_CHECK_ARG(Er == nullptr || kv_group <= 1, "amt_attn_train_fwd: relative positions with kv_group %d: amt_attn_bwd takes kv_group 1 with Er", kv_group);
+    AttnParams a = strided_params(q, k, v, o, strides, B, H, Lq, Lk, hd, causal, kv_group, q_scale);
+    a.Er = Er; a.er_len = er_len; a.keep = keep; a.keep_scale = keep_scale; a.lse = lse;
+    return amt_launch_attn_train(a, (hipStream_t)stream);
+}
+
+extern "C" int64_t amt_attn_bwd_ws_floats(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t rpr) {
+    if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || hd <= 0) return 0;
+    return amt_attn_bwd_ws_floats_of(B, H, Lq, Lk, hd, rpr);
+}
+
+extern "C" int32_t amt_attn_bwd(const float* dO, const float* q, const float* k, const float* v, const float* o, const float* lse,
+                                const float* Er, int32_t er_len, const uint8_t* keep, float keep_scale, float* dq, float* dk, float* dv,
+                                float* dEr, const int64_t* strides, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd,
+                                int32_t causal, int32_t kv_group, float q_scale, float* ws, void* stream) {
+    AMT_CHECK_ARG(dO && q && k && v && o && lse && dq && dk && dv && strides && ws, "amt_attn_bwd: null pointer");
+    AMT_CHECK_ARG(((uintptr_t)ws & 15) == 0, "amt_attn_bwd: ws must be 16-byte aligned");
+    AttnBwdParams P{};
+    P.f = strided_params(q, k, v, const_cast<float*>(o), strides, B, H, Lq, Lk, hd, causal, kv_group, q_scale);
+    P.f.Er = Er; P.f.er_len = er_len; P.f.keep = keep; P.f.keep_scale = keep_scale; P.f.lse = const_cast<float*>(lse);
+    P.dO = dO; P.dq = dq; P.dk = dk; P.dv = dv; P.dEr = dEr; P.ws = ws;
+    return amt_launch_attn_bwd(P, (hipStream_t)stream);
+}
+
 extern "C" int32_t amt_concat_features_fwd(const float* sem, int32_t sem_dim, const float* scene, const float* motion, int32_t motion_dim,
                                            const float* emotion, int32_t emo_dim, float* out, int32_t rows, int32_t ld_out, void* stream) {
     AMT_CHECK_ARG(sem && scene && motion && emotion && out && rows > 0, "amt_concat_features_fwd: bad argument");

@@ -79,6 +79,28 @@ def attention(q, k, v, strides, B, H, Lq, Lk, hd, causal, q_scale, out):
     return out
 
 
+def attention_train(q, k, v, strides, B, H, Lq, Lk, hd, causal, q_scale, out, kv_group=1, Er=None, keep=None, keep_scale=1.0):
+    """amt_attn_train_fwd: `attention` that also returns lse (B, H, Lq) for `attention_bwd`.  Er (er_len, hd): the relative-position
+    table (causal self-attention only); keep (B, H, Lq, Lk) uint8, 1 = kept, with keep_scale = 1 / (1 - p)."""
+    s = (C.c_int64 * 12)(*strides)
+    assert keep is None or (keep.dtype == torch.uint8 and keep.shape == (B, H, Lq, Lk))
+    lse = torch.empty(B, H, Lq, device=out.device, dtype=torch.float32)
+    _lib.call("amt_attn_train_fwd", p(q), p(k), p(v), p(out), s, B, H, Lq, Lk, hd, int(causal), int(kv_group), float(q_scale), p(Er),
+              0 if Er is None else Er.shape[0], p(keep), float(keep_scale), p(lse), _st())
+    return out, lse
+
+
+def attention_bwd(dO, q, k, v, o, lse, strides, B, H, Lq, Lk, hd, causal, q_scale, dq, dk, dv, kv_group=1, Er=None, keep=None,
+                  keep_scale=1.0, need_dEr=True):
+    """amt_attn_bwd: fills dq / dk / dv (buffers laid out as q / k / v; dO as o) and returns dEr (er_len, hd) or None."""
+    s = (C.c_int64 * 12)(*strides)
+    dEr = torch.empty_like(Er) if Er is not None and need_dEr else None
+    ws = torch.empty(_lib.call("amt_attn_bwd_ws_floats", B, H, Lq, Lk, hd, int(Er is not None)), device=dO.device, dtype=torch.float32)
+    _lib.call("amt_attn_bwd", p(dO), p(q), p(k), p(v), p(o), p(lse), p(Er), 0 if Er is None else Er.shape[0], p(keep), float(keep_scale),
+              p(dq), p(dk), p(dv), p(dEr), s, B, H, Lq, Lk, hd, int(causal), int(kv_group), float(q_scale), p(ws), _st())
+    return dEr
+
+
 def glu(x, e):
     """GLUExpert.forward on rows x (n, d): W2((W1 x + b1) * silu(Wg x + bg)) + b2."""
     from .model.moe import expert_dff, expert_tensors
@@ -190,6 +212,42 @@ def reg_loss(ln_nd, inst, note_density, loudness, instrument):
     _lib.call("amt_reg_loss_fwd_bwd", p(ln_nd), p(inst), p(note_density), p(loudness), p(instrument), rows, p(loss), p(d_ln_nd), p(d_logit),
               p(ws), _st())
     return loss, d_ln_nd, d_logit
+
+
+def layernorm_bwd(dy, x, w, resid=None, eps=1e-5):
+    """amt_layernorm_bwd: the backward of `layernorm(x, w, b, resid, eps)` from dy and the forward's own inputs.  Returns dx (the
+    gradient of x and of resid alike), dw, db."""
+    rows, dim = x.shape
+    assert dy.shape == x.shape and (resid is None or resid.shape == x.shape) and w.shape == (dim,)
+    for t in (dy, x, w) + (() if resid is None else (resid,)):
+        assert t.dtype == torch.float32
+    dx = torch.empty_like(x)
+    dw, db = torch.empty_like(w), torch.empty_like(w)
+    ws = torch.empty(4 + 256 * dim, device=x.device, dtype=torch.float32)       # AMT_LAYERNORM_BWD_WS_FLOATS(dim); a call's own scratch
+    _lib.call("amt_layernorm_bwd", p(dy), p(x), p(resid), p(w), p(dx), p(dw), p(db), p(ws), rows, dim, float(eps), _st())
+    return dx, dw, db
+
+
+CHORD_LOSS_CLIP_FIELDS = ("n_valid", "ce_sum", "bce_sum", "n_rows")
+
+
+def chord_loss(logits, tgt, emo_class, lam, smoothing, backward=True):
+    """amt_chord_loss_fwd_bwd on logits (B, L, >=159) whose last dimension is contiguous and whose rows are evenly strided; tgt (B, L)
+    int64, emo_class (B, L) int32.  Returns loss (3,) = {total, chord, emotion}, clip (B, 4) in the order of CHORD_LOSS_CLIP_FIELDS
+    and dlogits (B, L, 159) -- None with backward=False, which leaves loss and clip the same bits."""
+    B, L = tgt.shape
+    assert logits.dtype == torch.float32 and logits.shape[:2] == (B, L) and logits.stride(2) == 1
+    assert tgt.dtype == torch.int64 and emo_class.dtype == torch.int32 and emo_class.shape == (B, L)
+    ld = logits.stride(1) if L > 1 else max(logits.stride(0), logits.shape[2])
+    assert B == 1 or logits.stride(0) == L * ld, "rows of logits must be evenly strided"
+    dev = logits.device
+    loss = torch.empty(3, device=dev, dtype=torch.float32)
+    clip = torch.empty(B, len(CHORD_LOSS_CLIP_FIELDS), device=dev, dtype=torch.float32)
+    dlogits = torch.empty(B, L, 159, device=dev, dtype=torch.float32) if backward else None
+    ws = torch.empty(_lib.call("amt_chord_loss_ws_floats", B, L), device=dev, dtype=torch.float32)
+    _lib.call("amt_chord_loss_fwd_bwd", C.c_void_p(logits.data_ptr()), ld, p(tgt), p(emo_class), B, L, float(lam), float(smoothing),
+              p(loss), p(clip), p(dlogits), p(ws), _st())
+    return loss, clip, dlogits
 
 
 def selective_scan(xc, draw, dt_bias, A_log, dbc, R, D, xz, B, L, version=1, reverse=False):

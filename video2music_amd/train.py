@@ -1,0 +1,262 @@
+"""``train.py`` entry point (reference ``train.py:46-380``, ``utilities/run_model_vevo.py:20-196``): trains the base
+``VideoMusicTransformer`` (``-music_gen_version None -chord_embed ""``, ``rpr`` on or off) on the GPU.
+
+A step is the model's training-state forward (``VideoMusicTransformer._forward_train``: the library's GEMMs, attention and
+LayerNorm kernels through ``video2music_amd/autograd.py``), the fused loss (``losses.chord_train_loss``), ``backward()`` and a torch
+optimiser.  The loop is the reference's: epoch "0" only evaluates; every epoch ends with six figures on the train and the validation
+split -- formed per clip and averaged over clips, as the reference's loaders of batch size 1 do, with the TRAINING loss function
+(the chord loss is the smoothed one): hits@1/3/5 and the emotion loss from ``metrics.chord_metrics``, the chord loss from the loss
+kernel's per-clip sums in forward-only mode --, a row of ``results.csv``, ``best_loss_weights.pickle`` / ``best_epochs.txt`` when the
+validation total loss improves, and ``weights/epoch_NNNN.pickle`` every ``-weight_modulus`` epochs.  The clips are read once; their
+order is shuffled per epoch from ``--seed``.
+
+Refused, with the reason: ``-music_gen_version`` 1.x / 2.x / 3.x, ``-is_video False``, ``-scene_embed``, ``-chord_embed``,
+``-auxiliary_loss``, ``-drop_loss``, ``-augmentation``, tensorboard, ``--force_cpu``, optimisers other than Adam / AdamW, one of
+``-continue_weights`` / ``-continue_epoch`` without the other.  The parser keeps the reference's defaults (``music_gen_version
+'1.2.3'``, ``chord_embed True``), so the bare command refuses and names the two flags that select the base model.
+
+    python -m video2music_amd.train -dataset_dir ./dataset/ -music_gen_version None -chord_embed "" -motion_type 1
+"""
+import csv
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import metrics, ops
+from .dataset import vevo_features as VF
+from .losses import chord_train_loss
+from .model.video_music_transformer import VideoMusicTransformer
+from .train_regression import (BASELINE_EPOCH, LR_DEFAULT_START, PREPEND_ZEROS_WIDTH, SCHEDULER_WARMUP_STEPS, SEPERATOR, LrStepTracker,
+                               make_optimizer, names_of)
+from .utilities.argument_funcs import parse_train_args
+from .utilities.constants import IS_SEPERATED, LOSS_LAMBDA, VERSION
+from .utilities.device import get_device
+
+CSV_HEADER = ["Epoch", "Learn rate",
+              "Avg Train loss (total)", "Avg Train loss (chord)", "Avg Train loss (emotion)",
+              "Avg Train h1", "Avg Train h3", "Avg Train h5",
+              "Avg Eval loss (total)", "Avg Eval loss (chord)", "Avg Eval loss (emotion)",
+              "Avg Eval h1", "Avg Eval h3", "Avg Eval h5"]                                   # train.py:30-34
+FIGURE_KEYS = ("avg_total_loss", "avg_loss_chord", "avg_loss_emotion", "avg_h1", "avg_h3", "avg_h5")
+BASE_FLAGS = '-music_gen_version None -chord_embed ""'
+# output files (train.py:73-88, :359-362), relative to -output_dir
+PARAMS_FILE, RESULTS_FILE, BEST_WEIGHTS_FILE, BEST_TEXT_FILE, WEIGHTS_DIR, ARCHITECTURE_FILE = (
+    "model_params.txt", "results.csv", "best_loss_weights.pickle", "best_epochs.txt", "weights", "model_architecture.txt")
+
+
+def output_paths(output_dir):
+    """The files of a run under `output_dir`, made ready: {params, results, best_weights, best_text, weights_dir, architecture}."""
+    out_dir = os.path.join(output_dir, VERSION)
+    os.makedirs(os.path.join(out_dir, WEIGHTS_DIR), exist_ok=True)
+    return {"params": os.path.join(out_dir, PARAMS_FILE), "results": os.path.join(out_dir, RESULTS_FILE),
+            "best_weights": os.path.join(out_dir, BEST_WEIGHTS_FILE), "best_text": os.path.join(out_dir, BEST_TEXT_FILE),
+            "weights_dir": os.path.join(out_dir, WEIGHTS_DIR), "architecture": os.path.join(output_dir, ARCHITECTURE_FILE)}
+
+
+def epoch_weights_path(weights_dir, epoch):
+    return os.path.join(weights_dir, "epoch_" + str(epoch).zfill(PREPEND_ZEROS_WIDTH) + ".pickle")
+PARAM_LINES = (("rpr", "rpr"), ("lr", "lr"), ("n_epochs", "epochs"), ("ce_smoothing", "ce_smoothing"), ("batch_size", "batch_size"),
+               ("max_sequence_midi", "max_sequence_midi"), ("max_sequence_video", "max_sequence_video"),
+               ("max_sequence_chord", "max_sequence_chord"), ("n_layers", "n_layers"), ("num_heads", "num_heads"), ("d_model", "d_model"),
+               ("dim_feedforward", "dim_feedforward"), ("dropout", "dropout"), ("rms_norm", "rms_norm"),
+               ("music_gen_version", "music_gen_version"), ("is_video", "is_video"), ("vis_models", "vis_models"), ("emo_model", "emo_model"),
+               ("motion_type", "motion_type"), ("scene_embed", "scene_embed"), ("chord_embed", "chord_embed"), ("augmentation", "augmentation"),
+               ("droptoken", "droptoken"), ("input_dir_music", "input_dir_music"), ("input_dir_video", "input_dir_video"),
+               ("optimizer", "optimizer"), ("auxiliary_loss", "auxiliary_loss"), ("drop_loss", "drop_loss"), ("balancing", "balancing"))
+
+
+def parse_args(argv=None):
+    args = parse_train_args(argv)[0]
+    if args.music_gen_version in ("None", "none", ""):
+        args.music_gen_version = None
+    return args
+
+
+def refuse(args):
+    """The reason this build does not run `args`, or None."""
+    if args.force_cpu:
+        return "--force_cpu: video2music_amd has no CPU path (the CPU oracle lives in oracle/ for tests only)"
+    if not args.is_video:
+        return "-is_video False (MusicTransformer) is not built"
+    if args.music_gen_version is not None:
+        return (f"-music_gen_version {args.music_gen_version}: training is built for the base model only (the V1 / V2 / V3 families run "
+                f"inference here); select it with {BASE_FLAGS}")
+    if args.chord_embed:
+        return f"-chord_embed: training with the frozen chord table is not built; select the base model with {BASE_FLAGS}"
+    if args.scene_embed:
+        return "-scene_embed: training with the scene-offset embedding is not built"
+    if IS_SEPERATED:
+        return "IS_SEPERATED: training the separate root / attr heads is not built"
+    if args.auxiliary_loss:
+        return "-auxiliary_loss: the top-k auxiliary losses are not built"
+    if args.drop_loss:
+        return "-drop_loss is not built: every step uses the weighted sum of both losses"
+    if args.augmentation:
+        return "-augmentation is not built: the clips are read as they are"
+    if not args.no_tensorboard:
+        return "--no_tensorboard False: tensorboard reporting is not built (results.csv holds the same figures)"
+    if args.optimizer not in (None, "Adam", "AdamW"):
+        return f"-optimizer {args.optimizer}: Adam or AdamW (RAdam, RAdamW, RAdanW and Lion are not ported)"
+    if (args.continue_weights is None) != (args.continue_epoch is None):
+        return "-continue_weights and -continue_epoch go together"
+    return None
+
+
+def write_model_params(args, path):
+    """utilities/argument_funcs.py:210-246: one "name: value" line per setting."""
+    with open(path, "w") as fh:
+        for name, k in PARAM_LINES:
+            fh.write(f"{name}: {getattr(args, k)}\n")
+
+
+def load(args, names, device):
+    f = VF.load_clips(args.dataset_dir, names, vis_models=args.vis_models, emo_model=args.emo_model, motion_type=args.motion_type,
+                      max_seq_video=args.max_sequence_video, max_seq_chord=args.max_sequence_chord)
+    if "tgt" not in f:
+        raise SystemExit("training needs max_sequence_video >= max_sequence_chord (the emotion row of every target second)")
+    return {k: torch.from_numpy(v).to(device) for k, v in f.items()}
+
+
+def forward(model, f, Tc):
+    return model(f["chord"][:, :Tc - 1].contiguous(), f["chord_root"][:, :Tc - 1].contiguous(), f["chord_attr"][:, :Tc - 1].contiguous(),
+                 f["semantic"], f["key"], f["scene_offset"], f["motion"], f["emotion"])
+
+
+def evaluate(model, data, batch_size, Tc, smoothing):
+    """eval_model's figures (utilities/run_model_vevo.py:198-452) with the training loss function, per clip, then averaged over the
+    clips: {avg_total_loss, avg_loss_chord, avg_loss_emotion, avg_h1, avg_h3, avg_h5}."""
+    model.eval()
+    rows, ce = [], []
+    with torch.set_grad_enabled(False):
+        for b0 in range(0, data["semantic"].shape[0], batch_size):
+            f = {k: v[b0:b0 + batch_size] for k, v in data.items()}
+            y = forward(model, f, Tc)
+            m = metrics.chord_metrics(y, f["tgt"], f["emo_class"], f["emo_prob"])
+            _, clip, _ = ops.chord_loss(y, f["tgt"].contiguous(), f["emo_class"].to(torch.int32).contiguous(), LOSS_LAMBDA, smoothing, backward=False)
+            rows.append(torch.stack([m[k] for k in metrics.FIELDS], dim=1).cpu())
+            ce.append(clip.cpu())
+    per_clip = {k: torch.cat(rows)[:, i].numpy() for i, k in enumerate(metrics.FIELDS)}
+    r = metrics.clip_ratios(per_clip)
+    clip = torch.cat(ce).numpy().astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        chord = clip[:, 1] / clip[:, 0]                     # the smoothed cross-entropy over the clip's valid targets
+    total = LOSS_LAMBDA * chord + (1 - LOSS_LAMBDA) * r["loss_emotion"]
+
+    def mean(a):
+        return sum(a.tolist()) / len(a)
+    return {"avg_total_loss": mean(total), "avg_loss_chord": mean(chord), "avg_loss_emotion": mean(r["loss_emotion"]),
+            "avg_h1": mean(r["h1"]), "avg_h3": mean(r["h3"]), "avg_h5": mean(r["h5"])}
+
+
+def train_epoch(cur_epoch, model, data, order, batch_size, Tc, smoothing, opt, lr_scheduler=None, print_modulus=1):
+    """utilities/run_model_vevo.py:20-196 over the clips `order` of `data`."""
+    model.train()
+    n_batches = (len(order) + batch_size - 1) // batch_size
+    for batch_num in range(n_batches):
+        idx = order[batch_num * batch_size:(batch_num + 1) * batch_size]
+        f = {k: v[idx] for k, v in data.items()}
+        opt.zero_grad()
+        loss = chord_train_loss(forward(model, f, Tc), f["tgt"], f["emo_class"], LOSS_LAMBDA, smoothing)
+        loss.backward()
+        opt.step()
+        if lr_scheduler is not None:
+            lr_scheduler.step()
+        if (batch_num + 1) % print_modulus == 0:
+            print(SEPERATOR)
+            print("Epoch", cur_epoch, " Batch", batch_num + 1, "/", n_batches)
+            print("LR:", opt.param_groups[0]["lr"])
+            print("Train loss (total):", float(loss))
+            print(SEPERATOR)
+            print("")
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    why = refuse(args)
+    if why:
+        raise SystemExit(why)
+    device = get_device()
+    if device.type != "cuda":
+        raise SystemExit("no GPU visible: video2music_amd runs on MI355X only")
+    train_names, val_names = names_of(args, args.train_ids), names_of(args, args.val_ids)
+    if not train_names or not val_names:
+        raise SystemExit("no clips to train or validate on")
+
+    paths = output_paths(args.output_dir)
+    write_model_params(args, paths["params"])
+    results_file, best_loss_file, best_text, weights_folder = paths["results"], paths["best_weights"], paths["best_text"], paths["weights_dir"]
+
+    train, val = load(args, train_names, device), load(args, val_names, device)
+    Tc = args.max_sequence_chord
+    smoothing = float(args.ce_smoothing or 0.0)
+    from .generate import total_vf_dim_of
+    torch.manual_seed(args.seed)
+    model = VideoMusicTransformer(n_layers=args.n_layers, num_heads=args.num_heads, d_model=args.d_model, dim_feedforward=args.dim_feedforward,
+                                  dropout=args.dropout, max_sequence_midi=args.max_sequence_midi, max_sequence_video=args.max_sequence_video,
+                                  max_sequence_chord=args.max_sequence_chord, total_vf_dim=total_vf_dim_of(args, sem_dim=train["semantic"].shape[-1]),
+                                  rpr=bool(args.rpr), scene_embed=False, chord_embed=False)
+    if args.synthetic_weights:
+        from . import synthetic
+        shapes = [(k, tuple(v.shape)) for k, v in model.state_dict().items()]
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic.synthetic_state_dict(shapes, seed=0).items()}, strict=False)
+    with open(paths["architecture"], "w") as fh:
+        fh.write(str(model))
+    start_epoch = BASELINE_EPOCH
+    if args.continue_weights is not None:
+        model.load_state_dict(torch.load(args.continue_weights, map_location="cpu"))
+        start_epoch = args.continue_epoch
+    model = model.to(device)
+
+    bs = max(1, args.batch_size)
+    n_batches = (len(train_names) + bs - 1) // bs
+    if args.lr is None:
+        init_step = 0 if args.continue_epoch is None else args.continue_epoch * n_batches
+        opt = make_optimizer(args, model.parameters(), LR_DEFAULT_START)
+        lr_scheduler = torch.optim.lr_scheduler.LambdaLR(opt, LrStepTracker(args.d_model, SCHEDULER_WARMUP_STEPS, init_step).step)
+    else:
+        opt, lr_scheduler = make_optimizer(args, model.parameters(), args.lr), None
+
+    best_eval_loss, best_eval_loss_epoch = float("inf"), -1
+    if not os.path.isfile(results_file):
+        with open(results_file, "w", newline="") as fh:
+            csv.writer(fh).writerow(CSV_HEADER)
+    rng = np.random.default_rng(args.seed)
+    for epoch in range(start_epoch, args.epochs):
+        if epoch > BASELINE_EPOCH:
+            print(SEPERATOR)
+            print("NEW EPOCH:", epoch + 1)
+            print(SEPERATOR)
+            print("")
+            train_epoch(epoch + 1, model, train, torch.from_numpy(rng.permutation(len(train_names))).to(device), bs, Tc, smoothing, opt,
+                        lr_scheduler, args.print_modulus)
+            print(SEPERATOR)
+            print("Evaluating:")
+        else:
+            print(SEPERATOR)
+            print("Baseline model evaluation (Epoch 0):")
+        tr, ev = evaluate(model, train, bs, Tc, smoothing), evaluate(model, val, bs, Tc, smoothing)
+        lr = opt.param_groups[0]["lr"]
+        print("Epoch:", epoch + 1)
+        for split, figs in (("train", tr), ("val", ev)):
+            for label, k in zip(("loss (total)", "loss (chord)", "loss (emotion)", "h1", "h3", "h5"), FIGURE_KEYS):
+                print(f"Avg {split} {label}:", figs[k])
+        print(SEPERATOR)
+        print("")
+
+        if ev["avg_total_loss"] < best_eval_loss:
+            best_eval_loss, best_eval_loss_epoch = ev["avg_total_loss"], epoch + 1
+            torch.save(model.state_dict(), best_loss_file)
+            with open(best_text, "w") as fh:
+                print("Best val loss epoch:", best_eval_loss_epoch, file=fh)
+                print("Best val loss:", best_eval_loss, file=fh)
+        if (epoch + 1) % args.weight_modulus == 0:
+            torch.save(model.state_dict(), epoch_weights_path(weights_folder, epoch + 1))
+        with open(results_file, "a", newline="") as fh:
+            csv.writer(fh).writerow([epoch + 1, lr] + [tr[k] for k in FIGURE_KEYS] + [ev[k] for k in FIGURE_KEYS])
+    return {"best_epoch": best_eval_loss_epoch, "best_val_total_loss": best_eval_loss}
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
