@@ -298,10 +298,12 @@ def eps_sensitivity(case, eps=1e-6):
 
 
 # ---- the device side -----------------------------------------------------------------------------------------------------------
-def build_model(case):
+def build_model(case, sd=None, **ctor):
+    """The case's model on the device with its options set; `sd` (default: the case's own state dict) and further constructor
+    keywords are for tests/helpers_decode_free.py (a scaled output head, `chord_embed`)."""
     from video2music_amd.model.video_music_transformer import VideoMusicTransformer
-    m = VideoMusicTransformer(**model_cfg(case)).eval()
-    missing, unexpected = m.load_state_dict(state_dict(case), strict=False)
+    m = VideoMusicTransformer(**model_cfg(case), **ctor).eval()
+    missing, unexpected = m.load_state_dict(state_dict(case) if sd is None else sd, strict=False)
     assert not unexpected and all(k.endswith(".pe") for k in missing), (missing, unexpected)
     m.max_decode_batch = case.max_decode_batch
     if case.plain_option:
