@@ -28,7 +28,8 @@
  *     threads concurrently, each on its own stream, as long as they share no output or scratch buffer.
  *   - global state: the library keeps no mutable global besides (a) the thread-local error message, (b) per-device one-time
  *     initialisations (the > 64 KiB dynamic-LDS opt-in of a kernel, a 256-byte block of zero words), each taken under a mutex,
- *     and (c) the immutable tuning record of csrc/amt_common.h.  The release build reads NO environment variable; a
+ *     (c) the process-wide key-stream default of amt_set_option(NULL, "scalar_key_stream", v), one atomic int, and (d) the immutable
+ *     tuning record of csrc/amt_common.h.  The release build reads NO environment variable; a
  *     -DAMT_EXPERIMENT build (tools/ab_build.sh) reads the A/B switches of DESIGN.md once, under std::call_once.
  *   - amt_abi_version() == AMT_ABI_VERSION of the header the caller was built against, or the caller must refuse the library.
  */
@@ -135,6 +136,12 @@ int32_t amt_generate_run(amt_handle* h, int32_t n_steps, float* logits_out, void
  *   "gemm_tile_pipeline" = 0 (any time): the skinny GEMMs of the decode step run their serial tile loop; 1, the default: the pipelined
  *   one (wave-uniform control, next k-tile's LDS reads and folded-FFN fix under this tile's MFMAs).  Part of the key of
  *   a captured graph; results are bit-identical either way.
+ *   "scalar_key_stream" = 0 (any time): the decode attentions of this handle keep the per-lane controlled key stream (every load
+ *   clamped, every key guarded, one batch requested past a wave's last); 1, the default: the scalar-controlled one (per wave a scalar
+ *   batch count, buffer loads on a scalar base, nothing requested behind the last batch).  Part of the key of a captured
+ *   graph; results are bit-identical either way.  With a NULL handle the option sets the process-wide default instead, which the
+ *   operator entry points (amt_attn_decode_fwd, amt_attn_decode_fold_fwd) and the lockstep step (amt_v2_step*) follow: they carry no
+ *   handle.  A launch runs the scalar stream when neither its handle (or its new_kv bit 2) nor the process-wide default says otherwise.
  *   "profile_skip" = 1 | 2 | 3 (any time; results become meaningless): measurement hook of bench.py, leaves the self-attention
  *   (bit 0) and / or cross-attention (bit 1) launches out of the captured decode step, so that what a kernel costs the step is
  *   the difference between two timed generates.  0 restores the real step. */
@@ -243,6 +250,8 @@ int32_t amt_decode_linear_fwd(const float* x, const float* w, const float* bias,
  *   caches and attends keys 0..pos; new_kv = 0 attends keys 0..n_keys-1 (cross-attention).  new_kv | 2 (Er given): the
  *   short-context instantiation of the relative-position self-attention, bit-identical to the long one at any length; with it u
  *   may be null: raw is then the finished query (B, H*hd) as amt_attn_decode_fwd takes it, keys 0..*pos_dev or 0..n_keys-1.
+ *   new_kv | 4: the per-lane controlled key stream instead of the scalar-controlled one (bit-identical; see "scalar_key_stream"); with
+ *   it u may be null as well, with or without Er (the plain self- and cross-attention on that stream).
  * amt_decode_gemm_ex_fwd: rows [x (K1 columns) | x2 (K-K1 columns)]; y_low (B, n_low) = act(x . w_low^T + b (+resid)) over the
  *   first K1 columns (all K when x2 is null), y_high (B, n_high) = [x|x2] . w_high^T + b_high.  pro = 1: the staged row is
  *   [relu((x - mu*fold_g)*rstd + fold_c) | LayerNorm(x2)] (statistics of x2's row) and LayerNorm(x2) is y_low's residual.

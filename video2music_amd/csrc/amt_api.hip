@@ -115,10 +115,11 @@ struct amt_handle {
     bool step_short = false;             // set by get_graph while it captures such a graph (eager steps keep the long kernels)
     bool l0_tables = true;               // amt_set_option("layer0_kv_from_tables"): 0 = the attention that carries the sampling head streams layer 0's keys from the cache
     bool gemm_pipe = true;               // amt_set_option("gemm_tile_pipeline"): 0 = the skinny GEMMs of the decode step run the serial tile loop (DecodeGemmParams::serial_loop)
+    bool scalar_stream = true;           // amt_set_option("scalar_key_stream"): 0 = the decode attentions keep the per-lane controlled key stream (AttnDecodeParams::lane_key_stream)
     bool plain_chain = false;            // amt_set_option("decode_chain_plain"), before the first amt_finalize: the 49-launch chain without folded LayerNorms
     bool gen_active = false;
     // graphs keyed by the parameters baked into the captured kernel arguments
-    struct GraphKey { int B, T, P, beam, mcN, mcC, S, nsteps, skip, pad, short_ctx, parity, gemm_pipe, spare; float* logits; };      // (compared bytewise: an even number of ints, no padding)
+    struct GraphKey { int B, T, P, beam, mcN, mcC, S, nsteps, skip, pad, short_ctx, parity, gemm_pipe, spare, key_stream, spare2; float* logits; };      // (compared bytewise: an even number of ints, no padding)
     struct GraphEntry { GraphKey key; hipGraphExec_t exec; hipGraph_t graph; };
     std::vector<GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;    // capture-only stream (the caller's may be the legacy null stream)
@@ -288,7 +289,7 @@ int32_t enqueue_decoder_step_folded(amt_handle* h, hipStream_t s, int step, Step
         const float* Vx = Kx + h->kvx_part;
         AttnDecodeParams a{};
         a.k = Kc; a.v = Vc; a.o = h->ob; a.B = B; a.H = H; a.hd = hd; a.cap = h->kv_rows;
-        a.pos = l == 0 && fused_sp ? fused_sp->pos : pos_slot(h, step); a.Er = L.Er; a.er_len = h->Tcap; a.short_ctx = h->step_short;
+        a.pos = l == 0 && fused_sp ? fused_sp->pos : pos_slot(h, step); a.Er = L.Er; a.er_len = h->Tcap; a.short_ctx = h->step_short; a.lane_key_stream = h->scalar_stream ? 0 : 1;
         if (l == 0 && fused_sp) {
             a.k_new = Kc; a.v_new = Vc; a.new_kv = 1;      // q / k / v of the new position are summed from the projected tables in the kernel
             // ... and, in the long graphs, the keys of the earlier positions too (shapes the kernel does not stage keep the cache stream)
@@ -317,7 +318,7 @@ int32_t enqueue_decoder_step_folded(amt_handle* h, hipStream_t s, int step, Step
         if ((rc = launch_step_gemm(h, g1, s))) return rc;
         PROF_END(2);
         AttnDecodeParams x{};
-        x.k = Kx; x.v = Vx; x.o = h->ob; x.B = B; x.H = H; x.hd = hd; x.cap = h->kx_rows; x.n_keys = h->encS;
+        x.k = Kx; x.v = Vx; x.o = h->ob; x.B = B; x.H = H; x.hd = hd; x.cap = h->kx_rows; x.n_keys = h->encS; x.lane_key_stream = h->scalar_stream ? 0 : 1;
         x.q = h->qraw; x.ldq = d; x.d = d; x.fold_u = h->u1; x.fold_g = L.va; x.fold_c = L.va + d;
         x.fold_lnw = L.n1w; x.fold_lnb = L.n1b; x.xn = h->xb; x.eps = LN_EPS; x.q_scale = qscale;
         if (!(h->skip_mask & 2)) {
@@ -371,7 +372,7 @@ int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, int step, StepProf* p
         // K2: relative-position self-attention over the cache
         AttnDecodeParams a{};
         a.q = h->qb; a.k = Kc; a.v = Vc; a.o = h->ob; a.B = B; a.H = H; a.hd = hd; a.cap = h->kv_rows;
-        a.pos = pos_slot(h, step); a.Er = L.Er; a.er_len = h->Tcap; a.short_ctx = h->step_short;
+        a.pos = pos_slot(h, step); a.Er = L.Er; a.er_len = h->Tcap; a.short_ctx = h->step_short; a.lane_key_stream = h->scalar_stream ? 0 : 1;
         if (!(h->skip_mask & 1)) {
             PROF_BEGIN();
             if ((rc = amt_launch_attn_decode(a, s))) return rc;
@@ -393,7 +394,7 @@ int32_t enqueue_decoder_step(amt_handle* h, hipStream_t s, int step, StepProf* p
         PROF_END(2);
         // K5: cross-attention over the clip's video keys
         AttnDecodeParams x{};
-        x.q = h->qb; x.k = Kx; x.v = Vx; x.o = h->ob; x.B = B; x.H = H; x.hd = hd; x.cap = h->kx_rows; x.n_keys = h->encS;
+        x.q = h->qb; x.k = Kx; x.v = Vx; x.o = h->ob; x.B = B; x.H = H; x.hd = hd; x.cap = h->kx_rows; x.n_keys = h->encS; x.lane_key_stream = h->scalar_stream ? 0 : 1;
         if (!(h->skip_mask & 2)) {
             PROF_BEGIN();
             if ((rc = amt_launch_attn_decode(x, s))) return rc;
@@ -442,7 +443,7 @@ int32_t get_graph(amt_handle* h, int first_pos, int nsteps, float* logits_out, h
     // of keys, every self-attention of the graph is the short-context instantiation (a graph that straddles the limit keeps the long one)
     const bool short_ctx = h->short_attn && first_pos + nsteps <= amt_attn_decode_stride(h->hd);
     amt_handle::GraphKey key{h->genB, h->genT, h->genP, h->beam, h->mcN, h->mcC, h->encS, nsteps, h->skip_mask | (h->fuse_head ? 4 : 0), h->use_unif,
-                             short_ctx ? 1 : 0, first_pos & 1, h->gemm_pipe ? 1 : 0, h->l0_tables ? 1 : 0, logits_out};
+                             short_ctx ? 1 : 0, first_pos & 1, h->gemm_pipe ? 1 : 0, h->l0_tables ? 1 : 0, h->scalar_stream ? 1 : 0, 0, logits_out};
     for (auto& g : h->graphs)
         if (memcmp(&g.key, &key, sizeof(key)) == 0) { *out = g.exec; return 0; }
     hipGraph_t graph;
@@ -749,6 +750,10 @@ extern "C" int32_t amt_finalize(amt_handle* h) {
 // encoder
 // ------------------------------------------------------------------------------------------------
 extern "C" int32_t amt_set_option(amt_handle* h, const char* name, int32_t value) {
+    if (!h && name && strcmp(name, "scalar_key_stream") == 0) {   // no handle: the process-wide default of the operator entry points and the lockstep step
+        amt_attn_decode_scalar_stream(value != 0);
+        return 0;
+    }
     AMT_CHECK_ARG(h && name, "amt_set_option: null argument");
     if (strcmp(name, "chord_embed") == 0) {
         AMT_CHECK_ARG(!h->KVx || h->chord_embed == (value != 0), "amt_set_option: chord_embed must be chosen before the first amt_finalize");
@@ -778,6 +783,10 @@ extern "C" int32_t amt_set_option(amt_handle* h, const char* name, int32_t value
     }
     if (strcmp(name, "layer0_kv_from_tables") == 0) {        // 0: layer 0's self-attention always streams its keys from the K/V cache (A/B and bit-identity tests); part of the graph key
         h->l0_tables = value != 0;
+        return 0;
+    }
+    if (strcmp(name, "scalar_key_stream") == 0) {            // 0: the decode attentions of this handle keep the per-lane controlled key stream (A/B and bit-identity tests); part of the graph key
+        h->scalar_stream = value != 0;
         return 0;
     }
     if (strcmp(name, "profile_skip") == 0) {                 // measurement hook of bench.py: leave a kernel class out of the captured step

@@ -13,6 +13,8 @@
 // and a fixed key count.
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "amt_common.h"
 #include "kernels.h"
 #include "sample_device.h"
@@ -33,8 +35,11 @@ __device__ __forceinline__ float4 ld4_stream(const float* p, bool nt) {
     return ld4(p);
 }
 
-// kb / vb / eb are wave-uniform bases (SGPR pairs); the lane part is a 32-bit element offset, so a load is
-// `global_load_dwordx4 v, v_off, s[base]` with one address VGPR and no 64-bit lane arithmetic
+// The per-lane controlled stream (the SHORT instantiations, the position-independent first batch, and every launch the caller asks
+// the previous stream for): kb / vb / eb are wave-uniform, but the lane part is a 32-bit ELEMENT offset, which the compiler scales in
+// 64 bits, and every load clamps its row -- the ISA is a v_cmp / v_cndmask, a 64-bit shift and two 64-bit adds per load pair and the
+// `off` addressing form.  The scalar-controlled stream below (load_kv_s ...) is the one whose loads are
+// `global_load_dwordx4 v, v_off, s[base]` with one loop-invariant address VGPR.
 // (RS = floats between two rows: HD in the cache, 2 * HD in the head-sliced position table, whose rows are [k | v])
 template <int HD, bool NT, int RS = HD>
 __device__ __forceinline__ void load_kv(Batch<HD>& bt, const float* kb, const float* vb, int j0, int sub, int c4, int n_keys) {
@@ -73,7 +78,9 @@ struct TabCtx {
     int c4;
 };
 
-template <int HD, bool RPR, bool TAB = false>
+// GUARD: 0 = every key is checked against n_keys lane by lane under a branch (the per-lane controlled stream), 1 = none is (an interior
+// batch of the scalar stream: every key of every group lies below n_keys), 2 = every key is, by selects (the scalar stream's last batch)
+template <int HD, bool RPR, bool TAB = false, int GUARD = 0>
 __device__ __forceinline__ void consume_batch(const Batch<HD>& bt, const float4 q4, int j0, int sub, int n_keys,
                                               float& m, float& l, float4& o, const TabCtx& tc = TabCtx{}) {
     constexpr int LPK = HD / 4, KPW = 64 / LPK;
@@ -85,7 +92,7 @@ __device__ __forceinline__ void consume_batch(const Batch<HD>& bt, const float4 
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
             const int j = j0 + u * NW * KPW + sub;
-            id[u] = tc.ids[j < n_keys ? j : 0];
+            id[u] = tc.ids[GUARD == 1 || j < n_keys ? j : 0];
         }
         float4 rk[UNROLL], ak[UNROLL], rv[UNROLL], av[UNROLL];
 #pragma unroll
@@ -108,7 +115,18 @@ __device__ __forceinline__ void consume_batch(const Batch<HD>& bt, const float4 
         if (RPR) { k4.x += bt.e[u].x; k4.y += bt.e[u].y; k4.z += bt.e[u].z; k4.w += bt.e[u].w; }
         float s = q4.x * k4.x + q4.y * k4.y + q4.z * k4.z + q4.w * k4.w;
         s = group_sum<LPK>(s);
-        if (j0 + u * NW * KPW + sub < n_keys) {
+        if constexpr (GUARD == 2) {
+            // selects, not a branch: the scalar stream's tail has no lane-divergent control flow.  The same arithmetic on the lanes
+            // that take the key, the state of the others is kept
+            const bool take = j0 + u * NW * KPW + sub < n_keys;
+            const float4 vv = TAB ? v4 : bt.v[u];
+            const float mn = fmaxf(m, s);
+            const float alpha = __expf(m - mn), pj = __expf(s - mn);
+            l = take ? l * alpha + pj : l;
+            o.x = take ? o.x * alpha + pj * vv.x : o.x; o.y = take ? o.y * alpha + pj * vv.y : o.y;
+            o.z = take ? o.z * alpha + pj * vv.z : o.z; o.w = take ? o.w * alpha + pj * vv.w : o.w;
+            m = take ? mn : m;
+        } else if (GUARD == 1 || j0 + u * NW * KPW + sub < n_keys) {
             const float mn = fmaxf(m, s);
             const float alpha = __expf(m - mn), pj = __expf(s - mn);
             l = l * alpha + pj;
@@ -121,6 +139,9 @@ __device__ __forceinline__ void consume_batch(const Batch<HD>& bt, const float4 
             }
             m = mn;
         }
+        // (the scalar stream's consumers have no branch between two groups: without a fence the scheduler interleaves the four
+        // chains, and the hd = 64 kernels with Er rows, which sit at their 128-VGPR bound, spill inside the loop)
+        if (GUARD != 0 && u + 1 < UNROLL) __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -144,6 +165,101 @@ __device__ __forceinline__ void stream_keys(Batch<HD>& cur, Batch<HD>& nxt, cons
         __builtin_amdgcn_sched_barrier(0);
         consume_batch<HD, RPR, TAB>(nxt, q4, j0, sub, n_keys, m, l, o, tc);
         j0 += STRIDE;
+    }
+}
+
+// ---- the scalar-controlled key stream (SCAL instantiations) ----
+// The wave index is a scalar (readfirstlane), so the wave knows as a scalar how many batches hold at least one of its keys (nb), and
+// the stream's control is SALU compares and branches.  K, V and the Er rows are read through buffer descriptors built from the
+// wave-uniform bases kb / vb / eb: a load is `buffer_load_dwordx4 v, v_off, s[rsrc], s_off offen` -- the batch and group part of the
+// address is the scalar offset (SALU adds), the lane part (koff / eoff, bytes) one loop-invariant VGPR.  Interior batches -- all but
+// the wave's last -- hold only keys below n_keys: the loop consumes them without a guard and requests the one behind the batch in
+// hand without a clamp.  A batch that may be the last one is requested with its rows clamped lane by lane (32-bit: to the batch's
+// first row, which is live) and, as the last one, consumed with every key guarded by selects.  Nothing is requested behind a wave's
+// last batch: no wave ends its stream waiting for rows nobody consumes.  Every wait count is exact: the loop keeps the batch in hand
+// in flight at both issue points, the two ends (one batch left, two left) are straight-line code behind one scalar branch.  Which
+// keys a lane group consumes, and in which order, is the per-lane controlled stream's.
+using rsrc_t = __amdgpu_buffer_rsrc_t;
+__device__ __forceinline__ rsrc_t make_rsrc(const float* base, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
+}
+template <bool NT>
+__device__ __forceinline__ float4 ld4_buf(rsrc_t r, unsigned voff, unsigned soff) {
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const u4 t = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, NT ? 2 : 0);      // (cache policy 2 = nt, as the non-temporal global load)
+    const f4 f = __builtin_bit_cast(f4, t);
+    return make_float4(f.x, f.y, f.z, f.w);
+}
+
+struct StreamS {                 // what the scalar stream carries besides the descriptors and the two register sets
+    unsigned kso, eso;           // byte offset of the first row of the batch in hand from kb / vb and from eb (wave-uniform)
+    unsigned koff, eoff, c4b;    // the lane's byte offsets inside a key group: (sub * RS + c4) * 4, (sub * HD + c4) * 4, c4 * 4
+    int j0, sub, n_keys;         // first key of the batch in hand for this wave (scalar), the lane's key inside a group
+};
+
+// requests the batch `ahead` batches behind the one in hand.  CLAMP: the batch may be the wave's last -- a lane whose key lies past the
+// end reads the batch's first row instead (the group part of the address then sits in the lane offset: a dead group's rows may lie
+// outside the descriptor)
+template <int HD, bool RPR, bool NT, int RS, bool CLAMP>
+__device__ __forceinline__ void load_batch_s(Batch<HD>& bt, rsrc_t kr, rsrc_t vr, rsrc_t er, const StreamS& a, int ahead) {
+    constexpr int GRP = NW * (64 / (HD / 4)), STRIDE = GRP * UNROLL;        // keys between two groups of a wave, keys per batch
+    const unsigned kso = a.kso + (unsigned)(ahead * STRIDE * RS * 4), eso = a.eso + (unsigned)(ahead * STRIDE * HD * 4);
+    const int j0 = a.j0 + ahead * STRIDE;
+    // fenced on both sides: behind the loads no consumer's wait moves in front of them, and in front of them the requests of a
+    // register set do not move up into the consumer of the batch it held before
+    __builtin_amdgcn_sched_barrier(0);
+    if (CLAMP) {
+        // group by group, fenced: one clamped lane offset is live at a time (all four at once cost the hd = 64 kernels of FOLD 0 / 2,
+        // which sit at their 128-VGPR bound, spills)
+        // the lane's key inside a group and its column offset are re-derived from the one lane offset the loop keeps (made opaque
+        // here, or the compiler hoists them out of the loop and keeps three VGPRs live where one does)
+        unsigned ko = a.koff;
+        asm volatile("" : "+v"(ko));
+        const int sub = (int)(ko / (unsigned)(RS * 4));
+        const unsigned c4b = ko % (unsigned)(RS * 4), eo = (unsigned)sub * (HD * 4) + c4b;
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const bool in = j0 + u * GRP + sub < a.n_keys;
+            const unsigned off = in ? ko + (unsigned)(u * GRP * RS * 4) : c4b;
+            bt.k[u] = ld4_buf<NT>(kr, off, kso);
+            bt.v[u] = ld4_buf<NT>(vr, off, kso);
+            if (RPR) bt.e[u] = ld4_buf<false>(er, RS == HD ? off : (in ? eo + (unsigned)(u * GRP * HD * 4) : c4b), eso);
+            if (u + 1 < UNROLL) __builtin_amdgcn_sched_barrier(0);
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            bt.k[u] = ld4_buf<NT>(kr, a.koff, kso + (unsigned)(u * GRP * RS * 4));
+            bt.v[u] = ld4_buf<NT>(vr, a.koff, kso + (unsigned)(u * GRP * RS * 4));
+        }
+        if (RPR) {
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) bt.e[u] = ld4_buf<false>(er, a.eoff, eso + (unsigned)(u * GRP * HD * 4));
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// `cur` holds the requested batch `a` points at, `rem` >= 0 batches are left with it included
+template <int HD, bool RPR, bool NT, bool TAB = false>
+__device__ __forceinline__ void stream_keys_s(Batch<HD>& cur, Batch<HD>& nxt, rsrc_t kr, rsrc_t vr, rsrc_t er, StreamS a, int rem,
+                                              const float4 q4, float& m, float& l, float4& o, const TabCtx& tc = TabCtx{}) {
+    constexpr int STRIDE = NW * (64 / (HD / 4)) * UNROLL, RS = TAB ? 2 * HD : HD;
+    while (rem >= 3) {           // two batches requested (the second may be the last), two interior ones consumed
+        load_batch_s<HD, RPR, NT, RS, false>(nxt, kr, vr, er, a, 1);
+        consume_batch<HD, RPR, TAB, 1>(cur, q4, a.j0, a.sub, a.n_keys, m, l, o, tc);
+        load_batch_s<HD, RPR, NT, RS, true>(cur, kr, vr, er, a, 2);
+        consume_batch<HD, RPR, TAB, 1>(nxt, q4, a.j0 + STRIDE, a.sub, a.n_keys, m, l, o, tc);
+        a.kso += 2 * STRIDE * RS * 4; a.eso += 2 * STRIDE * HD * 4; a.j0 += 2 * STRIDE;
+        rem -= 2;
+    }
+    if (rem == 2) {
+        load_batch_s<HD, RPR, NT, RS, true>(nxt, kr, vr, er, a, 1);
+        consume_batch<HD, RPR, TAB, 1>(cur, q4, a.j0, a.sub, a.n_keys, m, l, o, tc);
+        consume_batch<HD, RPR, TAB, 2>(nxt, q4, a.j0 + STRIDE, a.sub, a.n_keys, m, l, o, tc);
+    } else if (rem == 1) {
+        consume_batch<HD, RPR, TAB, 2>(cur, q4, a.j0, a.sub, a.n_keys, m, l, o, tc);
     }
 }
 
@@ -177,9 +293,12 @@ constexpr int UCH_MAX = 4;       // folded prologue: the pre-LN row has at most 
 // not a run-time branch: one guarded load in the stream turns the later waits into vmcnt(0).  The per-clip HBM stream becomes one
 // [t][2 hd] run per head that the 32 clips of the head share in L2.  Row t of the cache is still written: the graph's first step, the
 // short graphs, the eager path and amt_kv_cache_io keep reading the cache.
-template <int HD, bool RPR, bool NT, int FOLD, int UCH, bool SHORT = false, bool TAB = false>
+// SCAL: the scalar-controlled key stream (stream_keys_s) behind the first batch instead of the per-lane controlled one (stream_keys).
+// A template flag, not a run-time branch inside the stream; the previous stream stays selectable (AttnDecodeParams::lane_key_stream).
+template <int HD, bool RPR, bool NT, int FOLD, int UCH, bool SHORT = false, bool TAB = false, bool SCAL = false>
 __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, const SampleParams* sp) {
     static_assert(!SHORT || (RPR && (FOLD == 0 || FOLD == 2 || FOLD == 5)), "the short-context order exists for the base model's self-attention");
+    static_assert(!(SCAL && SHORT), "the short-context order requests one batch: there is no stream to control");
     static_assert(!TAB || (FOLD == 5 && RPR && !SHORT && !NT), "the table-sourced stream exists for the long layer-0 launch behind the sampling head");
 #ifdef AMT_STAMPS
     unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -192,7 +311,8 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
     __shared__ __attribute__((aligned(16))) float sm_o[NW][HD];
 
     const int h = blockIdx.x, b = blockIdx.y;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // (SCAL: the compiler cannot see that threadIdx.x >> 6 is wave-uniform; through readfirstlane the stream's control is SALU)
+    const int lane = threadIdx.x & 63, wave = SCAL ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     const int c = lane % LPK, sub = lane / LPK;
     const int c4 = c * 4;
     constexpr int RS = TAB ? 2 * HD : HD;
@@ -422,6 +542,12 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
         st4(p.k_new + (((size_t)b * p.H + h) * p.cap + t) * HD + c * 4, kn4);
         st4(p.v_new + (((size_t)b * p.H + h) * p.cap + t) * HD + c * 4, vn4);
     }
+    // SCAL: the own key / value wait in LDS, not in eight VGPRs of every wave, while the keys stream (wave 0 alone reads them back;
+    // under the 128-VGPR bound of hd = 64 the registers were spilled to scratch around the stream instead)
+    __shared__ __attribute__((aligned(16))) float sm_own[SCAL && fresh ? 2 : 1][SCAL && fresh ? HD : 4];
+    if constexpr (SCAL && fresh) {
+        if (wave == 0 && sub == 0) { st4(&sm_own[0][c4], kn4); st4(&sm_own[1][c4], vn4); }
+    }
     if (RPR && !fresh) load_er<HD>(b0, eb, j0, sub, c4, n_keys);
     // (fresh variants requested the first batch's Er rows inside their prologue)
     float m = -INFINITY, l = 0.f;
@@ -435,6 +561,34 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
             load_batch<HD, RPR, NT>(b0, kb, vb, eb, j0, sub, c4, n_keys);
             consume_batch<HD, RPR>(b0, q4, j0, sub, n_keys, m, l, o);
             j0 += STRIDE;
+        }
+    } else if constexpr (SCAL) {
+        constexpr int GRP = NW * KPW;
+        // per wave, as scalars: live key groups, batches that hold one.  The trip count is bounded by
+        // the cache (a replay too many of FOLD 5 stays harmless)
+        const int nk = min(n_keys, p.cap);
+        const int ng = nk > j0 ? (nk - j0 + GRP - 1) / GRP : 0;
+        const int nb = (ng + UNROLL - 1) / UNROLL;
+        // descriptors over the head's rows: the table's tab_T rows (v at + HD inside a row) or the cache's cap, and Er rows of keys 0 .. nk-1
+        const int kv_rows = TAB ? sp->tab_T : p.cap;
+        const rsrc_t kr = make_rsrc(kb, kv_rows * RS * 4), vr = make_rsrc(vb, (kv_rows * RS - (TAB ? HD : 0)) * 4);
+        const rsrc_t er = RPR ? make_rsrc(eb, nk * HD * 4) : kr;
+        StreamS a;
+        a.kso = (unsigned)(j0 * RS * 4); a.eso = (unsigned)(j0 * HD * 4);
+        a.koff = (unsigned)(sub * RS + c4) * 4u; a.eoff = (unsigned)(sub * HD + c4) * 4u; a.c4b = (unsigned)c4 * 4u;
+        a.j0 = j0; a.sub = sub; a.n_keys = nk;
+        if constexpr (FOLD == 5) {
+            // both batches are in flight since the prologue (the second one clamped lane by lane: requested before the query exists,
+            // it is nobody's tail)
+            if (nb >= 2) {
+                consume_batch<HD, RPR, TAB, 1>(b0, q4, j0, sub, nk, m, l, o, tc);
+                a.kso += STRIDE * RS * 4; a.eso += STRIDE * HD * 4; a.j0 += STRIDE;
+                stream_keys_s<HD, RPR, NT, TAB>(b1, b0, kr, vr, er, a, nb - 1, q4, m, l, o, tc);
+            } else if (nb == 1) {
+                consume_batch<HD, RPR, TAB, 2>(b0, q4, j0, sub, nk, m, l, o, tc);
+            }
+        } else {
+            stream_keys_s<HD, RPR, NT, TAB>(b0, b1, kr, vr, er, a, nb, q4, m, l, o, tc);
         }
     } else if constexpr (FOLD == 5) {
         // both batches are in flight since the prologue
@@ -454,6 +608,10 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
         stream_keys<HD, RPR, NT>(b0, b1, kb, vb, eb, q4, j0, sub, c4, n_keys, m, l, o);
     }
     if (fresh && wave == 0) {                        // the current position's own key (relative distance 0)
+        if constexpr (SCAL) {
+            asm volatile("" ::: "memory");           // (a real LDS read: not the stored registers forwarded)
+            kn4 = ld4(&sm_own[0][c4]); vn4 = ld4(&sm_own[1][c4]);
+        }
         float4 k4 = kn4;
         if (RPR) {
             if (!own_er) e_own = ld4(p.Er + (size_t)(p.er_len - 1) * HD + c * 4);
@@ -528,26 +686,33 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecodeParams& p, cons
     }
 }
 
-template <int HD, bool RPR, bool NT, int FOLD, int UCH, bool SHORT = false>
+template <int HD, bool RPR, bool NT, int FOLD, int UCH, bool SHORT = false, bool SCAL = false>
 // hd = 64 at d_model <= 512 (the benchmark's shape) is held at 128 VGPRs = two workgroups per CU: it fits without spilling and a
 // launch of more than 256 workgroups (more than 32 clips per chain) then runs in one round (+6-7 % tokens/s at 64-256 clips); the
 // other shapes keep the compiler's own choice (the same bound makes the hd = 16 / 32 relative-position variants spill)
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((HD == 64 && UCH == 2) ? 4 : 1, (HD == 64 && UCH == 2) ? 4 : 8)))
 void attn_decode_kernel(AttnDecodeParams p) {
-    attn_decode_body<HD, RPR, NT, FOLD, UCH, SHORT>(p, nullptr);
+    attn_decode_body<HD, RPR, NT, FOLD, UCH, SHORT, false, SCAL>(p, nullptr);
 }
 
 // layer 0 of the base model's folded chain with the previous step's decision in front (FOLD 5).  No 128-VGPR bound here: with the
 // first K/V batch in flight the decision and the twelve table rows need more (the bound spilled 36 registers); at 32 clips the launch is
 // one workgroup per CU either way, above that this ONE launch of the step's six self-attentions takes two rounds
-template <int HD, bool RPR, bool NT, int UCH, bool SHORT = false, bool TAB = false>
+template <int HD, bool RPR, bool NT, int UCH, bool SHORT = false, bool TAB = false, bool SCAL = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_sample_kernel(AttnDecodeParams p, SampleParams sp) {
-    attn_decode_body<HD, RPR, NT, 5, UCH, SHORT, TAB>(p, &sp);
+    attn_decode_body<HD, RPR, NT, 5, UCH, SHORT, TAB, SCAL>(p, &sp);
 }
+
+// the process-wide choice of the key stream for launches that do not ask for the per-lane controlled one themselves
+// (amt_set_option with a null handle; the operator entry points and the lockstep step have no handle to carry an option)
+std::atomic<int> g_scalar_key_stream{1};
+
+inline bool scalar_stream(const AttnDecodeParams& p) { return !p.lane_key_stream && g_scalar_key_stream.load(std::memory_order_relaxed) != 0; }
 
 template <int HD, int FOLD, int UCH>
 void launch_decode_u(const AttnDecodeParams& p, hipStream_t stream) {
     dim3 grid(p.H, p.B);
+    const bool scal = scalar_stream(p);
     // K/V are streamed once per launch and exceed the 256 MiB Infinity Cache per step: non-temporal loads keep
     // the step's re-used bytes (weights, activations) resident instead (measured +8 % tokens/s at
     // config 2).  AmtTuning::nt_mask: bit 0 = self-attention, bit 1 = cross-attention.
@@ -561,9 +726,21 @@ void launch_decode_u(const AttnDecodeParams& p, hipStream_t stream) {
             }
         }
         if constexpr (FOLD != 4) {               // (the rotary self-attention has no relative-position table: checked by the launcher)
-            if (nt_mask & 1) hipLaunchKernelGGL((attn_decode_kernel<HD, true, true, FOLD, UCH>), grid, dim3(NW * 64), 0, stream, p);
-            else hipLaunchKernelGGL((attn_decode_kernel<HD, true, false, FOLD, UCH>), grid, dim3(NW * 64), 0, stream, p);
+            // the relative-position kernels of hd = 64 without an own key (the plain-query self-attention, and FOLD 1 / 3 with a table,
+            // which no model launches) stay on the per-lane controlled stream: with Er rows and no own key to park in LDS, the scalar
+            // stream's loop spills under the 128-VGPR bound (ISA: 8 VGPRs, 36 bytes of scratch, inside the loop)
+            constexpr bool SCAL_FITS = !(HD == 64 && UCH == 2 && (FOLD == 0 || FOLD == 1 || FOLD == 3));
+            if (SCAL_FITS && scal) {
+                if (nt_mask & 1) hipLaunchKernelGGL((attn_decode_kernel<HD, true, true, FOLD, UCH, false, SCAL_FITS>), grid, dim3(NW * 64), 0, stream, p);
+                else hipLaunchKernelGGL((attn_decode_kernel<HD, true, false, FOLD, UCH, false, SCAL_FITS>), grid, dim3(NW * 64), 0, stream, p);
+            } else {
+                if (nt_mask & 1) hipLaunchKernelGGL((attn_decode_kernel<HD, true, true, FOLD, UCH>), grid, dim3(NW * 64), 0, stream, p);
+                else hipLaunchKernelGGL((attn_decode_kernel<HD, true, false, FOLD, UCH>), grid, dim3(NW * 64), 0, stream, p);
+            }
         }
+    } else if (scal) {
+        if (nt_mask & 2) hipLaunchKernelGGL((attn_decode_kernel<HD, false, true, FOLD, UCH, false, true>), grid, dim3(NW * 64), 0, stream, p);
+        else hipLaunchKernelGGL((attn_decode_kernel<HD, false, false, FOLD, UCH, false, true>), grid, dim3(NW * 64), 0, stream, p);
     } else {
         if (nt_mask & 2) hipLaunchKernelGGL((attn_decode_kernel<HD, false, true, FOLD, UCH>), grid, dim3(NW * 64), 0, stream, p);
         else hipLaunchKernelGGL((attn_decode_kernel<HD, false, false, FOLD, UCH>), grid, dim3(NW * 64), 0, stream, p);
@@ -580,31 +757,38 @@ void launch_decode(const AttnDecodeParams& p, hipStream_t stream) {
 template <int HD>
 void launch_decode_sample(const AttnDecodeParams& p, const SampleParams& sp, hipStream_t stream) {
     dim3 grid(p.H, p.B);
-    const bool nt = (amt_tuning().nt_mask & 1) != 0;
-#define AMT_LAUNCH_DS(RPR, NTV, UCHV) hipLaunchKernelGGL((attn_decode_sample_kernel<HD, RPR, NTV, UCHV>), grid, dim3(NW * 64), 0, stream, p, sp)
+    const bool nt = (amt_tuning().nt_mask & 1) != 0, scal = scalar_stream(p);
+#define AMT_LAUNCH_DS(RPR, NTV, UCHV) do { \
+        if (scal) hipLaunchKernelGGL((attn_decode_sample_kernel<HD, RPR, NTV, UCHV, false, false, true>), grid, dim3(NW * 64), 0, stream, p, sp); \
+        else hipLaunchKernelGGL((attn_decode_sample_kernel<HD, RPR, NTV, UCHV>), grid, dim3(NW * 64), 0, stream, p, sp); } while (0)
+#define AMT_LAUNCH_DST(UCHV) do { \
+        if (scal) hipLaunchKernelGGL((attn_decode_sample_kernel<HD, true, false, UCHV, false, true, true>), grid, dim3(NW * 64), lds, stream, p, sp); \
+        else hipLaunchKernelGGL((attn_decode_sample_kernel<HD, true, false, UCHV, false, true>), grid, dim3(NW * 64), lds, stream, p, sp); } while (0)
 #define AMT_LAUNCH_DSS(NTV, UCHV) hipLaunchKernelGGL((attn_decode_sample_kernel<HD, true, NTV, UCHV, true>), grid, dim3(NW * 64), 0, stream, p, sp)
     if (p.Er && p.l0_tables && !p.short_ctx) {
         // shared table rows are meant to stay in L2: plain loads whatever nt_mask says.  LDS: the head's TR / TA rows, then the ids
         const size_t lds = (size_t)(sp.n_root + 16) * 2 * HD * sizeof(float) + (size_t)p.cap * 2;
-        if (sp.d <= 512) hipLaunchKernelGGL((attn_decode_sample_kernel<HD, true, false, 2, false, true>), grid, dim3(NW * 64), lds, stream, p, sp);
-        else hipLaunchKernelGGL((attn_decode_sample_kernel<HD, true, false, 4, false, true>), grid, dim3(NW * 64), lds, stream, p, sp);
+        if (sp.d <= 512) AMT_LAUNCH_DST(2); else AMT_LAUNCH_DST(4);
     } else if (p.Er && p.short_ctx) {
         if (sp.d <= 512) { if (nt) AMT_LAUNCH_DSS(true, 2); else AMT_LAUNCH_DSS(false, 2); }
         else { if (nt) AMT_LAUNCH_DSS(true, 4); else AMT_LAUNCH_DSS(false, 4); }
     } else if (sp.d <= 512) {
         if (p.Er) { if (nt) AMT_LAUNCH_DS(true, true, 2); else AMT_LAUNCH_DS(true, false, 2); }
-        else { if (nt) AMT_LAUNCH_DS(false, true, 2); else AMT_LAUNCH_DS(false, false, 2); }
+        else if (nt) AMT_LAUNCH_DS(false, true, 2); else AMT_LAUNCH_DS(false, false, 2);
     } else {
         if (p.Er) { if (nt) AMT_LAUNCH_DS(true, true, 4); else AMT_LAUNCH_DS(true, false, 4); }
-        else { if (nt) AMT_LAUNCH_DS(false, true, 4); else AMT_LAUNCH_DS(false, false, 4); }
+        else if (nt) AMT_LAUNCH_DS(false, true, 4); else AMT_LAUNCH_DS(false, false, 4);
     }
 #undef AMT_LAUNCH_DS
+#undef AMT_LAUNCH_DST
 #undef AMT_LAUNCH_DSS
 }
 
 }  // namespace
 
 // keys one workgroup takes per batch: the limit below which a step qualifies for the short-context instantiations
+void amt_attn_decode_scalar_stream(int on) { g_scalar_key_stream.store(on ? 1 : 0, std::memory_order_relaxed); }
+
 int amt_attn_decode_stride(int hd) { return NW * (64 / (hd / 4)) * UNROLL; }
 
 // the table-sourced layer-0 stream stages at most TAB_ROWS_MAX table rows and TAB_ID_IT * STAGE_T ids per workgroup (35 KB of LDS at most)

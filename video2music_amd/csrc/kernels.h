@@ -116,8 +116,14 @@ struct AttnDecodeParams {
     // (SampleParams::tab_p0 / tab_ra0 and the id sequences) instead of read back from the cache -- the same bits, see table_sum4;
     // the caller sets it only where amt_attn_decode_tables_fit() holds
     int l0_tables;
+    // 1 = the per-lane controlled key stream behind the first batch (every load clamped, every key guarded, one batch requested past
+    // the end) instead of the scalar-controlled one (attn_decode.hip, SCAL).  The same bits; kept for A/B runs and bit-identity
+    // tests.  The short-context instantiations request one batch and have no stream to choose
+    int lane_key_stream;
 };
 int32_t amt_launch_attn_decode(const AttnDecodeParams& p, hipStream_t stream);
+// process-wide default of launches whose lane_key_stream is 0: 1 (initial) = the scalar-controlled stream, 0 = the per-lane controlled one
+void amt_attn_decode_scalar_stream(int on);
 int amt_attn_decode_stride(int hd);
 // whether the table-sourced layer-0 key stream (AttnDecodeParams::l0_tables) takes this shape: ra_rows = rows of TR and TA together
 bool amt_attn_decode_tables_fit(int hd, int cap, int ra_rows);

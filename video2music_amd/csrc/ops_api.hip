@@ -181,21 +181,23 @@ extern "C" int32_t amt_attn_decode_fold_fwd(const float* raw, int32_t ldq, float
                                             float eps, float q_scale, void* stream) {
     // new_kv bit 1: the short-context instantiation of the relative-position self-attention (AttnDecodeParams::short_ctx); with it u may
     // be null: raw is then the finished query (B, H*hd), as amt_attn_decode_fwd takes it, and the key count comes from pos_dev / n_keys
-    const int short_ctx = (new_kv >> 1) & 1;
+    // new_kv bit 2: the per-lane controlled key stream (AttnDecodeParams::lane_key_stream) instead of the scalar-controlled one; with it
+    // u may be null too (the finished query, with or without Er: the plain self- and cross-attention on the previous stream)
+    const int short_ctx = (new_kv >> 1) & 1, lane_stream = (new_kv >> 2) & 1;
     new_kv &= 1;
     AMT_CHECK_ARG(!short_ctx || Er, "amt_attn_decode_fold_fwd: the short-context kernel is a relative-position self-attention");
     AMT_CHECK_ARG(pos_dev || (!new_kv && n_keys > 0 && n_keys <= cap), "amt_attn_decode_fold_fwd: need a device position or a key count");
-    if (short_ctx && !u) {
+    if ((short_ctx || lane_stream) && !u) {
         AMT_CHECK_ARG(raw && kcache && vcache && o && !new_kv, "amt_attn_decode_fold_fwd: null pointer");
         AttnDecodeParams a{};
         a.q = raw; a.k = kcache; a.v = vcache; a.o = o; a.B = B; a.H = H; a.hd = hd; a.cap = cap;
-        a.pos = (const int*)pos_dev; a.n_keys = n_keys; a.Er = Er; a.er_len = er_len; a.short_ctx = 1;
+        a.pos = (const int*)pos_dev; a.n_keys = n_keys; a.Er = Er; a.er_len = er_len; a.short_ctx = short_ctx; a.lane_key_stream = lane_stream;
         return amt_launch_attn_decode(a, (hipStream_t)stream);
     }
     AMT_CHECK_ARG(raw && kcache && vcache && u && fold_g && fold_c && o, "amt_attn_decode_fold_fwd: null pointer");
     AttnDecodeParams a{};
     a.q = raw; a.ldq = ldq; a.k = kcache; a.v = vcache; a.o = o; a.B = B; a.H = H; a.hd = hd; a.cap = cap; a.d = H * hd;
-    a.pos = (const int*)pos_dev; a.n_keys = n_keys; a.Er = Er; a.er_len = er_len; a.short_ctx = short_ctx;
+    a.pos = (const int*)pos_dev; a.n_keys = n_keys; a.Er = Er; a.er_len = er_len; a.short_ctx = short_ctx; a.lane_key_stream = lane_stream;
     a.fold_u = u; a.fold_g = fold_g; a.fold_c = fold_c; a.fold_lnw = ln_w; a.fold_lnb = ln_b; a.xn = xn_out;
     a.new_kv = new_kv; a.k_new = kcache; a.v_new = vcache; a.eps = eps; a.q_scale = q_scale;
     return amt_launch_attn_decode(a, (hipStream_t)stream);
