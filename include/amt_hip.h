@@ -37,13 +37,15 @@
 #define AMT_HIP_H
 #include <stdint.h>
 
-#define AMT_ABI_VERSION 7    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
+#define AMT_ABI_VERSION 8    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
                                 3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights;
                                 4: amt_chord_metrics_fwd;
                                 5: amt_reg_metrics_fwd;
                                 6: amt_rnn_seq_train_fwd, amt_rnn_seq_bwd, amt_reg_loss_fwd_bwd;
                                 7: amt_attn_train_fwd, amt_attn_bwd, amt_attn_bwd_ws_floats, amt_layernorm_bwd, amt_chord_loss_fwd_bwd,
-                                   amt_chord_loss_ws_floats */
+                                   amt_chord_loss_ws_floats;
+                                8: amt_selective_scan_train_fwd, amt_selective_scan_bwd, amt_selective_scan_bwd_ws_floats,
+                                   amt_dwconv1d_silu_bwd, amt_dwconv1d_silu_bwd_ws_floats */
 
 #ifdef __cplusplus
 extern "C" {
@@ -462,6 +464,36 @@ int32_t amt_selective_scan_fwd(const float* x, int32_t ldx, const float* delta_r
                                const float* A_log, const float* Bm, const float* Cm, int32_t ld_bc, const float* D,
                                const float* z, int32_t ldz, float* y, int32_t ldy, int32_t B, int32_t L, int32_t ED,
                                int32_t N, int32_t version, int32_t reverse, void* stream);
+/* ---- training the Mamba heads ('bimamba+', 'bimamba'): the two kernels above with what their backward needs, and the backward.
+ * d_state N = 16 only (other values are refused with the reason).  No floating-point atomics: the same inputs give the same bits. ---- */
+/* amt_selective_scan_fwd (y: the same bits) that also writes y_pre (B*L, ld_ypre), the un-gated y_t = h_t . C_t + D x_t, and
+ * h_chunks [B][ceil(L / 32)][ED][N], the state at the start of every 32-step chunk in the order the scan walks them (reverse = 1:
+ * from the last position). */
+int32_t amt_selective_scan_train_fwd(const float* x, int32_t ldx, const float* delta_raw, int32_t ld_delta, const float* dt_bias,
+                                     const float* A_log, const float* Bm, const float* Cm, int32_t ld_bc, const float* D,
+                                     const float* z, int32_t ldz, float* y, int32_t ldy, float* y_pre, int32_t ld_ypre,
+                                     float* h_chunks, int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse,
+                                     void* stream);
+/* Backward of the scan and its gate from dout (B*L, ld_dout), the forward's inputs, y_pre and h_chunks: the states inside a chunk
+ * are recomputed from its checkpoint, the chunks walked from the last to the first.  Writes dx, ddraw (the gradient of delta_raw;
+ * its column sums are the gradient of dt_bias), dz (each B*L x ED with its own row stride), dBm / dCm (B*L x N, row stride ld_dbc:
+ * slices of the x_proj output's gradient), dA_log (ED, N) and dD (ED).  ws: amt_selective_scan_bwd_ws_floats(B, L, ED, N) floats --
+ * ceil(ED / 16) per-block copies of dB | dC (B*L x 2N each) and per-clip partials of dA and dD, summed in index order by a second
+ * launch. */
+int64_t amt_selective_scan_bwd_ws_floats(int32_t B, int32_t L, int32_t ED, int32_t N);
+int32_t amt_selective_scan_bwd(const float* dout, int32_t ld_dout, const float* x, int32_t ldx, const float* delta_raw,
+                               int32_t ld_delta, const float* dt_bias, const float* A_log, const float* Bm, const float* Cm,
+                               int32_t ld_bc, const float* D, const float* z, int32_t ldz, const float* y_pre, int32_t ld_ypre,
+                               const float* h_chunks, float* dx, int32_t lddx, float* ddraw, int32_t ld_ddraw, float* dz,
+                               int32_t lddz, float* dBm, float* dCm, int32_t ld_dbc, float* dA_log, float* dD, float* ws,
+                               int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse, void* stream);
+/* Backward of amt_dwconv1d_silu_fwd from dy (B*L, lddy) and the forward's inputs (the pre-activation is formed again): dx (B*L, C
+ * columns, row stride lddx), dw (C, K), dbias (C; null exactly when bias is).  K <= 8.  ws: amt_dwconv1d_silu_bwd_ws_floats floats
+ * (the pre-activation's gradient and per-64-row partials of dw | dbias, summed in index order). */
+int64_t amt_dwconv1d_silu_bwd_ws_floats(int32_t B, int32_t L, int32_t C, int32_t K);
+int32_t amt_dwconv1d_silu_bwd(const float* dy, int32_t lddy, const float* x, int32_t ldx, const float* w, const float* bias,
+                              float* dx, int32_t lddx, float* dw, float* dbias, float* ws, int32_t B, int32_t L, int32_t C,
+                              int32_t K, int32_t reverse, void* stream);
 /* out[row] = [a[row][0:da] | b[row][0:db] | 0 ...] (ld_out columns): cat(semantic, emotion) of get_feature
  * (video_regression.py:199-216), zero-padded to the GEMM's K step. */
 int32_t amt_concat2_fwd(const float* a, int32_t da, const float* b, int32_t db, float* out, int32_t rows, int32_t ld_out,

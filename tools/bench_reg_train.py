@@ -3,6 +3,8 @@
 
     python tools/bench_reg_train.py --which ours            # the project's step alone
     python tools/bench_reg_train.py --which both            # then, alternating with it, the comparison
+    python tools/bench_reg_train.py --which ours --regModel bimamba+      # any head whose backward is built; the comparison stack
+                                                                          # below is the recurrent heads' only
 
 The comparison is the way the reference itself would run on this GPU: torch's own nn.Linear / nn.LSTM modules and autograd on the
 device, built from the same state dict, the reference's loss expressions, the same Adam.  Method: device events around --steps
@@ -64,6 +66,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
+    if a.which == "both" and "mamba" in a.regModel:
+        ap.error("--which both compares against torch's nn.LSTM / nn.GRU: use --which ours for a Mamba head")
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     B, S, F = a.batch, a.seq, 774

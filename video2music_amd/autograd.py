@@ -1,11 +1,14 @@
 """`torch.autograd.Function`s over the library calls: what `VideoRegression` is built from in the training state
-(regModel 'lstm' / 'bilstm' / 'gru' / 'bigru'), so that `loss.backward()` and any torch optimiser work on the module's own parameters.
+(regModel 'lstm' / 'bilstm' / 'gru' / 'bigru' / 'bimamba+' / 'bimamba'), so that `loss.backward()` and any torch optimiser work on the
+module's own parameters.
 
-    LinearFn          y = act(x w^T + b), act 0 none / 1 ReLU / 2 sigmoid   amt_linear_ex_fwd; backward: two GEMMs
+    LinearFn          y = act(x w^T + b) (+ resid), act 0 none / 1 ReLU / 2 sigmoid   amt_linear_ex_fwd; backward: two GEMMs
     SigmoidHeadFn     the classifier head; hands out a second, empty-storage output that stands for its logits, so that the
                       fused loss can send its logit gradient straight to the head's GEMMs (losses.regression_train_loss)
     RnnLayerFn        one nn.LSTM / nn.GRU layer, all its directions    amt_linear_ex_fwd + amt_rnn_seq_train_fwd;
                       backward: amt_rnn_seq_bwd + GEMMs
+    MambaBlockFn      one MambaBlock (+ the layer's residual)           amt_linear_ex_fwd, amt_dwconv1d_silu_fwd,
+                      amt_selective_scan_train_fwd; backward: amt_selective_scan_bwd, amt_dwconv1d_silu_bwd + GEMMs
     RegLossFn         SmoothL1 + BCE and both gradients                 amt_reg_loss_fwd_bwd
 
 and the pieces of the chord model's training that do not depend on the model (losses.chord_train_loss):
@@ -67,12 +70,14 @@ def _linear_backward(ctx, dz, x, w, need_x):
 
 
 class LinearFn(torch.autograd.Function):
-    """y = act(x w^T + b); x (M, K), K a multiple of 32; w (N, K0 <= K) with `w_fwd` its zero-padded (N, K) copy when K0 < K."""
+    """y = act(x w^T + b); x (M, K), K a multiple of 32; w (N, K0 <= K) with `w_fwd` its zero-padded (N, K) copy when K0 < K.
+    `resid` (M, N), act 0 only: added in the GEMM's epilogue, as the inference path adds a layer's residual; it receives dy."""
 
     @staticmethod
-    def forward(ctx, x, w, b, act=0, w_fwd=None):
-        assert act in (0, 1, 2)
-        y = ops.linear_ex(x, (w if w_fwd is None else w_fwd).detach(), b.detach(), act=act)
+    def forward(ctx, x, w, b, act=0, w_fwd=None, resid=None):
+        assert act in (0, 1, 2) and (resid is None or act == 0)
+        y = ops.linear_ex(x, (w if w_fwd is None else w_fwd).detach(), b.detach(), act=act,
+                          resid=None if resid is None else resid.contiguous())
         ctx.act = act
         ctx.save_for_backward(x, w, y if act else None)
         return y
@@ -87,7 +92,7 @@ class LinearFn(torch.autograd.Function):
         else:
             dz = (dy * y * (1.0 - y)).contiguous()              # the sigmoid's derivative from its output
         dx, dw, db = _linear_backward(ctx, dz, x, w.detach(), ctx.needs_input_grad[0])
-        return dx, dw, db, None, None
+        return dx, dw, db, None, None, (dz if len(ctx.needs_input_grad) > 5 and ctx.needs_input_grad[5] else None)
 
 
 class SigmoidHeadFn(torch.autograd.Function):
@@ -162,6 +167,70 @@ class RnnLayerFn(torch.autograd.Function):
             blk = dwi[r * R:(r + 1) * R]
             grads += [blk[:, :x.shape[1]].contiguous(), blk[:, x.shape[1]].contiguous(), dwh[:, :d].contiguous(), dwh[:, d].contiguous()]
         return (dx, None, None, None, None, None, *grads)
+
+
+class MambaBlockFn(torch.autograd.Function):
+    """One MambaBlock (reference model/mamba.py:259-354, no inner layernorms) on rows x (B*L, d), plus `resid` (or None) in the
+    out-projection's epilogue: the launches of `VideoRegression._mamba`, with the training scan in the scan's place.
+
+    apply(x, resid, B, L, version, reverse, wdt, wx, in_w, in_b, conv_w, conv_b, xproj_w, dt_w, dt_b, A_log, D, out_w, out_b): the eleven
+    parameters are the block's own (conv_w (ED, 1, K), xproj_w (R + 2N, ED), dt_w (ED, R)) and receive the gradients; `wdt` (ED, 32) and
+    `wx` (R + 2N rounded up to 4, ED) are their zero-padded copies, the tensors the GEMMs read.  version 1: the Mamba+ gate; reverse:
+    the block of the time-flipped sequence, un-flipped.
+
+    Saved: x, xz, xc, dbc, draw, the gated and the un-gated scan output and one state per 32 steps (B * ceil(L / 32) * ED * N floats);
+    the states in between are recomputed by the backward."""
+
+    @staticmethod
+    def forward(ctx, x, resid, B, L, version, reverse, wdt, wx, in_w, in_b, conv_w, conv_b, xproj_w, dt_w, dt_b, A_log, D, out_w, out_b):
+        ED, K = conv_w.shape[0], conv_w.shape[2]
+        R = dt_w.shape[1]
+        x = x.contiguous()
+        cw = conv_w.detach().reshape(ED, K).contiguous()
+        xz = ops.linear_ex(x, in_w.detach(), in_b.detach())
+        xc = ops.dwconv1d_silu(xz, ED, cw, conv_b.detach(), B, L, reverse)
+        dbc = ops.linear_ex(xc, wx)
+        draw = ops.linear_ex(dbc, wdt, K=32)
+        g, y_pre, h_chunks = ops.selective_scan_train(xc, draw, dt_b.detach(), A_log.detach(), dbc, R, D.detach(), xz, B, L,
+                                                      version=version, reverse=reverse)
+        out = ops.linear_ex(g, out_w.detach(), out_b.detach(), resid=None if resid is None else resid.contiguous())
+        ctx.dims = (B, L, int(version), bool(reverse), R)
+        ctx.save_for_backward(x, xz, xc, dbc, draw, g, y_pre, h_chunks, wx, in_w, cw, conv_b, dt_w, dt_b, A_log, D, out_w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, xz, xc, dbc, draw, g, y_pre, h_chunks, wx, in_w, cw, conv_b, dt_w, dt_b, A_log, D, out_w = ctx.saved_tensors
+        B, L, version, reverse, R = ctx.dims
+        ED, N = A_log.shape
+        M = B * L
+        dout = dout.contiguous()
+        in_w, dt_w, out_w = in_w.detach(), dt_w.detach(), out_w.detach()
+        # out_proj
+        dg = mm_nt(dout, out_w.t())
+        d_out_wb = mm_tn(dout, g, ones=True)                                 # (d, ED + 1): dW_out | db_out
+        # scan + gate: dxc, ddraw, the z half of dxz, dB | dC inside ddbc
+        dxz = torch.empty(M, 2 * ED, device=x.device, dtype=torch.float32)
+        ddbc = torch.zeros_like(dbc)
+        dxc, ddraw, dA_log, dD = ops.selective_scan_bwd(dg, xc, draw, dt_b.detach(), A_log.detach(), dbc, R, D.detach(), xz, y_pre, h_chunks,
+                                                        dxz, ddbc, B, L, version=version, reverse=reverse)
+        # dt_proj: draw = dbc[:, :R] W_dt^T (the bias enters inside the scan)
+        ddbc[:, :R] = mm_nt(ddraw, dt_w.t())
+        d_dt_wb = mm_tn(ddraw, dbc[:, :R], ones=True)                        # (ED, R + 1): dW_dt | d dt_bias
+        # x_proj: dbc = xc W_x^T
+        Kp = _ceil32(ddbc.shape[1])
+        dxc = ops.linear_ex(_padded(ddbc, Kp), _padded(wx.t(), Kp), resid=dxc)
+        d_x_w = mm_tn(ddbc, xc)[:R + 2 * N].contiguous()
+        # conv + SiLU: the x half of dxz
+        d_cw, d_cb = ops.dwconv1d_silu_bwd(dxc, xz, ED, cw, conv_b.detach(), dxz, B, L, reverse)
+        # in_proj
+        dx = mm_nt(dxz, in_w.t()) if ctx.needs_input_grad[0] else None
+        d_in_wb = mm_tn(dxz, x, ones=True)
+        d = x.shape[1]
+        return (dx, dout if ctx.needs_input_grad[1] else None, None, None, None, None, None, None,
+                d_in_wb[:, :d].contiguous(), d_in_wb[:, d].contiguous(), d_cw.view(ED, 1, -1), d_cb, d_x_w,
+                d_dt_wb[:, :R].contiguous(), d_dt_wb[:, R].contiguous(), dA_log, dD,
+                d_out_wb[:, :ED].contiguous(), d_out_wb[:, ED].contiguous())
 
 
 class RegLossFn(torch.autograd.Function):

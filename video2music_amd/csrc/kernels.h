@@ -233,8 +233,14 @@ struct ScanParams {
     const float* z; int ldz;            // [B*L][ED] gate branch (pre-SiLU)
     float* y; int ldy;                  // [B*L][ED] gated output
     int B, L, ED, N, version, reverse;
+    // training forward only (amt_launch_selective_scan_train): what the backward reads
+    float* ypre; int ldyp;              // [B*L][ED] un-gated y_t = h_t . C_t + D x_t
+    float* hck;                         // [B][ceil(L / SCAN_TCH)][ED][N] the state at the start of every chunk, in walking order
 };
+constexpr int SCAN_TCH = 32;            // time steps per chunk of the N = 16 scan (staged per pass; the checkpoint interval)
+constexpr int SCAN_CPB = 16;            // channels per 256-thread block of the scan kernels
 int32_t amt_launch_selective_scan(const ScanParams& p, hipStream_t stream);
+int32_t amt_launch_selective_scan_train(const ScanParams& p, hipStream_t stream);      // N = 16 only; fills ypre and hck too
 // out[row] = [a[row][0:da] | b[row][0:db] | 0-pad to ld_out]
 int32_t amt_launch_concat2(const float* a, int da, const float* b, int db, float* out, int rows, int ld_out, hipStream_t stream);
 

@@ -36,10 +36,12 @@ __global__ void dwconv_silu_kernel(const float* __restrict__ x, int ldx, const f
     y[idx] = silu(acc);
 }
 
-constexpr int TCH = 32;          // time steps staged per pass
-constexpr int CPB = 16;          // channels per 256-thread block (N = 16 lanes each)
+constexpr int TCH = SCAN_TCH;    // time steps staged per pass
+constexpr int CPB = SCAN_CPB;    // channels per 256-thread block (N = 16 lanes each)
 
-template <int N>
+// TRAIN: the same arithmetic, and two more stores for amt_selective_scan_bwd (mamba_bwd.hip): the un-gated y_t and the state at the
+// start of every pass (the backward recomputes the states inside a pass from it).
+template <int N, bool TRAIN>
 __global__ __launch_bounds__(CPB * N) void selective_scan_kernel(ScanParams p) {
     // per staged step: x, delta = softplus(.), silu(z), partial y for the block's channels; B and C rows
     __shared__ float sx[TCH][CPB], sd[TCH][CPB], sz[TCH][CPB], sy[TCH][CPB], sB[TCH][N], sC[TCH][N];
@@ -93,6 +95,7 @@ __global__ __launch_bounds__(CPB * N) void selective_scan_kernel(ScanParams p) {
         }
         __syncthreads();
         if (s0 + TCH < p.L) fetch(s0 + TCH);
+        if (TRAIN && ch < p.ED) p.hck[(((size_t)b * ((p.L + TCH - 1) / TCH) + s0 / TCH) * p.ED + ch) * N + n] = h;
         // the recurrence: one FMA on the dependency chain per step; exp / LDS reads of later steps overlap (unrolled)
 #pragma unroll 8
         for (int s = 0; s < TCH; ++s) {
@@ -110,6 +113,7 @@ __global__ __launch_bounds__(CPB * N) void selective_scan_kernel(ScanParams p) {
                 const float xv = sx[s][cc], zs = sz[s][cc];
                 const float yv = sy[s][cc] + p.D[c0 + cc] * xv;
                 p.y[((size_t)b * p.L + t) * p.ldy + c0 + cc] = p.version == 1 ? yv * zs + xv * (1.0f - 1.0f / (1.0f + __expf(-zs))) : yv * zs;
+                if (TRAIN) p.ypre[((size_t)b * p.L + t) * p.ldyp + c0 + cc] = yv;
             }
         }
         __syncthreads();
@@ -207,12 +211,23 @@ int32_t amt_launch_selective_scan(const ScanParams& p, hipStream_t stream) {
     AMT_CHECK_ARG(p.ldx >= p.ED && p.ldd >= p.ED && p.ldz >= p.ED && p.ldy >= p.ED && p.ldbc >= p.N, "selective_scan: bad leading dimension");
     const dim3 grid(cdiv(p.ED, CPB), p.B), block(CPB * 16);
     switch (p.N) {
-        case 16: hipLaunchKernelGGL(selective_scan_kernel<16>, grid, block, 0, stream, p); break;
+        case 16: hipLaunchKernelGGL((selective_scan_kernel<16, false>), grid, block, 0, stream, p); break;
         case 32: hipLaunchKernelGGL(selective_scan_wide_kernel<2>, grid, block, 0, stream, p); break;
         case 64: hipLaunchKernelGGL(selective_scan_wide_kernel<4>, grid, block, 0, stream, p); break;
         case 128: hipLaunchKernelGGL(selective_scan_wide_kernel<8>, grid, block, 0, stream, p); break;
         default: hipLaunchKernelGGL(selective_scan_wide_kernel<16>, grid, block, 0, stream, p); break;
     }
+    AMT_LAUNCH_CHECK();
+    return 0;
+}
+
+int32_t amt_launch_selective_scan_train(const ScanParams& p, hipStream_t stream) {
+    AMT_CHECK_ARG(p.B > 0 && p.L > 0 && p.ED > 0, "selective_scan_train: bad shape B=%d L=%d ED=%d", p.B, p.L, p.ED);
+    AMT_CHECK_ARG(p.N == 16, "selective_scan_train: d_state=%d: the training scan is built for 16 states per channel (the reference's "
+                  "default) only; wider states run inference", p.N);
+    AMT_CHECK_ARG(p.ldx >= p.ED && p.ldd >= p.ED && p.ldz >= p.ED && p.ldy >= p.ED && p.ldyp >= p.ED && p.ldbc >= p.N,
+                  "selective_scan_train: bad leading dimension");
+    hipLaunchKernelGGL((selective_scan_kernel<16, true>), dim3(cdiv(p.ED, CPB), p.B), dim3(CPB * 16), 0, stream, p);
     AMT_LAUNCH_CHECK();
     return 0;
 }
@@ -243,6 +258,20 @@ extern "C" int32_t amt_selective_scan_fwd(const float* x, int32_t ldx, const flo
     p.x = x; p.ldx = ldx; p.draw = delta_raw; p.ldd = ld_delta; p.dt_bias = dt_bias; p.A_log = A_log; p.Bm = Bm; p.Cm = Cm; p.ldbc = ld_bc;
     p.D = D; p.z = z; p.ldz = ldz; p.y = y; p.ldy = ldy; p.B = B; p.L = L; p.ED = ED; p.N = N; p.version = version; p.reverse = reverse;
     return amt_launch_selective_scan(p, (hipStream_t)stream);
+}
+
+extern "C" int32_t amt_selective_scan_train_fwd(const float* x, int32_t ldx, const float* delta_raw, int32_t ld_delta, const float* dt_bias,
+                                                const float* A_log, const float* Bm, const float* Cm, int32_t ld_bc, const float* D,
+                                                const float* z, int32_t ldz, float* y, int32_t ldy, float* y_pre, int32_t ld_ypre,
+                                                float* h_chunks, int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version,
+                                                int32_t reverse, void* stream) {
+    AMT_CHECK_ARG(x && delta_raw && dt_bias && A_log && Bm && Cm && D && z && y && y_pre && h_chunks, "amt_selective_scan_train_fwd: null pointer");
+    AMT_CHECK_ARG(version == 0 || version == 1, "amt_selective_scan_train_fwd: version %d not in {0,1}", version);
+    ScanParams p{};
+    p.x = x; p.ldx = ldx; p.draw = delta_raw; p.ldd = ld_delta; p.dt_bias = dt_bias; p.A_log = A_log; p.Bm = Bm; p.Cm = Cm; p.ldbc = ld_bc;
+    p.D = D; p.z = z; p.ldz = ldz; p.y = y; p.ldy = ldy; p.B = B; p.L = L; p.ED = ED; p.N = N; p.version = version; p.reverse = reverse;
+    p.ypre = y_pre; p.ldyp = ld_ypre; p.hck = h_chunks;
+    return amt_launch_selective_scan_train(p, (hipStream_t)stream);
 }
 
 extern "C" int32_t amt_concat2_fwd(const float* a, int32_t da, const float* b, int32_t db, float* out, int32_t rows, int32_t ld_out,

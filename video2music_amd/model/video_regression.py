@@ -18,10 +18,11 @@ library's kernels; no torch arithmetic runs in `forward`:
 
 The backward Mamba block runs with `reverse=1` instead of `torch.flip` before and after (bimamba.py:171-185).
 
-Training: for 'lstm' / 'bilstm' / 'gru' / 'bigru', `forward` / `get_feature` called in the training state with gradients enabled build
-their result through the autograd Functions of `video2music_amd/autograd.py` on the module's own parameters (amt_rnn_seq_train_fwd,
-amt_rnn_seq_bwd, the same GEMMs), so `loss.backward()` and a torch optimiser work; every other state and regModel runs the inference
-path above on detached parameters.
+Training: for 'lstm' / 'bilstm' / 'gru' / 'bigru' and for 'bimamba+' / 'bimamba', `forward` / `get_feature` called in the training
+state with gradients enabled build their result through the autograd Functions of `video2music_amd/autograd.py` on the module's own
+parameters (amt_rnn_seq_train_fwd / amt_rnn_seq_bwd; amt_selective_scan_train_fwd / amt_selective_scan_bwd / amt_dwconv1d_silu_bwd /
+amt_layernorm_bwd; the same GEMMs), so `loss.backward()` and a torch optimiser work; every other state and regModel runs the
+inference path above on detached parameters ('mamba' / 'mamba+' lack an RMSNorm backward, the mixture heads the mixture layer's).
 """
 import math
 
@@ -268,15 +269,20 @@ class VideoRegression(nn.Module):
         return ops.linear_ex(g, m.out_proj.weight.detach(), m.out_proj.bias.detach(), resid=resid)
 
     def _train_path(self):
-        """The state in which the four recurrent regModels build an autograd graph (video2music_amd/autograd.py); every other state
-        and regModel runs the inference kernels on detached parameters."""
-        return self.training and torch.is_grad_enabled() and self.regModel in ("lstm", "bilstm", "gru", "bigru")
+        """The state in which the four recurrent regModels and 'bimamba+' / 'bimamba' build an autograd graph
+        (video2music_amd/autograd.py); every other state and regModel runs the inference kernels on detached parameters."""
+        return self.training and torch.is_grad_enabled() and self.regModel in ("lstm", "bilstm", "gru", "bigru", "bimamba+", "bimamba")
 
     def _get_feature_train(self, vf, B, S):
-        """get_feature's recurrent branch through the autograd Functions, on the module's own parameters.  Dropout sits where the
-        reference has it: after in_proj (:169) and between the recurrent layers, not after the last (nn.LSTM / nn.GRU).  The
-        multipliers (0 or 1 / (1 - p), shape (B*S, width)) are drawn by torch on the device, or taken in this order from
-        `self.dropout_masks` when that is a list; the ones used are kept in `self.last_dropout_masks`."""
+        """get_feature's recurrent and bidirectional-Mamba branches through the autograd Functions, on the module's own parameters.
+        Dropout sits where the reference has it: after in_proj (:169); between the recurrent layers, not after the last (nn.LSTM /
+        nn.GRU); in a BiMambaEncoderLayer_V1 (bimamba.py:166-189) after the forward block, after the backward block, inside the FFN
+        (width d_hidden) and after it; in a BiMambaEncoderLayer (:65-98) after the forward block, inside and after ffn1, after the
+        backward block, inside and after ffn2.  MambaBlock constructs a Dropout of its own and never applies it (mamba.py:167,
+        259-290): none here.  The multipliers (0 or 1 / (1 - p), shape (B*S, width)) are drawn by torch on the device, or taken in
+        this order from `self.dropout_masks` when that is a list; the ones used are kept in `self.last_dropout_masks`.  Where no
+        mask intervenes the launches are those of the inference path (residuals in the GEMM epilogues): at dropout 0 the result is
+        the same bits."""
         from .. import autograd as AG
         given = list(self.dropout_masks) if self.dropout_masks is not None else None
         used = []
@@ -290,6 +296,10 @@ class VideoRegression(nn.Module):
 
         lin = self.in_proj[0]
         x = drop(AG.LinearFn.apply(vf, lin.weight, lin.bias, 0, self._Win), self.in_proj[1].p)
+        if not self._rnn:
+            x = self._bimamba_train(x, B, S, drop)
+            self.__dict__["last_dropout_masks"] = used
+            return x.view(B, S, self.d_model)
         gates = 4 if isinstance(self._rnn_mod, nn.LSTM) else 3
         for l in range(self.n_layers):
             names = [n + f"_l{l}" + sfx for sfx in (("", "_reverse") if self._dirs == 2 else ("",))
@@ -299,6 +309,40 @@ class VideoRegression(nn.Module):
                 x = drop(x, self._rnn_mod.dropout)
         self.__dict__["last_dropout_masks"] = used
         return x.view(B, S, self._dirs * self.d_model)
+
+    def _bimamba_train(self, x, B, S, drop):
+        """The encoder layers of 'bimamba+' (V1) / 'bimamba' (V0) on the graph; `drop(x, p)` applies the next dropout mask."""
+        from .. import autograd as AG
+
+        def block(x, m, i, reverse, p):          # dropout(MambaBlock(x)) + x, the sum left to the GEMM epilogue where it can be
+            args = (B, S, self._version, reverse, self._Wdt[i], self._Wx[i], m.in_proj.weight, m.in_proj.bias, m.conv1d.weight,
+                    m.conv1d.bias, m.x_proj.weight, m.dt_proj.weight, m.dt_proj.bias, m.A_log, m.D, m.out_proj.weight, m.out_proj.bias)
+            if m.dt_rank + 2 * m.d_state < 32:
+                raise ValueError("dt_rank + 2*d_state < 32 is not supported")
+            if p <= 0.0:
+                return AG.MambaBlockFn.apply(x, x, *args), None
+            return drop(AG.MambaBlockFn.apply(x, None, *args), p), x
+
+        def ffn(x, f, resid, p_in, p_out):       # dropout(W2 dropout(relu(W1 x))) + resid, likewise
+            h = drop(AG.LinearFn.apply(x, f[0].weight, f[0].bias, 1), p_in)
+            if p_out <= 0.0:
+                return AG.LinearFn.apply(h, f[3].weight, f[3].bias, 0, None, resid), None
+            return drop(AG.LinearFn.apply(h, f[3].weight, f[3].bias), p_out), resid
+
+        ln = lambda t, r, n: AG.LayerNormFn.apply(t, r, n.weight, n.bias, n.eps)
+        p = self.in_proj[1].p                    # the model's one dropout rate: the encoder and its FFNs get the same (video_regression.py:159-167)
+        for i, lyr in enumerate(self.model.layers):
+            if self._version == 0:               # BiMambaEncoderLayer.forward
+                xf = ln(*block(x, lyr.mamba_forward, 2 * i, False, p), lyr.norm1)
+                xf = ln(*ffn(xf, lyr.ffn1, xf, p, p), lyr.norm2)
+                xb = ln(*block(x, lyr.mamba_backward, 2 * i + 1, True, p), lyr.norm3)
+                x = xf + ln(*ffn(xf, lyr.ffn2, xb, p, p), lyr.norm4)          # ffn2 reads x_f, as written at :92
+            else:                                # BiMambaEncoderLayer_V1.forward, norm_first False
+                xf = ln(*block(x, lyr.mamba_forward, 2 * i, False, p), lyr.norm1)
+                xb = ln(*block(x, lyr.mamba_backward, 2 * i + 1, True, p), lyr.norm2)
+                s = xb + xf
+                x = ln(*ffn(s, lyr.ffn, s, p, p), lyr.norm3)
+        return x
 
     def get_feature(self, feature_semantic_list, feature_scene_offset, feature_motion, feature_emotion):
         """video_regression.py:199-238: (B, S, d_model) encoder output.  Scene offset and motion are not used."""

@@ -260,6 +260,52 @@ def selective_scan(xc, draw, dt_bias, A_log, dbc, R, D, xz, B, L, version=1, rev
     return y
 
 
+SCAN_CHUNK = 32                 # steps between two state checkpoints of the training scan (SCAN_TCH of csrc/kernels.h)
+
+
+def selective_scan_train(xc, draw, dt_bias, A_log, dbc, R, D, xz, B, L, version=1, reverse=False):
+    """`selective_scan` (the same bits) that also returns what `selective_scan_bwd` reads: y_pre (B*L, ED), the un-gated scan output,
+    and h_chunks (B, ceil(L / 32), ED, N), the state at the start of every chunk in walking order.  N = 16."""
+    ED, N = A_log.shape
+    y = torch.empty(B * L, ED, device=xc.device, dtype=torch.float32)
+    y_pre = torch.empty_like(y)
+    h_chunks = torch.empty(B, (L + SCAN_CHUNK - 1) // SCAN_CHUNK, ED, N, device=xc.device, dtype=torch.float32)
+    _lib.call("amt_selective_scan_train_fwd", p(xc), ED, p(draw), ED, p(dt_bias), p(A_log), _off(dbc, R), _off(dbc, R + N), dbc.shape[1],
+              p(D), _off(xz, ED), xz.shape[1], p(y), ED, p(y_pre), ED, p(h_chunks), B, L, ED, N, int(version), int(reverse), _st())
+    return y, y_pre, h_chunks
+
+
+def selective_scan_bwd(dout, xc, draw, dt_bias, A_log, dbc, R, D, xz, y_pre, h_chunks, dxz, ddbc, B, L, version=1, reverse=False):
+    """amt_selective_scan_bwd: from dout (B*L, ED) and what `selective_scan_train` read and left.  Fills the z half of dxz (B*L, 2 ED)
+    and columns R .. R + 2N of ddbc (B*L, ld) with dB | dC; returns dx (the gradient of xc), ddraw, dA_log, dD."""
+    ED, N = A_log.shape
+    M = B * L
+    assert dout.shape == (M, ED) and dxz.shape == (M, 2 * ED) and ddbc.shape == dbc.shape
+    for t in (dout, xc, draw, y_pre, h_chunks, dxz, ddbc):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    dx, ddraw = torch.empty_like(xc), torch.empty_like(draw)
+    dA_log, dD = torch.empty_like(A_log), torch.empty_like(D)
+    ws = torch.empty(_lib.call("amt_selective_scan_bwd_ws_floats", B, L, ED, N), device=dout.device, dtype=torch.float32)   # a call's own scratch
+    _lib.call("amt_selective_scan_bwd", p(dout), ED, p(xc), ED, p(draw), ED, p(dt_bias), p(A_log), _off(dbc, R), _off(dbc, R + N),
+              dbc.shape[1], p(D), _off(xz, ED), xz.shape[1], p(y_pre), ED, p(h_chunks), p(dx), ED, p(ddraw), ED, _off(dxz, ED), dxz.shape[1],
+              _off(ddbc, R), _off(ddbc, R + N), ddbc.shape[1], p(dA_log), p(dD), p(ws), B, L, ED, N, int(version), int(reverse), _st())
+    return dx, ddraw, dA_log, dD
+
+
+def dwconv1d_silu_bwd(dy, xz, C_, w, bias, dxz, B, L, reverse=False):
+    """amt_dwconv1d_silu_bwd: the backward of `dwconv1d_silu(xz, C_, w, bias, B, L, reverse)` from dy (B*L, C_).  Fills the first C_
+    columns of dxz (B*L, ld); returns dw (C_, K), dbias (C_)."""
+    M, K = B * L, w.shape[1]
+    assert dy.shape == (M, C_) and dxz.shape[0] == M and dxz.shape[1] >= C_
+    for t in (dy, xz, w, bias, dxz):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    dw, dbias = torch.empty_like(w), torch.empty_like(bias)
+    ws = torch.empty(_lib.call("amt_dwconv1d_silu_bwd_ws_floats", B, L, C_, K), device=dy.device, dtype=torch.float32)
+    _lib.call("amt_dwconv1d_silu_bwd", p(dy), C_, p(xz), xz.shape[1], p(w), p(bias), p(dxz), dxz.shape[1], p(dw), p(dbias), p(ws), B, L, C_, K,
+              int(reverse), _st())
+    return dw, dbias
+
+
 CLIP_METRIC_FIELDS = ("n_valid", "n_top1", "n_hit1", "n_hit3", "n_hit5", "ce_sum", "bce_sum", "n_counted", "n_right", "n_rows")
 
 

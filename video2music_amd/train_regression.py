@@ -1,5 +1,7 @@
 """``train_regression.py`` entry point (reference ``train_regression.py:35-236``, ``utilities/run_model_regression.py:10-68``):
-trains the loudness / note-density / instrument head ``VideoRegression(regModel = lstm | bilstm | gru | bigru)`` on the GPU.
+trains the loudness / note-density / instrument head ``VideoRegression(regModel = lstm | bilstm | gru | bigru)`` on the GPU; the
+Mamba heads ``bimamba+`` (the reference's default head) and ``bimamba`` train through the same loop from
+``python -m video2music_amd.train_regression_mamba`` (``main(argv, trainable=...)``).
 
 A step is the model's training-state forward (``video2music_amd/autograd.py``: the library's GEMMs and recurrence, saved
 activations), the fused loss (``losses.regression_train_loss``), ``backward()`` (``amt_rnn_seq_bwd`` and GEMMs) and a torch
@@ -59,8 +61,15 @@ class LrStepTracker:
         return self.invsqrt_dim * (1 / math.sqrt(step))
 
 
-def refuse(args):
-    """The reason this build does not run `args`, or None."""
+UNBUILT = {"mamba": "the RMSNorm backward is not built", "mamba+": "the RMSNorm backward is not built",
+           "moemamba": "the mixture layer's and the RMSNorm backward are not built (nor the backward of its wide-state scan)",
+           "moe_bimamba+": "the mixture layer's backward is not built", "sharedmoe_bimamba+": "the mixture layer's backward is not built",
+           "cnngru": "the backward of its convolution front is not built", "cnnbigru": "the backward of its convolution front is not built"}
+
+
+def refuse(args, trainable=TRAINABLE):
+    """The reason this build does not run `args`, or None.  `trainable`: the regModels the caller trains (the default: the
+    recurrent heads; train_regression_mamba adds 'bimamba+' and 'bimamba')."""
     if args.force_cpu:
         return "--force_cpu: video2music_amd has no CPU path (the CPU oracle lives in oracle/ for tests only)"
     if not args.is_video:
@@ -71,9 +80,12 @@ def refuse(args):
         return "-augmentation is not built: the clips are read as they are"
     if not args.no_tensorboard:
         return "--no_tensorboard False: tensorboard reporting is not built (results_regression.csv holds the same figures)"
-    if args.regModel not in TRAINABLE:
-        return (f"-regModel {args.regModel}: the backward pass is built for the recurrent heads {', '.join(TRAINABLE)} only (the Mamba, "
-                "mixture and CNN heads run inference here)")
+    if args.regModel not in trainable:
+        if tuple(trainable) == TRAINABLE:
+            return (f"-regModel {args.regModel}: the backward pass is built for the recurrent heads {', '.join(TRAINABLE)} only (the Mamba, "
+                    "mixture and CNN heads run inference here)")
+        return (f"-regModel {args.regModel}: {UNBUILT.get(args.regModel, 'no such regression head')}; the backward pass is built for "
+                f"{', '.join(trainable)} (the other heads run inference here)")
     if args.optimizer in ("RAdam", "RAdamW"):
         return f"-optimizer {args.optimizer}: the reference's own RAdam file is not ported; use Adam or AdamW"
     if args.optimizer not in (None, "Adam", "AdamW"):
@@ -147,9 +159,9 @@ def train_epoch(cur_epoch, model, data, order, batch_size, opt, lr_scheduler=Non
             print("")
 
 
-def main(argv=None):
+def main(argv=None, trainable=TRAINABLE):
     args = parse_train_args(argv)[0]
-    why = refuse(args)
+    why = refuse(args, trainable)
     if why:
         raise SystemExit(why)
     device = get_device()
