@@ -301,8 +301,9 @@ def v2_attention(xq, xkv, sd, prefix, H, cache, causal):
     q = linear(xq, W[:E], b[:E]).contiguous()
     k = linear(xkv, W[E:2 * E], b[E:2 * E]).contiguous()
     v = linear(xkv, W[2 * E:], b[2 * E:]).contiguous()
-    q = rope(q.view(H, L, B, hd), cache).reshape(L, B, E)
-    k = rope(k.view(H, S, B, hd), cache).reshape(S, B, E)
+    if cache is not None:                # no RoPE (V2 '2.0', and nn.MultiheadAttention of the V1 versions other than '1.2'): the same attention
+        q = rope(q.view(H, L, B, hd), cache).reshape(L, B, E)
+        k = rope(k.view(H, S, B, hd), cache).reshape(S, B, E)
     qh = q.reshape(L, B * H, hd).transpose(0, 1) * math.sqrt(1.0 / float(hd))
     kh = k.reshape(S, B * H, hd).transpose(0, 1)
     vh = v.reshape(S, B * H, hd).transpose(0, 1)
@@ -330,7 +331,11 @@ def forward_v2(sd, H, x_root, x_attr, sem, key, scene_off, motion, emotion, max_
     """VideoMusicTransformer_V2.forward, version '2.2', chord_embed=False (:427-516): no additive positional
     encoding, RoPE inside every attention, post-norm layers (custom_transformer.py:1228-1240, 1260-1276).  ``mask=False``:
     tgt_mask=None (:440-443).  ``drop_keep`` (B, S) in {0, 1}: the dropTokenRate mask ``torch.rand(B, S) > rate`` (:488-492).
-    ``collect`` (list): the gate logits of every mixture layer, encoder layers first, each seq-first (L, B, n_experts)."""
+    ``collect`` (list): the gate logits of every mixture layer, encoder layers first, each seq-first (L, B, n_experts).
+    `forward_family` covers this member too (bit-identical in fp32).  In a float64 run this function rotates with the model's own
+    fp32 RoPE table cast up, `forward_family` with a table built in float64; at position 299 the two tables differ by ~2e-5, which
+    reaches the logits of the "feedback" recipe at 7e-6 relative -- over the 5e-6 that test_lockstep_parity_gpu.py holds the decode
+    step to against this function, so the table stays as it is here."""
     d = sd["Wout.weight"].shape[1]
     cache = rope_cache(d, max_seq_video).to(sd["Wout.weight"].dtype)
     x = sd["embedding_root.weight"][x_root] + sd["embedding_attr.weight"][x_attr]
@@ -363,20 +368,180 @@ def forward_v2(sd, H, x_root, x_attr, sem, key, scene_off, motion, emotion, max_
 
 
 # ----------------------------------------------------------------------------------------------
+# the model families: VideoMusicTransformer_V1 / _V2 / _V3, every version string (model/video_music_transformer.py:22-909)
+# ----------------------------------------------------------------------------------------------
+# Deliberately wrong variants of `forward_family` (its `wrong=` argument).  They exist for the sensitivity check of
+# tests/test_family_parity_host.py only: a parity case must be able to tell each of them from the restatement.
+WRONG_VARIANTS = ("odd_heads_from_0", "rope_dim_d_model", "transposed_output", "lambda_init_depth0", "no_rope", "rms_eps_1e-5")
+
+
+def lambda_init_of(depth):
+    """custom_transformer.py:607-608."""
+    return 0.8 - 0.6 * math.exp(-0.3 * depth)
+
+
+def family_plan(version):
+    """What a version string selects: (learned positional tables, RoPE cache dim as a multiple of d_model or None, pre-norm).
+    The V1 and V2 classes test ``version_name in ('1.2.3')`` / ``in ('2.0')``: strings, not tuples, hence substring tests (:86, :375,
+    :497), so of the V1 versions '1.2' is the one with rotary attention."""
+    if version.startswith("1"):
+        return True, (1 if version in "1.2.3" else None), False
+    if version.startswith("2"):
+        return version in "2.0", (1 if version in ("2.1", "2.2", "2.3") else None), False
+    return False, 2, version == "3.2"                              # V3: RotaryPositionalEmbeddings(d_model * 2, ...) (:660), '3.2' pre-norm (:693)
+
+
+def diff_attention(xq, xkv, sd, prefix, H, cache, causal, depth, wrong=()):
+    """DifferentialMultiheadAttention.forward as wired (custom_transformer.py:770-832), seq-first (L, B, E) in and out.
+
+    q, k = x Wq^T, x Wk^T (E -> 2E, no bias) are rotated through the raw (2H, L, B, hd) view of their (L, B, 2E) buffers (:779-785)
+    and then read through the raw (B, L, 2H, hd) view, v through the raw (B, S, H, hd) view (:787-789).  Heads 2h and 2h+1 give the
+    two softmax maps of pair h (:817); lambda_full = exp(lq1.lk1) - exp(lq2.lk2) + lambda_init(depth) (:814-816); the result is
+    RMSNorm over head_dim with eps 1e-5 times (1 - lambda_init) (:823-824) and its (B, H, L, hd) buffer is *viewed* as (L, B, E)
+    (:825).  A mask, when one is passed, is always the causal one (:800-808)."""
+    L, B, E = xq.shape
+    S = xkv.shape[0]
+    hd = E // H
+    q = linear(xq, sd[prefix + "q_proj.weight"]).contiguous()
+    k = linear(xkv, sd[prefix + "k_proj.weight"]).contiguous()
+    v = linear(xkv, sd[prefix + "v_proj.weight"]).contiguous()
+    cq = ck = cache
+    if "rope_dim_d_model" in wrong:      # `cache` was built for dim = d_model and holds H head slices per length: heads H .. 2H-1 reuse them
+        cq, ck = (torch.cat([cache[:n].contiguous().view(H, -1)] * 2).view(n, -1, 2) for n in (L, S))
+    q = rope(q.view(2 * H, L, B, hd), cq).contiguous().view(B, L, 2 * H, hd).transpose(1, 2) * (float(hd) ** -0.5)
+    k = rope(k.view(2 * H, S, B, hd), ck).contiguous().view(B, S, 2 * H, hd).transpose(1, 2)
+    v = v.view(B, S, H, hd).transpose(1, 2)
+    s = q @ k.transpose(-1, -2)                                                    # (B, 2H, L, S)
+    if causal:
+        s = s + torch.triu(torch.full((L, S), float("-inf"), dtype=s.dtype), diagonal=1 + S - L)
+    a = torch.softmax(_hi(s), dim=-1).to(s.dtype).view(B, H, 2, L, S)
+    lam_init = lambda_init_of(0 if "lambda_init_depth0" in wrong else depth)
+    l1 = torch.exp(torch.sum(_hi(sd[prefix + "lambda_q1"] * sd[prefix + "lambda_k1"]), dim=-1))
+    l2 = torch.exp(torch.sum(_hi(sd[prefix + "lambda_q2"] * sd[prefix + "lambda_k2"]), dim=-1))
+    lam = (l1 - l2).to(s.dtype) + lam_init
+    a2 = a[:, :, 0] if "odd_heads_from_0" in wrong else a[:, :, 1]
+    o = (a[:, :, 0] - lam * a2) @ v                                                # (B, H, L, hd)
+    o = rms_norm(o, sd[prefix + "subln.weight"], eps=1e-5) * (1.0 - lam_init)
+    o = o.permute(2, 0, 1, 3).reshape(L, B, E) if "transposed_output" in wrong else o.contiguous().view(L, B, E)
+    return linear(o, sd[prefix + "out_proj.weight"])
+
+
+def family_ff(x, sd, prefix, collect=None):
+    """A layer's feed-forward: a plain GLUExpert, or a 6-expert top-2 mixture -- MoELayer (moe.py:167-200) when the layer holds
+    no shared expert, else SharedMoELayer (:231-302) -- over GLU or Linear-SiLU-Linear experts.  SharedMoELayer's balancing `bias`
+    buffer (V3, :224-226) only enters the routing in training mode (:257-262): ignored."""
+    if prefix + "linear1.weight" in sd:
+        return glu_expert(x, sd, prefix)
+    sub = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+    if collect is not None:
+        collect.append(linear(x, sub["gate.weight"], sub.get("gate.bias")))
+    return moe_forward(x, sub, sub["gate.weight"].shape[0], k=2, shared="shared_expert.linear2.weight" in sub or "shared_expert.3.weight" in sub)
+
+
+def forward_family(sd, version, H, x_root, x_attr, sem, key, scene_off, motion, emotion, max_seq_video=300, mask=True, drop_keep=None,
+                   collect=None, wrong=()):
+    """Teacher-forced eval forward of VideoMusicTransformer_V1 ('1.0', '1.1', '1.2', '1.3', '1.3.3', '1.3.4'; :142-225), _V2 ('2.0',
+    '2.1', '2.2'; :439-520) and _V3 ('3.0', '3.1', '3.2'; :749-819): logits (B, L, 159).  The version string fixes the positional
+    scheme and pre- / post-norm (`family_plan`); everything else is read off the state dict: LayerNorm has a bias and RMSNorm
+    (``rms_norm=True`` of V1, every norm of V3; eps 1e-6) has none, a differential attention holds `q_proj`, a mixture holds `experts`,
+    `chord_embedding_model` / `scene_embedding` are present when the model was built with chord_embed / scene_embed (`x_root` then
+    carries the chord ids).  ``mask=False``: tgt_mask=None.  ``drop_keep`` (B, S) in {0, 1}: the dropTokenRate mask
+    ``torch.rand(B, S) > rate``, applied before the positional rows.  ``collect`` (list): the gate logits of every mixture layer,
+    encoder layers first, each seq-first (L, B, n_experts).  The whole batch goes through at once: for B > 1 the raw views of the
+    rotary and differential attentions tie the clips together.  ``wrong``: see WRONG_VARIANTS."""
+    assert all(w in WRONG_VARIANTS for w in wrong)
+    learned_pos, rope_mult, pre_norm = family_plan(version)
+    dt = sd["Wout.weight"].dtype
+    d = sd["Wout.weight"].shape[1]
+    assert learned_pos == ("positional_embedding.weight" in sd)
+    if "no_rope" in wrong:
+        rope_mult = None
+    if "rope_dim_d_model" in wrong:
+        rope_mult = 1
+    cache = None if rope_mult is None else rope_cache(rope_mult * d, max_seq_video, dtype=dt)
+    rms_eps = 1e-5 if "rms_eps_1e-5" in wrong else 1e-6
+
+    def norm(x, p):
+        if p + "bias" in sd:
+            return layer_norm(x, sd[p + "weight"], sd[p + "bias"])
+        return rms_norm(x, sd[p + "weight"], eps=rms_eps)
+
+    def attention(xq, xkv, p, causal, depth):
+        if p + "q_proj.weight" in sd:
+            return diff_attention(xq, xkv, sd, p, H, cache, causal, depth, wrong)
+        return v2_attention(xq, xkv, sd, p, H, cache, causal)
+
+    # chord stream (:148-166): embeddings, the key as one more column, Linear_chord
+    if "chord_embedding_model.weight" in sd:
+        x = sd["chord_embedding_model.weight"][x_root]
+    else:
+        x = sd["embedding_root.weight"][x_root] + sd["embedding_attr.weight"][x_attr]
+    B, L, _ = x.shape
+    kk = key.to(dt).reshape(-1)
+    if kk.numel() == 1:
+        kk = kk.expand(B)
+    x = linear(torch.cat([x, kk.view(B, 1, 1).expand(B, L, 1)], dim=-1), sd["Linear_chord.weight"], sd["Linear_chord.bias"])
+    # video stream (:168-197): concatenated features, Linear_vis, scene embedding, dropped tokens
+    scene_embed = "scene_embedding.weight" in sd
+    cols = [sem.to(dt)] + ([] if scene_embed else [scene_off.unsqueeze(-1).to(dt)])
+    cols += [motion.unsqueeze(-1).to(dt) if motion.dim() == 2 else motion.to(dt), emotion.to(dt)]
+    vf = linear(torch.cat(cols, dim=-1), sd["Linear_vis.weight"], sd["Linear_vis.bias"])
+    if scene_embed:
+        vf = vf + sd["scene_embedding.weight"][scene_off.to(torch.int32).long()]
+    if drop_keep is not None:
+        vf = vf * drop_keep.to(dt).unsqueeze(-1)
+    S = vf.shape[1]
+    t, src = x.permute(1, 0, 2).contiguous(), vf.permute(1, 0, 2).contiguous()             # seq-first
+    if learned_pos:                                                                        # (:199-208, :497-503)
+        t = t + sd["positional_embedding.weight"][:L].unsqueeze(1)
+        src = src + sd["positional_embedding_video.weight"][:S].unsqueeze(1)
+    causal = mask is True
+    for i in range(n_layers_of(sd, "encoder")):
+        p = f"transformer.encoder.layers.{i}."
+        if pre_norm:                                                                       # custom_transformer.py:1239-1247
+            h = norm(src, p + "norm1.")
+            src = src + attention(h, h, p + "self_attn.", False, i)
+            src = src + family_ff(norm(src, p + "norm2."), sd, p + "ff.", collect)
+        else:                                                                              # :1231-1238
+            src = norm(src + attention(src, src, p + "self_attn.", False, i), p + "norm1.")
+            src = norm(src + family_ff(src, sd, p + "ff.", collect), p + "norm2.")
+    memory = norm(src, "transformer.encoder.norm.")
+    for i in range(n_layers_of(sd, "decoder")):
+        p = f"transformer.decoder.layers.{i}."
+        if pre_norm:                                                                       # :1278-1291
+            h = norm(t, p + "norm1.")
+            t = t + attention(h, h, p + "self_attn.", causal, i)
+            t = t + attention(norm(t, p + "norm2."), memory, p + "cross_attn.", False, i)
+            t = t + family_ff(norm(t, p + "norm3."), sd, p + "ff.", collect)
+        else:                                                                              # :1263-1277
+            t = norm(t + attention(t, t, p + "self_attn.", causal, i), p + "norm1.")
+            t = norm(t + attention(t, memory, p + "cross_attn.", False, i), p + "norm2.")
+            t = norm(t + family_ff(t, sd, p + "ff.", collect), p + "norm3.")
+    t = norm(t, "transformer.decoder.norm.")
+    return linear(t.permute(1, 0, 2), sd["Wout.weight"], sd["Wout.bias"])
+
+
+# ----------------------------------------------------------------------------------------------
 # standalone modules of configs 4/5 and the kernel-level rows (a10-a12)
 # ----------------------------------------------------------------------------------------------
+def _hi(x):
+    """The reference's ``.float()`` up-cast (fp32 at least), which must not round a float64 run of the oracle down to fp32."""
+    return x if x.dtype == torch.float64 else x.float()
+
+
 def rms_norm(x, w, eps=1e-6):
-    """model/custom_transformer.py:38-45: x * rsqrt(mean(x^2)+eps) * w, computed in fp32."""
-    xf = x.float()
+    """model/custom_transformer.py:38-45: x * rsqrt(mean(x^2)+eps) * w, computed in fp32 (in float64 for float64 input)."""
+    xf = _hi(x)
     y = (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)).type_as(x)
     return y * w if w is not None else y
 
 
-def rope_cache(dim, max_seq_len, base=10000):
-    """model/rotate_operation.py:88-109: theta_i = base^(-2i/dim); cache (max_seq, dim/2, [cos,sin])."""
-    theta = 1.0 / (base ** (torch.arange(0, dim, 2)[: dim // 2].float() / dim))
+def rope_cache(dim, max_seq_len, base=10000, dtype=torch.float32):
+    """model/rotate_operation.py:88-109: theta_i = base^(-2i/dim); cache (max_seq, dim/2, [cos,sin]).  The reference builds it
+    in fp32; ``dtype=torch.float64`` builds the angles and their cos / sin in float64 for the float64 runs of the oracle."""
+    theta = 1.0 / (base ** (torch.arange(0, dim, 2)[: dim // 2].to(dtype) / dim))
     idx = torch.arange(max_seq_len, dtype=theta.dtype)
-    ang = torch.einsum("i,j->ij", idx, theta).float()
+    ang = torch.einsum("i,j->ij", idx, theta).to(dtype)
     return torch.stack([torch.cos(ang), torch.sin(ang)], dim=-1)
 
 
@@ -385,7 +550,7 @@ def rope(x, cache, input_pos=None):
     by the cached angle of position s."""
     seq_len = x.size(1)
     rc = cache[:seq_len] if input_pos is None else cache[input_pos]
-    xs = x.float().reshape(*x.shape[:-1], -1, 2)
+    xs = _hi(x).reshape(*x.shape[:-1], -1, 2)
     # when the cache was built for dim != h_d (the reference builds it with dim=d_model,
     # video_music_transformer.py:87,380,660) this view folds the extra frequencies into the
     # leading axis, which is then truncated to x's leading size (rotate_operation.py:148-149)
@@ -440,6 +605,16 @@ def glu_expert(x, sd, p):
     return linear(a * gte, sd[p + "linear2.weight"], sd[p + "linear2.bias"])
 
 
+def silu_expert(x, sd, p):
+    """The V1 family's other expert (model/video_music_transformer.py:80-85): Sequential(Linear(d, 2d), SiLU, Dropout, Linear(2d, d)),
+    so the two products sit at indices 0 and 3."""
+    return linear(F.silu(linear(x, sd[p + "0.weight"], sd[p + "0.bias"])), sd[p + "3.weight"], sd[p + "3.bias"])
+
+
+def expert(x, sd, p):
+    return glu_expert(x, sd, p) if p + "linear1.weight" in sd else silu_expert(x, sd, p)
+
+
 def moe_forward(x, sd, n_experts, k=2, shared=False, routing=None, temperature=1.0):
     """model/moe.py:167-200 (MoELayer) / :231-302 (SharedMoELayer), eval mode, Appendix A6.
 
@@ -449,7 +624,7 @@ def moe_forward(x, sd, n_experts, k=2, shared=False, routing=None, temperature=1
     """
     logits = linear(x, sd["gate.weight"], sd.get("gate.bias"))
     w, idx = torch.topk(logits, k, dim=-1)
-    w = torch.softmax(w.float() / temperature, dim=-1).to(x.dtype)
+    w = torch.softmax(_hi(w) / temperature, dim=-1).to(x.dtype)
     out = torch.zeros_like(x)
     for e in range(n_experts):
         sel = idx == e                                          # (..., k)
@@ -457,9 +632,9 @@ def moe_forward(x, sd, n_experts, k=2, shared=False, routing=None, temperature=1
         if not tok.any():
             continue
         we = (w * sel).sum(-1)[tok]
-        out[tok] += we.unsqueeze(-1) * glu_expert(x[tok], sd, f"experts.{e}.")
+        out[tok] += we.unsqueeze(-1) * expert(x[tok], sd, f"experts.{e}.")
     if shared:
-        out = out + (1.0 / k) * glu_expert(x, sd, "shared_expert.")
+        out = out + (1.0 / k) * expert(x, sd, "shared_expert.")
     if routing is not None:
         routing["idx"], routing["weights"] = idx, w
     return out

@@ -389,3 +389,144 @@ def test_rpr_false_forward_and_generate(golden):
     args = (sd, 4, one["semantic"], one["key"], one["scene_offset"], one["motion"], one["emotion"], torch.tensor([1]), torch.tensor([1]), torch.tensor([0]))
     assert np.array_equal(O.generate(*args, target_seq_length=48, beam=1).numpy(), g["g1"])
     assert np.array_equal(O.generate(*args, target_seq_length=48, beam=0).numpy(), g["g2"])
+
+
+# ---------------- the model families: O.forward_family against the reference's V1 / V2 / V3 classes ----------------
+# Bound: this file's convention, 5e-5 at logits of magnitude ~10 (test_v2_forward_logits), scaled by max(1, max|golden| / 10).  The
+# float64 run's distance to the golden is printed next to it: that is the reference's own fp32 noise.
+FAMILY_KEY = np.array([[0.0], [1.0], [0.0]], dtype=np.float32)
+FAMILY_CFG = dict(n_layers=4, num_heads=4, d_model=128, dim_feedforward=256, total_vf_dim=synthetic.total_vf_dim(1))
+
+
+def family_sd(version, seed=0, **over):
+    from tests.helpers_family_parity import named_shapes
+    cfg = dict(FAMILY_CFG, **over)
+    if cfg.get("scene_embed"):
+        cfg["total_vf_dim"] -= 1
+    return cfg, {k: torch.from_numpy(v) for k, v in synthetic.synthetic_state_dict(named_shapes(version, **cfg), seed=seed).items()}
+
+
+def check_family_golden(what, cfg, sd, version, want, x_root, x_attr, clips, feats=None, **kw):
+    """forward_family in fp32 (asserted) and fp64 (printed) against the reference's logits `want`."""
+    feats = synthetic.synthetic_features(3, seed=1234) if feats is None else feats
+    dist = {}
+    for dtype in (torch.float32, torch.float64):
+        f = feats_t(feats, clips, key=FAMILY_KEY[:len(feats["key"])], dtype=dtype)
+        with torch.no_grad():
+            lg = O.forward_family({k: v.to(dtype) for k, v in sd.items()}, version, cfg["num_heads"], torch.from_numpy(x_root), torch.from_numpy(x_attr),
+                                  f["semantic"], f["key"], f["scene_offset"], f["motion"], f["emotion"], **kw)
+        assert tuple(lg.shape) == want.shape
+        dist[dtype] = float(np.abs(lg.numpy() - want).max())
+    tol = 5e-5 * max(1.0, float(np.abs(want).max()) / 10.0)
+    print(f"\nFAMILY_GOLDEN {what}: fp32 oracle {dist[torch.float32]:.2e}  fp64 oracle {dist[torch.float64]:.2e}  bound {tol:.2e}  "
+          f"max|golden| {float(np.abs(want).max()):.1f}")
+    assert dist[torch.float32] <= tol, (what, dist[torch.float32], tol)
+    return dist
+
+
+@pytest.mark.parametrize("tag,version,rms", [("v10", "1.0", False), ("v11", "1.1", False), ("v12", "1.2", False), ("v13", "1.3", False),
+                                             ("v133", "1.3.3", False), ("v134", "1.3.4", False), ("v11rms", "1.1", True)])
+def test_family_v1_vs_reference(golden, tag, version, rms):
+    g = golden("g_v1.npz")
+    cfg, sd = family_sd(version, rms_norm=rms)
+    assert len(sd) == int(g[f"{tag}_n_keys"])
+    check_family_golden(f"g_v1 {tag}", cfg, sd, version, g[f"{tag}_logits"], g[f"{tag}_root"], g[f"{tag}_attr"], slice(0, 2))
+
+
+@pytest.mark.parametrize("tag,version,over", [("v20", "2.0", {}), ("v21", "2.1", {}), ("v22ce", "2.2", dict(chord_embed=True)),
+                                              ("v22se", "2.2", dict(scene_embed=True))])
+def test_family_v2_variants_vs_reference(golden, tag, version, over):
+    g = golden("g_v2_variants.npz")
+    cfg, sd = family_sd(version, n_layers=6, **over)
+    for B in (1, 2):
+        x_root = g[f"{tag}_x_B{B}"] if over.get("chord_embed") else g[f"{tag}_root_B{B}"]
+        check_family_golden(f"g_v2_variants {tag} B{B}", cfg, sd, version, g[f"{tag}_logits_B{B}"], x_root, g[f"{tag}_attr_B{B}"], slice(0, B))
+
+
+@pytest.mark.parametrize("tag,version", [("v30", "3.0"), ("v31", "3.1"), ("v32", "3.2")])
+def test_family_v3_vs_reference(golden, tag, version):
+    g = golden("g_v3.npz")
+    cfg, sd = family_sd(version)
+    assert len(sd) == int(g[f"{tag}_n_keys"])
+    check_family_golden(f"g_v3 {tag} B2", cfg, sd, version, g[f"{tag}_logits"], g[f"{tag}_root"], g[f"{tag}_attr"], slice(0, 2))
+    check_family_golden(f"g_v3 {tag} B1", cfg, sd, version, g[f"{tag}_logits1"], g[f"{tag}_root1"], g[f"{tag}_attr1"], slice(2, 3))
+
+
+@pytest.mark.parametrize("tag,version", [("v22", "2.2"), ("v20", "2.0"), ("v11", "1.1"), ("v30", "3.0")])
+def test_family_options_vs_reference(golden, tag, version):
+    """dropTokenRate=0.3 under torch.manual_seed(5) and forward(mask=False) of the family classes (oracle/make_goldens_opts.py)."""
+    g = golden("g_opts.npz")
+    cfg, sd = family_sd(version)
+    keep = torch.from_numpy(g[f"{tag}_drop_mask"])
+    torch.manual_seed(5)
+    assert torch.equal(torch.rand(2, 300) > 0.3, keep)
+    check_family_golden(f"g_opts {tag} drop", cfg, sd, version, g[f"{tag}_drop_logits"], g["fam_root"], g["fam_attr"], slice(0, 2), drop_keep=keep)
+    check_family_golden(f"g_opts {tag} nomask", cfg, sd, version, g[f"{tag}_nomask_logits"], g["fam_root"], g["fam_attr"], slice(0, 2), mask=False)
+
+
+def test_forward_v2_is_the_family_member():
+    """`forward_v2` keeps its signature and is version '2.2' of `forward_family`."""
+    from tests.helpers import CFG_V2, synthetic_sd_v2
+    sd = synthetic_sd_v2(dict(CFG_V2, n_layers=4))
+    f = feats_t(synthetic.synthetic_features(2, seed=7, n_frames=40))
+    rs = np.random.RandomState(3)
+    root, attr = torch.from_numpy(rs.randint(0, 15, size=(2, 9))), torch.from_numpy(rs.randint(0, 16, size=(2, 9)))
+    args = (root, attr, f["semantic"], f["key"], f["scene_offset"], f["motion"], f["emotion"])
+    ga, gb = [], []
+    a = O.forward_v2(sd, 4, *args, collect=ga)
+    b = O.forward_family(sd, "2.2", 4, *args, collect=gb)
+    assert torch.equal(a, b) and len(ga) == len(gb) == 2 and all(torch.equal(p, q) for p, q in zip(ga, gb))
+
+
+def test_float64_stays_float64():
+    """rms_norm, rope, rope_cache and the mixture weights keep float64 (no rounding to fp32 inside a float64 run) and return for float32
+    input what they returned before (test_rms_rope pins that to the reference)."""
+    rs = np.random.RandomState(0)
+    x = torch.from_numpy(rs.standard_normal((4, 7, 2, 32)))
+    w = torch.from_numpy(rs.uniform(0.5, 1.5, 32))
+    y = O.rms_norm(x, w)
+    assert y.dtype == torch.float64
+    ref = x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + 1e-6) * w
+    assert float((y - ref).abs().max()) < 1e-14 and float((O.rms_norm(x.float(), w.float()).double() - ref).abs().max()) > 1e-9
+    c64, c32 = O.rope_cache(64, 300, dtype=torch.float64), O.rope_cache(64, 300)
+    assert c64.dtype == torch.float64 and c32.dtype == torch.float32
+    ang = torch.arange(300, dtype=torch.float64)[:, None] * (10000.0 ** (-torch.arange(0, 64, 2, dtype=torch.float64) / 64))[None, :]
+    assert float((c64 - torch.stack([ang.cos(), ang.sin()], -1)).abs().max()) < 1e-12
+    assert float((c32.double() - c64).abs().max()) < 3e-5                  # 299 x an fp32 rounding of theta
+    r = O.rope(x, O.rope_cache(128, 300, dtype=torch.float64))            # (n_h, s, b, h_d) = (4, 7, 2, 32) with the d_model-wide cache
+    assert r.dtype == torch.float64 and r.shape == x.shape
+    assert float((r.pow(2).sum(-1) - x.pow(2).sum(-1)).abs().max()) < 1e-12   # rotations: every vector keeps its norm to float64 accuracy
+    r32 = O.rope(x.float(), O.rope_cache(128, 300))
+    assert r32.dtype == torch.float32 and 1e-9 < float((r32.double() - r).abs().max()) < 1e-5
+
+
+@pytest.mark.parametrize("tag,version,rms", [("v12", "1.2", False), ("v10rms", "1.0", True), ("v20", "2.0", False), ("v31", "3.1", False),
+                                             ("v32", "3.2", False)])
+def test_family_second_configuration_vs_reference(golden, tag, version, rms):
+    """oracle/make_goldens_families_alt.py: d_model 256, 2 heads (head_dim 128), 3 layers, dim_feedforward 192, B = 3, L = 40, 64
+    frames -- where a wrong generalisation of the raw views no longer coincides with the right one; the V1 models also hold the
+    gate logits of their six mixture layers."""
+    g = golden("g_families_alt.npz")
+    cfg, sd = family_sd(version, n_layers=3, num_heads=2, d_model=256, dim_feedforward=192, rms_norm=rms)
+    assert len(sd) == int(g[f"{tag}_n_keys"])
+    feats = synthetic.synthetic_features(3, seed=4242, n_frames=64)
+    assert np.array_equal(feats["key"], g["key"])
+    f = feats_t(feats)
+    want = g[f"{tag}_logits"]
+    assert want.shape == (3, 40, 159)
+    dist = {}
+    for dtype in (torch.float32, torch.float64):
+        gates = []
+        with torch.no_grad():
+            lg = O.forward_family({k: v.to(dtype) for k, v in sd.items()}, version, 2, torch.from_numpy(g[f"{tag}_root"]), torch.from_numpy(g[f"{tag}_attr"]),
+                                  *(f[k].to(dtype) for k in ("semantic", "key", "scene_offset", "motion", "emotion")), collect=gates)
+        dist[dtype] = float(np.abs(lg.numpy() - want).max())
+        n_gates = sum(1 for k in g if k.startswith(f"{tag}_gate"))
+        assert len(gates) == n_gates == (6 if version[0] == "1" else 0)
+        gd = max([float(np.abs(q.numpy() - g[f"{tag}_gate{i}"]).max()) for i, q in enumerate(gates)], default=0.0)
+        if dtype == torch.float32:
+            assert gd <= 5e-5, (tag, "gate logits", gd)
+    tol = 5e-5 * max(1.0, float(np.abs(want).max()) / 10.0)
+    print(f"\nFAMILY_GOLDEN g_families_alt {tag}: fp32 oracle {dist[torch.float32]:.2e}  fp64 oracle {dist[torch.float64]:.2e}  bound {tol:.2e}  "
+          f"max|golden| {float(np.abs(want).max()):.1f}  gate logits {gd:.2e}")
+    assert dist[torch.float32] <= tol, (tag, dist[torch.float32], tol)

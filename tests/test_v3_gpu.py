@@ -46,7 +46,7 @@ def test_v3_vs_reference_golden(golden, tag, version):
             m.generate(beam=0, use_cache=True, **kw)
 
 
-@pytest.mark.parametrize("hd", [32, 64, 128])
+@pytest.mark.parametrize("hd", [16, 32, 64, 128])
 def test_diff_subln_kernel(hd):
     rs = np.random.RandomState(hd)
     o1, o2 = (torch.from_numpy(rs.standard_normal((3, 5, 7, hd)).astype(np.float32)) for _ in range(2))
