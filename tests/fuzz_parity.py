@@ -431,8 +431,8 @@ def run_case_modules(i, rs):
 
 
 def run_case_reg(i, rs):
-    """VideoRegression (row f2) at random sizes against oracle/reg_oracle.py: the Mamba / BiMamba heads in both gate versions and the
-    recurrent heads, 1-4 layers, clips of 1 ... 300 frames."""
+    """VideoRegression (row f2) at random sizes against the float64 run of oracle/reg_oracle.py: the Mamba / BiMamba heads in both gate
+    versions and the recurrent heads, 1-4 layers, clips of 1 ... 300 frames."""
     from oracle import reg_oracle as R
     from video2music_amd.model.video_regression import VideoRegression
     reg = str(rs.choice(["bimamba+", "bimamba", "mamba+", "mamba", "lstm", "bilstm", "gru", "bigru", "cnngru", "cnnbigru"]))
@@ -441,7 +441,10 @@ def run_case_reg(i, rs):
                d_hidden=int(rs.choice([16, 32, 64, 128, 256])), total_vf_dim=774, regModel=reg)
     B, S = int(rs.choice([1, 2, 3])), int(rs.choice([1, 2, 31, 32, 33, 120, 299, 300]))
     info = dict(case=i, module="VideoRegression", cfg=cfg, B=B, S=S)
-    m = VideoRegression(**cfg).eval()
+    try:
+        m = VideoRegression(**cfg).eval()
+    except ValueError as e:                           # a width the head documents as refused (d_model / d_hidden 16): reported, not a failure
+        return dict(info, refused=str(e), fails=[])
     shapes = [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
     sd = {k: torch.from_numpy(v) for k, v in synthetic.synthetic_state_dict(shapes, seed=80 + i).items()}
     m.load_state_dict(sd, strict=True)
@@ -450,8 +453,8 @@ def run_case_reg(i, rs):
     sem, emo = torch.from_numpy(f["semantic"][:, :S].copy()), torch.from_numpy(f["emotion"][:, :S].copy())
     with torch.no_grad():
         ln_nd, inst = m(sem.cuda(), None, None, emo.cuda())
-    ref_ln, ref_inst = R.forward(sd, sem, emo, reg_model=reg)
-    info["err"] = float(max((ln_nd.cpu() - ref_ln).abs().max(), (inst.cpu() - ref_inst).abs().max()))
+    ref_ln, ref_inst = R.forward(sd, sem, emo, reg_model=reg, dtype=torch.float64)      # the float64 run, as the families sweep compares
+    info["err"] = float(max((ln_nd.cpu().double() - ref_ln).abs().max(), (inst.cpu().double() - ref_inst).abs().max()))
     info["scale"] = float(ref_ln.abs().max())
     info["fails"] = [] if info["err"] < 1e-4 * max(1.0, info["scale"]) else ["output"]
     return info

@@ -146,8 +146,11 @@ class VideoRegression(nn.Module):
             moe = cls(GLUExpert(d_model, d_model * 2 + 1), d_model, n_experts=6, n_experts_per_token=2, dropout=dropout)
         if use_KAN or scene_embed or chord_embed:
             raise NotImplementedError("use_KAN / scene_embed / chord_embed are outside this path")
-        if d_model % 32 != 0 or d_hidden % 32 != 0:
+        if d_model % 32 != 0 or (d_hidden % 32 != 0 and regModel != "moemamba"):       # 'moemamba': d_hidden is d_state, no GEMM's K
             raise ValueError("d_model and d_hidden must be multiples of 32 (GEMM K step)")
+        if d_model > 512 and regModel not in ("lstm", "bilstm", "gru", "bigru", "cnngru", "cnnbigru"):
+            raise ValueError("the Mamba regModels take d_model <= 512: dt_rank = ceil(d_model / 16) must fit the 32 columns of `dbc` that the "
+                             "dt projection reads")
         self.n_layers, self.d_model, self.d_hidden = n_layers, d_model, d_hidden
         self.max_seq_video, self.total_vf_dim, self.regModel = max_sequence_video, total_vf_dim, regModel
         self._rnn = regModel in ("lstm", "bilstm", "gru", "bigru", "cnngru", "cnnbigru")
