@@ -567,6 +567,16 @@ def norm_inputs(rows, dim):
     return dict(x=f(rows, dim, scale=3.0), resid=f(rows, dim), post=f(rows, dim), w=f(dim), b=f(dim))
 
 
+@functools.lru_cache(maxsize=None)
+def norm_inputs_small_variance(rows, dim, std):
+    """`norm_inputs` with every second row of x and resid scaled to standard deviation `std`: with std^2 near a norm's epsilon the
+    output depends on the epsilon, which rows of unit scale cannot show."""
+    inp = {k: v.copy() for k, v in norm_inputs(rows, dim).items()}
+    inp["x"][1::2] *= np.float32(std / 3.0)
+    inp["resid"][1::2] *= np.float32(std)
+    return inp
+
+
 def layernorm64(x, w, b, eps=1e-5):
     x = x.astype(np.float64)
     mu = x.mean(-1, keepdims=True)

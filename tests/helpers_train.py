@@ -99,8 +99,11 @@ class Masks(list):
         self.p = p
 
 
-def forward(P, cfg, bt, masks=None, causal=True):
-    """Logits (B, L, 159) from parameters P {key: tensor} (any float dtype and device; they may require grad) and a `batch`."""
+def forward(P, cfg, bt, masks=None, causal=True, eps=1e-5, pe_offset=0, pre_relu=None):
+    """Logits (B, L, 159) from parameters P {key: tensor} (any float dtype and device; they may require grad) and a `batch`.  `eps`
+    and `pe_offset` (the first positional-encoding row) are the model's 1e-5 and 0; tests/helpers_train_edges.py moves them to state
+    wrong variants; a list given as `pre_relu` collects every feed-forward pre-activation, from which it reads how far the case's ReLUs
+    are from their kink."""
     dt, dev = P["Wout.weight"].dtype, P["Wout.weight"].device
     H = cfg["num_heads"]
     t = lambda a: torch.as_tensor(np.asarray(a)).to(dev, dt)
@@ -108,11 +111,16 @@ def forward(P, cfg, bt, masks=None, causal=True):
     def drop(x):
         return x if masks is None else x * masks.pop(0).to(dev, dt).view(x.shape)
 
+    def relu(z):
+        if pre_relu is not None:
+            pre_relu.append(z.detach())
+        return torch.relu(z)
+
     def ln(pre, x):
-        return F.layer_norm(x, (x.shape[-1],), P[pre + ".weight"], P[pre + ".bias"], 1e-5)
+        return F.layer_norm(x, (x.shape[-1],), P[pre + ".weight"], P[pre + ".bias"], eps)
 
     def pe(n, d):
-        pos = torch.arange(n, dtype=torch.float32)[:, None]
+        pos = torch.arange(n, dtype=torch.float32)[:, None] + pe_offset
         div = torch.exp(torch.arange(0, d, 2).float() * (-np.log(10000.0) / d))
         out = torch.zeros(n, d)
         out[:, 0::2], out[:, 1::2] = torch.sin(pos * div), torch.cos(pos * div)
@@ -132,7 +140,7 @@ def forward(P, cfg, bt, masks=None, causal=True):
     for i in range(cfg["n_layers"]):
         pre = f"transformer.encoder.layers.{i}."
         mem = ln(pre + "norm1", mem + drop(mha(P, pre + "self_attn.", mem, mem, H, False, masks)))
-        h = drop(torch.relu(F.linear(mem, P[pre + "linear1.weight"], P[pre + "linear1.bias"])))
+        h = drop(relu(F.linear(mem, P[pre + "linear1.weight"], P[pre + "linear1.bias"])))
         mem = ln(pre + "norm2", mem + drop(F.linear(h, P[pre + "linear2.weight"], P[pre + "linear2.bias"])))
     mem = ln("transformer.encoder.norm", mem)
     y = xf
@@ -140,7 +148,7 @@ def forward(P, cfg, bt, masks=None, causal=True):
         pre = f"transformer.decoder.layers.{i}."
         y = ln(pre + "norm1", y + drop(mha(P, pre + "self_attn.", y, y, H, causal, masks)))
         y = ln(pre + "norm2", y + drop(mha(P, pre + "multihead_attn.", y, mem, H, False, masks)))
-        h = drop(torch.relu(F.linear(y, P[pre + "linear1.weight"], P[pre + "linear1.bias"])))
+        h = drop(relu(F.linear(y, P[pre + "linear1.weight"], P[pre + "linear1.bias"])))
         y = ln(pre + "norm3", y + drop(F.linear(h, P[pre + "linear2.weight"], P[pre + "linear2.bias"])))
     y = ln("transformer.decoder.norm", y)
     assert masks is None or not masks
@@ -156,10 +164,10 @@ def loss(logits, bt, smoothing=SMOOTHING, lam=LAM):
     return lam * chord + (1 - lam) * emotion, chord, emotion
 
 
-def grads(sd, cfg, bt, dtype, masks=None, smoothing=SMOOTHING):
+def grads(sd, cfg, bt, dtype, masks=None, smoothing=SMOOTHING, causal=True):
     """(losses (3,), logits, {key: gradient or None}) of the restatement in `dtype`."""
     P = {k: torch.as_tensor(np.asarray(v)).to(dtype).requires_grad_(True) for k, v in sd.items()}
-    logits = forward(P, cfg, bt, masks)
+    logits = forward(P, cfg, bt, masks, causal)
     total, chord, emotion = loss(logits, bt, smoothing)
     total.backward()
     return (np.array([float(total.detach()), float(chord.detach()), float(emotion.detach())]), logits.detach().numpy(),

@@ -3,7 +3,10 @@ F.layer_norm(x (+ resid), w, b): the gradients of x, resid, w and b.
 
 Bound per tensor, the one tests/test_rnn_train_gpu.py established: err = max|g - g64| / max|g64| <= max(8 err_torch32, n 2^-24), with
 err_torch32 torch's own fp32 CPU autograd on the same inputs and n the longest sum's length: `dim` values inside a row (the statistics
-and the two means of dx), `rows` terms of a column of dw / db -- n = max(rows, dim)."""
+and the two means of dx), `rows` terms of a column of dw / db -- n = max(rows, dim).
+
+Every third row of x (and resid) is scaled by SMALL = 3e-3, so that its variance is near eps: on rows of unit variance no epsilon shows
+(test_a_wrong_epsilon_shows_on_the_small_variance_rows_only)."""
 import numpy as np
 import pytest
 import torch
@@ -16,6 +19,7 @@ from video2music_amd.autograd import LayerNormFn
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 EPS = 1e-5
+SMALL = 3e-3                            # rows 1, 4, 7, ... of x and resid: variance about 1e-5, the epsilon itself
 CASES = [(rows, dim, resid) for rows in (1, 37, 600) for dim in (32, 100, 512, 1024) for resid in (False, True)]
 
 
@@ -25,13 +29,15 @@ def inputs(rows, dim, resid):
          "dy": rng.standard_normal((rows, dim))}
     if resid:
         a["resid"] = 0.5 * rng.standard_normal((rows, dim))
+        a["resid"][1::3] *= SMALL
+    a["x"][1::3] *= SMALL
     return {k: v.astype(np.float32) for k, v in a.items()}
 
 
-def torch_cpu(a, dtype):
+def torch_cpu(a, dtype, eps=EPS):
     t = {k: torch.from_numpy(v).to(dtype).requires_grad_(k != "dy") for k, v in a.items()}
     u = t["x"] + t["resid"] if "resid" in t else t["x"]
-    y = F.layer_norm(u, (u.shape[1],), t["w"], t["b"], EPS)
+    y = F.layer_norm(u, (u.shape[1],), t["w"], t["b"], eps)
     y.backward(t["dy"])
     out = {k: t[k].grad.numpy() for k in t if k != "dy"}
     out["y"] = y.detach().numpy()
@@ -61,6 +67,20 @@ def test_gradients_against_fp64(rows, dim, resid):
         assert err <= bound, (k, err, e32, bound)
     if resid:
         assert np.array_equal(got["x"], got["resid"])                    # one gradient for both addends
+
+
+@pytest.mark.parametrize("rows,dim,resid", [(37, 100, True), (600, 512, False), (600, 1024, True)])
+def test_a_wrong_epsilon_shows_on_the_small_variance_rows_only(rows, dim, resid):
+    """Host side, fp64: eps = 1e-6 in place of 1e-5 misses the bound of test_gradients_against_fp64 by over 10 times on the rows scaled
+    by SMALL, in y and in dx alike, and stays inside it on the rows of unit variance -- the rows these cases had before."""
+    a = inputs(rows, dim, resid)
+    g64, g32, wrong = torch_cpu(a, torch.float64), torch_cpu(a, torch.float32), torch_cpu(a, torch.float64, eps=1e-6)
+    small = np.zeros(rows, dtype=bool)
+    small[1::3] = True
+    for k in ("y", "x"):
+        bound = max(8 * rel_err(g32[k], g64[k]), max(rows, dim) * U)
+        d = np.abs(wrong[k] - g64[k]).max(axis=1) / np.abs(g64[k]).max()
+        assert d[small].max() >= 10 * bound and d[~small].max() <= bound, (k, d[small].max(), d[~small].max(), bound)
 
 
 def test_more_rows_than_the_workgroup_cap_spreads():

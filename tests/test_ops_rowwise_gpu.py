@@ -51,6 +51,39 @@ def test_norms(rows, dim):
     assert max(errs.values()) < TOL, errs
 
 
+@pytest.mark.parametrize("rows,dim", [(6, 36), (6, 260)])
+def test_norms_use_the_epsilon_they_are_given(rows, dim):
+    """`norm_inputs` has rows of variance 9 (1 for resid): no epsilon moves their output by TOL.  Here every second row has a variance
+    near the epsilon (3e-3 squared against 1e-5 for LayerNorm, 1e-3 squared against 1e-6 for RMSNorm), held to the same TOL; the fp64
+    reference with the other epsilon misses it by over 10 times on those rows and stays inside it on the others."""
+    errs = {}
+
+    def run(tag, fn, args, ref, wrong):
+        y = H.Guarded(rows * dim)
+        _lib.call(fn, *args(C.c_void_p(y.addr())), _sp())
+        errs[tag] = float(np.abs(_finish(y, rows, dim) - ref).max())
+        assert np.abs(wrong - ref)[1::2].max() >= 10 * TOL and np.abs(wrong - ref)[0::2].max() < TOL, tag
+
+    inp = H.norm_inputs_small_variance(rows, dim, 3e-3)
+    x, r, post, w, b = (inp[k] for k in ("x", "resid", "post", "w", "b"))
+    dx, dr, dp, dw, db = (H.dev(v) for v in (x, r, post, w, b))
+    run("layernorm", "amt_layernorm_fwd", lambda y: (P(dx), None, P(dw), P(db), y, rows, dim, 1e-5), H.layernorm64(x, w, b), H.layernorm64(x, w, b, 1e-6))
+    run("layernorm+resid", "amt_layernorm_fwd", lambda y: (P(dx), P(dr), P(dw), P(db), y, rows, dim, 1e-5), H.layernorm64(x + r, w, b),
+        H.layernorm64(x + r, w, b, 1e-6))
+    p64 = post.astype(np.float64)
+    run("layernorm_post resid+post", "amt_layernorm_post_fwd", lambda y: (P(dx), P(dr), P(dw), P(db), P(dp), y, rows, dim, 1e-5),
+        H.layernorm64(x + r, w, b) + p64, H.layernorm64(x + r, w, b, 1e-6) + p64)
+    # another value than the entry point's usual one is taken as given
+    run("layernorm eps 1e-6", "amt_layernorm_fwd", lambda y: (P(dx), None, P(dw), P(db), y, rows, dim, 1e-6), H.layernorm64(x, w, b, 1e-6), H.layernorm64(x, w, b))
+    inp = H.norm_inputs_small_variance(rows, dim, 1e-3)
+    x, r, w = inp["x"], inp["resid"], inp["w"]
+    dx, dr, dw = (H.dev(v) for v in (x, r, w))
+    run("rmsnorm", "amt_rmsnorm_fwd", lambda y: (P(dx), P(dw), y, rows, dim, 1e-6), H.rmsnorm64(x, w), H.rmsnorm64(x, w, 1e-5))
+    run("rmsnorm_resid", "amt_rmsnorm_resid_fwd", lambda y: (P(dx), P(dr), P(dw), y, rows, dim, 1e-6), H.rmsnorm64(x + r, w), H.rmsnorm64(x + r, w, 1e-5))
+    print(f"small-variance norms rows={rows} dim={dim}: " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    assert max(errs.values()) < TOL, errs
+
+
 @pytest.mark.parametrize("dim", H.NORM_REFUSED)
 def test_norms_refuse_bad_widths(dim):
     x = torch.zeros(2 * 2052, device="cuda")
