@@ -37,7 +37,7 @@
 #define AMT_HIP_H
 #include <stdint.h>
 
-#define AMT_ABI_VERSION 8    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
+#define AMT_ABI_VERSION 9    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
                                 3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights;
                                 4: amt_chord_metrics_fwd;
                                 5: amt_reg_metrics_fwd;
@@ -45,7 +45,8 @@
                                 7: amt_attn_train_fwd, amt_attn_bwd, amt_attn_bwd_ws_floats, amt_layernorm_bwd, amt_chord_loss_fwd_bwd,
                                    amt_chord_loss_ws_floats;
                                 8: amt_selective_scan_train_fwd, amt_selective_scan_bwd, amt_selective_scan_bwd_ws_floats,
-                                   amt_dwconv1d_silu_bwd, amt_dwconv1d_silu_bwd_ws_floats */
+                                   amt_dwconv1d_silu_bwd, amt_dwconv1d_silu_bwd_ws_floats;
+                                9: amt_gemm_route, amt_attn_route */
 
 #ifdef __cplusplus
 extern "C" {
@@ -503,6 +504,11 @@ int32_t amt_concat2_fwd(const float* a, int32_t da, const float* b, int32_t db, 
  * K % 32 == 0. */
 int32_t amt_linear_ex_fwd(const float* x, int32_t ldx, const float* w, int32_t ldw, const float* bias, const float* resid,
                           int32_t ldr, float* y, int32_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
+/* Which kernel the dense GEMM launcher takes for y (M, N) = act(x (M, K) w (N, K)^T ...): 0 the skinny GEMM, 1 the 64x64-tile kernel,
+ * 2 the 128x128-tile kernel; negative for a shape or act amt_linear_ex_fwd refuses.  act as amt_linear_ex_fwd's; other_forms != 0
+ * stands for the operand and epilogue forms only the library's own callers set (head-split store, row addend, silu-multiply,
+ * grouped or gathered rows).  The launcher's own rule, evaluated on the host: no device, no stream; a code, not a status. */
+int32_t amt_gemm_route(int32_t M, int32_t N, int32_t K, int32_t act, int32_t other_forms);
 /* y = LayerNorm(x (+ resid)) + post : the "norm2(x_b + x) then x_f + x_b" step of bimamba.py:183-188 in one pass. */
 int32_t amt_layernorm_post_fwd(const float* x, const float* resid, const float* w, const float* b, const float* post,
                                float* y, int32_t rows, int32_t dim, float eps, void* stream);
@@ -588,6 +594,10 @@ int32_t amt_attn_train_fwd(const float* q, const float* k, const float* v, float
  * of every addition is a function of the shapes alone.  With Er: kv_group 1.  Head dims 32, 64, 128.
  * ws: amt_attn_bwd_ws_floats(B, H, Lq, Lk, hd, Er != null) floats of scratch, 16-byte aligned, this call's alone until it finishes
  * (184 MB at 32 clips x 8 heads x 299 x 299, 226 MB with Er). */
+/* Which prefill kernel amt_rpr_attn_fwd / amt_cross_attn_fwd / amt_attn_fwd / amt_attn_train_fwd take for a shape: 0 the 128-row
+ * kernel, 1 the split-key kernel (32-row blocks, keys split over the waves); negative for a shape they refuse.  has_er != 0: with a
+ * relative position table.  The launcher's own rule, evaluated on the host: no device, no stream; a code, not a status. */
+int32_t amt_attn_route(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t has_er);
 int64_t amt_attn_bwd_ws_floats(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t rpr);
 int32_t amt_attn_bwd(const float* dO, const float* q, const float* k, const float* v, const float* o, const float* lse,
                      const float* Er, int32_t er_len, const uint8_t* keep, float keep_scale, float* dq, float* dk, float* dv,

@@ -1,8 +1,8 @@
 """Case table, input builders and bounds of the family forward parity tests: the teacher-forced eval forward of
 VideoMusicTransformer_V1 / _V2 / _V3 against `oracle.amt_oracle.forward_family` in float64 (test_family_parity_host.py checks the
-table on the CPU, test_family_forward_parity_gpu.py runs it on the GPU).  Nothing here imports the model classes or the HIP
-library: the state dicts are built from the key lists below (the GPU test checks them against the classes), the weights and video
-features are the procedural ones of `video2music_amd.synthetic`.
+table on the CPU, test_family_forward_parity_gpu.py runs it on the GPU).  Nothing here imports the model classes, and the HIP
+library is asked for launch routes only (tests/launch_routes.py; no GPU): the state dicts are built from the key lists below (the
+GPU test checks them against the classes), the weights and video features are the procedural ones of `video2music_amd.synthetic`.
 
 Every case names the edge it exists for.  Shapes (d_model, heads, L chord positions, S frames, B clips):
   s1  128, 4 (head_dim 32),  L 300, S 300, B 2   every attention on the split-key kernel (Lk 300, 24 workgroups), for V3 through the
@@ -32,7 +32,8 @@ import torch
 
 from oracle import amt_oracle as O
 from video2music_amd import synthetic
-from tests.helpers_ops_edges import AttnCase, GemmCase, attn_expected_kernel, gemm_expected_route
+from tests import launch_routes as R
+from tests.helpers_ops_edges import AttnCase
 
 ROUTE_GAP = 1e-5            # smallest relative 2nd-vs-3rd gate-logit gap a row may have (test_lockstep_parity_gpu.py)
 BOUND_FACTOR = 8.0
@@ -45,17 +46,17 @@ RMS_GAIN = 0.1              # scale of every norm gain in the rms_norm=True case
 
 Shape = namedtuple("Shape", "d H L S B dff attn gemm what")
 SHAPES = {
-    "s1": Shape(128, 4, 300, 300, 2, 192, dict(enc="splitk", self="splitk", cross="splitk"), {"skinny", "t64"},
+    "s1": Shape(128, 4, 300, 300, 2, 192, dict(enc="splitk", self="splitk", cross="splitk"), {"skinny", "tile64"},
                 "split-key kernel in every attention (Lk 300), three query blocks, 600 tokens per mixture layer"),
-    "s2": Shape(256, 4, 257, 256, 1, 192, dict(enc="splitk", self="splitk", cross="splitk"), {"skinny", "t64"},
+    "s2": Shape(256, 4, 257, 256, 1, 192, dict(enc="splitk", self="splitk", cross="splitk"), {"skinny", "tile64"},
                 "Lk at the 256 threshold in the cross-attention; a one-row last query block and a ragged last key tile"),
-    "s3": Shape(256, 2, 129, 17, 3, 192, dict(enc="rows128", self="rows128", cross="rows128"), {"skinny", "t64"},
+    "s3": Shape(256, 2, 129, 17, 3, 192, dict(enc="rows128", self="rows128", cross="rows128"), {"skinny", "tile64"},
                 "128-row kernel at head_dim 128; B = 3 through the raw views; S below one key tile"),
-    "s4": Shape(128, 8, 33, 120, 2, 192, dict(enc="rows128", self="rows128", cross="rows128"), {"skinny", "t64"},
+    "s4": Shape(128, 8, 33, 120, 2, 192, dict(enc="rows128", self="rows128", cross="rows128"), {"skinny", "tile64"},
                 "head_dim 16 in the attention and in diff_subln"),
-    "s5": Shape(128, 4, 1, 1, 1, 192, dict(enc="rows128", self="rows128", cross="rows128"), {"skinny", "t64"},
+    "s5": Shape(128, 4, 1, 1, 1, 192, dict(enc="rows128", self="rows128", cross="rows128"), {"skinny", "tile64"},
                 "one query, one key, one frame"),
-    "s6": Shape(512, 8, 40, 300, 2, 1024, dict(enc="splitk", self="rows128", cross="splitk"), {"skinny", "t64"},
+    "s6": Shape(512, 8, 40, 300, 2, 1024, dict(enc="splitk", self="rows128", cross="splitk"), {"skinny", "tile64"},
                 "dim_feedforward 1024: plain products up to 614400 outputs on the skinny GEMM, fused epilogues on the 64-tile kernel"),
 }
 
@@ -309,14 +310,13 @@ def attention_calls(c):
 
 
 def gemm_calls(c):
-    """The GEMM launches of the forward of case `c` as GemmCase rows.  act 0: plain epilogue (bias, residual); act 3 stands for every
-    epilogue or operand form the skinny kernel does not have (SiLU, the silu-multiply of the GLU up branch, grouped / gathered expert
-    rows), which the launcher keeps on the tiled kernels."""
+    """The GEMM launches of the forward of case `c` as launch_routes.GemmCall rows.  act 0: plain epilogue (bias, residual), act 3: SiLU;
+    other: a form only the library's own callers set (the silu-multiply of the GLU up branch, grouped / gathered expert rows)."""
     s = SHAPES[c.shape]
     d, hd = s.d, s.d // s.H
     pad32 = lambda n: (n + 31) // 32 * 32
     out = []
-    g = lambda tag, M, N, K, act=0: out.append(GemmCase(tag, "plain", M, N, K, act, True, False, 0, 0, 0, 0, 0, None, None, ""))
+    g = lambda tag, M, N, K, act=0, other=False: out.append(R.GemmCall(tag, M, N, K, act, other))
 
     def attn(tag, kind, nq, nk):
         w = 2 * d if kind == "diff" else d
@@ -325,15 +325,16 @@ def gemm_calls(c):
     def ffn(tag, plan, n):
         kind, shared, grouped = ("glu", True, False) if plan == "glu" else (plan[0], plan[1], True)
         dff = pad32(s.dff) if kind == "glu" else 2 * d
+        silu = 0 if kind == "glu" else 3                         # the SiLU experts' one activation sits in their gate product
         if grouped:
             rows = 2 * n                                         # top-2 rows sorted by expert (plus the plan's per-expert tile padding)
-            g(tag + ".experts.gate", rows, dff, d, 3), g(tag + ".experts.down", rows, d, dff, 3)
+            g(tag + ".experts.gate", rows, dff, d, silu, other=True), g(tag + ".experts.down", rows, d, dff, other=True)
             if kind == "glu":
-                g(tag + ".experts.up", rows, dff, d, 3)
+                g(tag + ".experts.up", rows, dff, d, other=True)
         if shared:
-            g(tag + ".gate", n, dff, d, 0 if kind == "glu" else 3), g(tag + ".down", n, d, dff)
+            g(tag + ".gate", n, dff, d, silu), g(tag + ".down", n, d, dff)
             if kind == "glu":
-                g(tag + ".up", n, dff, d, 3)
+                g(tag + ".up", n, dff, d, other=True)
 
     g("Linear_vis", s.S * s.B, d, pad32(synthetic.total_vf_dim(1)))
     for i in range(c.n_layers):
@@ -346,8 +347,8 @@ def gemm_calls(c):
 
 
 def routes(c):
-    """(attention kernels by call, set of GEMM routes) under the dispatch rules restated in helpers_ops_edges.py."""
-    return {k: attn_expected_kernel(a) for k, a in attention_calls(c).items()}, {gemm_expected_route(q) for q in gemm_calls(c)}
+    """(attention kernels by call, set of GEMM routes) as the library's launchers answer (tests/launch_routes.py)."""
+    return {k: R.attn_route(a.B, a.H, a.Lq, a.Lk, a.hd) for k, a in attention_calls(c).items()}, {R.route_of(q) for q in gemm_calls(c)}
 
 
 # ---- wrong variants for the sensitivity check ----------------------------------------------------------------------------------------

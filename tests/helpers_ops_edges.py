@@ -3,8 +3,8 @@ test_gemm_routes_gpu.py, test_attn_strided_gpu.py, test_moe_plan_gpu.py, test_op
 
 The restatements are plain numpy / torch in float64, written from the contracts of include/amt_hip.h and from
 oracle/amt_oracle.py; nothing here calls the library.  Every case names the route, kernel or plan edge it exists for
-(`edge`): the routes are those of csrc/gemm_f32.hip, csrc/attn_prefill.hip and csrc/moe.hip under the defaults of
-csrc/amt_common.h (gemm_small_m = 4096, gemm_small_mn = 650000, gemm_t64_below = 768).
+(`edge`): the routes are those of csrc/gemm_f32.hip, csrc/attn_prefill.hip and csrc/moe.hip at the boundaries of
+tests/launch_routes.py, where test_ops_edges_host.py asks the library for the route of every GEMM and attention case.
 
 Tolerances come from the project (2e-5: test_linear, test_cross_attention_prefill; 1e-6: test_moe_other_top_k_vs_oracle;
 1e-4: fuzz_parity.py) or from a restatement of the arithmetic run here on the CPU -- never from the code under test.
@@ -14,6 +14,8 @@ from collections import namedtuple
 
 import numpy as np
 import torch
+
+from tests.launch_routes import vec_ok
 
 SENTINEL = np.float32(-7.0e37)          # written everywhere an output buffer must stay untouched; compared as bits
 GUARD = 64                              # floats in front of and behind every output buffer (keeps 16-byte alignment)
@@ -37,50 +39,41 @@ def untouched(buf, written_mask):
 GemmCase = namedtuple("GemmCase", "name entry M N K act bias resid dx dw dy dr xcol route vec edge")
 
 
-def _g(name, M, N, K, act=0, bias=True, resid=False, dx=0, dw=0, dy=0, dr=0, xcol=0, entry="ex", route="t64", vec=None, edge=""):
-    if vec is None:       # the clauses of vec_ok in gemm_f32.hip (the skinny kernel has one element-wise epilogue)
-        vec = route != "skinny" and N % 4 == 0 and (N + dy) % 4 == 0 and (not resid or (N + dr) % 4 == 0)
+def _g(name, M, N, K, act=0, bias=True, resid=False, dx=0, dw=0, dy=0, dr=0, xcol=0, entry="ex", route="tile64", edge=""):
+    vec = route != "skinny" and vec_ok(N, N + dy, N + dr if resid else None)      # the skinny kernel has one element-wise epilogue
     return GemmCase(name, entry, M, N, K, act, bias, resid, dx, dw, dy, dr, xcol, route, vec, edge)
 
 
 GEMM_CASES = [
-    # ---- skinny route: act 0 / 1, K <= 1536, M <= 4096, M*N <= 650000 ----
+    # ---- skinny route: act 0 / 1, K, M and M*N within the skinny boundaries ----
     _g("skinny_1x16x32", 1, 16, 32, route="skinny", edge="skinny GEMM, one row, one k-tile pair, one column tile"),
     _g("skinny_strided", 33, 159, 96, act=1, resid=True, dx=4, dw=8, dy=1, dr=3, xcol=8, route="skinny",
        edge="skinny GEMM through ldw (un-packed weights) with ldx, ldy, ldr all different from K / N, ragged row block and column tile"),
     _g("skinny_under_switch", 4096, 158, 64, entry="plain", route="skinny",
-       edge="M*N = 647168, just under the 650000 route switch: the last shape on the skinny GEMM"),
+       edge="M*N = 647168, just under the route switch: the last shape on the skinny GEMM"),
     # ---- route-switch partners: the 64x64 tile ----
-    _g("t64_over_switch", 4096, 159, 64, entry="plain", route="t64",
+    _g("t64_over_switch", 4096, 159, 64, entry="plain", route="tile64",
        edge="M*N = 651264, just over the switch: 64-tile kernel, N % 4 != 0 so the element-wise epilogue, nk = 2"),
-    _g("t64_over_small_m", 4097, 16, 64, entry="plain", route="t64",
-       edge="M = 4097 > gemm_small_m: 64-tile kernel with a one-row last row tile, vector epilogue, 65 tiles (65 mod 8 = 1)"),
+    _g("t64_over_small_m", 4097, 16, 64, entry="plain", route="tile64",
+       edge="M = 4097, one row over the skinny limit: 64-tile kernel with a one-row last row tile, vector epilogue, 65 tiles (65 mod 8 = 1)"),
     # ---- 64-tile kernel because the activation or K excludes the skinny route ----
-    _g("t64_sigmoid_nk1", 5, 40, 32, act=2, route="t64", edge="sigmoid keeps a small product off the skinny route; nk = 1: the second prefetch stage re-reads k-tile 0"),
-    _g("t64_silu_nk3", 70, 132, 96, act=3, route="t64", edge="SiLU on the 64-tile kernel; odd nk = 3; 6 tiles, fewer than the 8 XCDs of the tile remap"),
-    _g("t64_sigmoid_resid_elt", 130, 66, 64, act=2, resid=True, route="t64", edge="sigmoid + residual, N % 4 != 0: element-wise epilogue of the 64-tile kernel"),
-    _g("t64_silu_resid_elt", 130, 66, 64, act=3, resid=True, route="t64", edge="SiLU + residual, N % 4 != 0: element-wise epilogue of the 64-tile kernel"),
-    _g("t64_long_k", 15, 64, 1568, route="t64", edge="K = 1568 > 1536 keeps 15 rows off the skinny route; nk = 49, odd"),
-    _g("t64_wgrad_k9600", 96, 40, 9600, route="t64", edge="the weight-gradient shape class of the autograd (K = 9600, nk = 300)"),
+    _g("t64_sigmoid_nk1", 5, 40, 32, act=2, route="tile64", edge="sigmoid keeps a small product off the skinny route; nk = 1: the second prefetch stage re-reads k-tile 0"),
+    _g("t64_silu_nk3", 70, 132, 96, act=3, route="tile64", edge="SiLU on the 64-tile kernel; odd nk = 3; 6 tiles, fewer than the 8 XCDs of the tile remap"),
+    _g("t64_sigmoid_resid_elt", 130, 66, 64, act=2, resid=True, route="tile64", edge="sigmoid + residual, N % 4 != 0: element-wise epilogue of the 64-tile kernel"),
+    _g("t64_silu_resid_elt", 130, 66, 64, act=3, resid=True, route="tile64", edge="SiLU + residual, N % 4 != 0: element-wise epilogue of the 64-tile kernel"),
+    _g("t64_long_k", 15, 64, 1568, route="tile64", edge="K = 1568 > 1536 keeps 15 rows off the skinny route; nk = 49, odd"),
+    _g("t64_wgrad_k9600", 96, 40, 9600, route="tile64", edge="the weight-gradient shape class of the autograd (K = 9600, nk = 300)"),
     # ---- each clause of vec_ok ----
-    _g("vec_all_mult4", 130, 64, 64, act=3, resid=True, route="t64", edge="vec_ok: every leading dimension a multiple of 4: vector epilogue through the LDS transpose"),
-    _g("vec_ldy_odd", 130, 64, 64, act=3, resid=True, dy=2, route="t64", edge="vec_ok clause ldc % 4: ldy = N + 2 falls back to the element-wise epilogue"),
-    _g("vec_ldr_odd", 130, 64, 64, act=3, resid=True, dr=2, route="t64", edge="vec_ok clause ldr % 4: ldr = N + 2 falls back to the element-wise epilogue"),
-    _g("vec_padded", 130, 64, 64, act=3, resid=True, dy=4, dr=8, route="t64", edge="vector epilogue with ldy = N + 4, ldr = N + 8: 16-byte stores must leave the padding columns alone"),
+    _g("vec_all_mult4", 130, 64, 64, act=3, resid=True, route="tile64", edge="vec_ok: every leading dimension a multiple of 4: vector epilogue through the LDS transpose"),
+    _g("vec_ldy_odd", 130, 64, 64, act=3, resid=True, dy=2, route="tile64", edge="vec_ok clause ldc % 4: ldy = N + 2 falls back to the element-wise epilogue"),
+    _g("vec_ldr_odd", 130, 64, 64, act=3, resid=True, dr=2, route="tile64", edge="vec_ok clause ldr % 4: ldr = N + 2 falls back to the element-wise epilogue"),
+    _g("vec_padded", 130, 64, 64, act=3, resid=True, dy=4, dr=8, route="tile64", edge="vector epilogue with ldy = N + 4, ldr = N + 8: 16-byte stores must leave the padding columns alone"),
     # ---- 128x128 tile: K >= 2048 and at least 768 tiles ----
-    _g("t128_vec", 3100, 4100, 2048, resid=True, route="t128",
+    _g("t128_vec", 3100, 4100, 2048, resid=True, route="tile128",
        edge="128-tile kernel, 25 x 33 = 825 tiles (825 mod 8 = 1 in the XCD remap), ragged last row and column tile, vector epilogue"),
-    _g("t128_silu_elt", 3100, 4101, 2048, act=3, route="t128", edge="128-tile kernel with N % 4 != 0: element-wise epilogue on the big tile, SiLU"),
+    _g("t128_silu_elt", 3100, 4101, 2048, act=3, route="tile128", edge="128-tile kernel with N % 4 != 0: element-wise epilogue on the big tile, SiLU"),
 ]
 GEMM_BY_NAME = {c.name: c for c in GEMM_CASES}
-
-
-def gemm_expected_route(c):
-    """The dispatch of amt_launch_gemm restated: what the case's comment claims must be what the launcher does."""
-    if c.M <= 4096 and c.M * c.N <= 650000 and c.K % 32 == 0 and c.K <= 1536 and c.act in (0, 1):
-        return "skinny"
-    t128 = -(-c.M // 128) * -(-c.N // 128)
-    return "t128" if (t128 >= 768 and c.K >= 2048) else "t64"
 
 
 @functools.lru_cache(maxsize=None)
@@ -199,11 +192,6 @@ SPLITK_PAIRS = [(1, 300, 0, "one query row, 10 key tiles over the four waves"),
                 (257, 257, 1, "causal, ragged last key tile and a one-row last block"),
                 (77, 300, 1, "causal, last row block partly filled"),
                 (300, 257, 1, "causal with Lq > Lk: rows past Lk see every key")]
-
-
-def attn_expected_kernel(c):
-    grid128 = -(-c.Lq // 128) * c.H * c.B
-    return "splitk" if (c.hd in (32, 64) and grid128 < 512 and c.Lk >= 256) else "rows128"
 
 
 def _attn_cases():

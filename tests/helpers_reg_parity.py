@@ -26,7 +26,7 @@ import torch
 from oracle import reg_oracle as R
 from video2music_amd import synthetic
 from tests.helpers_family_parity import BOUND_FACTOR, CAP, ROUTE_GAP, SENSITIVITY, chosen, rel_err, route_gap       # noqa: F401 (re-exported)
-from tests.helpers_ops_edges import GemmCase, gemm_expected_route
+from tests import launch_routes as LR
 
 REG_MODELS = ("bimamba+", "bimamba", "mamba", "mamba+", "moe_bimamba+", "sharedmoe_bimamba+", "moemamba", "lstm", "bilstm", "gru", "bigru",
               "cnngru", "cnnbigru")
@@ -46,7 +46,7 @@ RegCase = namedtuple("RegCase", "name rm d dh vf B S n_layers seed gemm edge")
 
 def _c(rm, d, dh, vf, B, S, n_layers, seed, edge):
     name = f"{rm.replace('+', 'p')}_{d}_{dh}_{vf}_{B}x{S}_L{n_layers}"
-    return RegCase(name, rm, d, dh, vf, B, S, n_layers, seed, frozenset({"skinny", "t64"}), edge)
+    return RegCase(name, rm, d, dh, vf, B, S, n_layers, seed, frozenset({"skinny", "tile64"}), edge)
 
 
 # seed: of the weights (seed) and of the inputs (seed + 1000).  The seeds listed are those whose mixture layers keep every row's 2nd-vs-3rd
@@ -259,21 +259,21 @@ def n_mixture_layers(c):
 
 # ---- what the forward issues ---------------------------------------------------------------------------------------------------------
 def gemm_calls(c):
-    """The GEMM launches of `forward` for case `c` as GemmCase rows.  act 0 / 1 / 2: plain, ReLU, sigmoid epilogue; act 3 stands for the SiLU
-    epilogue and for the products inside the fused mixture layer (silu-multiply, grouped expert rows), which stay on the tiled kernels."""
+    """The GEMM launches of `forward` for case `c` as launch_routes.GemmCall rows.  act 0 / 1 / 2 / 3: plain, ReLU, sigmoid, SiLU epilogue;
+    other: the products inside the fused mixture layer (silu-multiply, grouped expert rows), forms only the library's own callers set."""
     q = derived(c)
     d, M = c.d, c.B * c.S
     out = []
-    g = lambda tag, M_, N, K, act=0: out.append(GemmCase(tag, "ex", M_, N, K, act, True, False, 0, 0, 0, 0, 0, None, None, ""))
+    g = lambda tag, M_, N, K, act=0, other=False: out.append(LR.GemmCall(tag, M_, N, K, act, other))
 
     def mamba(tag):
         g(tag + ".in_proj", M, 4 * d, d), g(tag + ".x_proj", M, q["ldbc"], 2 * d), g(tag + ".dt_proj", M, 2 * d, 32), g(tag + ".out_proj", M, d, 2 * d)
 
     def moe(tag, shared):
         w = (q["expert_width"] + 31) // 32 * 32
-        g(tag + ".experts.up", 2 * M, w, d, 3), g(tag + ".experts.gate", 2 * M, w, d, 3), g(tag + ".experts.down", 2 * M, d, w, 3)
+        g(tag + ".experts.up", 2 * M, w, d, other=True), g(tag + ".experts.gate", 2 * M, w, d, other=True), g(tag + ".experts.down", 2 * M, d, w, other=True)
         if shared:
-            g(tag + ".shared.up", M, w, d, 3), g(tag + ".shared.gate", M, w, d, 3), g(tag + ".shared.down", M, d, w, 3)
+            g(tag + ".shared.up", M, w, d, other=True), g(tag + ".shared.gate", M, w, d, other=True), g(tag + ".shared.down", M, d, w, other=True)
 
     g("in_proj", M, d, q["Fpad"])
     if c.rm.startswith("cnn"):
@@ -299,8 +299,8 @@ def gemm_calls(c):
 
 
 def routes(c):
-    """{GEMM tag: route} under the dispatch rule restated in helpers_ops_edges.py."""
-    return {q.name: gemm_expected_route(q) for q in gemm_calls(c)}
+    """{GEMM tag: route} as the library's launcher answers (tests/launch_routes.py)."""
+    return {q.name: LR.route_of(q) for q in gemm_calls(c)}
 
 
 # ---- wrong variants for the sensitivity check ----------------------------------------------------------------------------------------

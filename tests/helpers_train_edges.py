@@ -3,9 +3,8 @@ variants of tests/test_train_edges_host.py and tests/test_train_edges_gpu.py.  E
 tests/helpers_train.py (pinned to the reference's own fp64 gradients by tests/test_train_host.py); nothing is recorded.
 
 A case is named for the edge it exists for; its sizes are the smallest at which that route is taken (the host test derives the routes
-from the shapes with the launch rules read from the sources)."""
+from the shapes by asking the library, tests/launch_routes.py)."""
 import functools
-import os
 import re
 
 import numpy as np
@@ -13,7 +12,7 @@ import torch
 
 from tests import helpers_eval as HE
 from tests import helpers_train as T
-from video2music_amd import synthetic
+from tests import launch_routes as R
 from video2music_amd.utilities import constants as C
 
 P_DROP = 0.2
@@ -51,8 +50,8 @@ CASES = {
     "d96_h3": _case(D96, 3, 17, 37, 4),
     # one key everywhere: dS cancels, dEr is identically zero, the chord loss sees one row
     "one_by_one": _case(cfg_of(1, 1, 32, 32, 1, 7), 1, 1, 1, 5),
-    # M = 4200 > gemm_small_m with M N far below gemm_small_mn; weight gradients with K = 4224; LayerNorm backward above its 2048-row
-    # spread; dEr summed over 14 slabs
+    # M = 4200 rows: past the skinny GEMM's row limit, M N far below its output limit; weight gradients with K = 4224; LayerNorm
+    # backward above its 2048-row spread; dEr summed over 14 slabs
     "rows_gt_4096": _case(cfg_of(1, 1, 32, 32, 300, 32), 14, 40, 300, 6),
     # B L = 1677: weight-gradient K = 1696 > 1536 leaves the skinny GEMM while M N is small; L = 129: one row in the second query
     # block and in the fifth key tile
@@ -336,52 +335,7 @@ def variant_miss(name, variant):
     return max(errs.values()) / (GRAD_FACTOR * ref["e32"]), logit_err(y, ref["y64"]) / (LOGIT_FACTOR * ref["e32_y"]), errs
 
 
-# ---- the launch rules, written out; their thresholds are read from the sources ----
-
-def _src(name):
-    with open(os.path.join(os.path.dirname(os.path.abspath(synthetic.__file__)), "csrc", name)) as fh:
-        return fh.read()
-
-
-@functools.lru_cache(maxsize=None)
-def thresholds():
-    common, gemm, attn = _src("amt_common.h"), _src("gemm_f32.hip"), _src("attn_prefill.hip")
-
-    def one(pat, s):
-        found = re.findall(pat, s)
-        assert len(found) == 1, f"launch rule not found once in the sources: {pat!r} matched {found}"
-        return found[0]
-
-    return dict(small_m=int(one(r"long\s+gemm_small_m\s*=\s*(\d+)\s*;", common)), small_mn=int(one(r"long\s+gemm_small_mn\s*=\s*(\d+)\s*;", common)),
-                t64_below=int(one(r"int\s+gemm_t64_below\s*=\s*(\d+)\s*;", common)),
-                skinny_k=int(one(r"p\.K % 32 == 0 && p\.K <= (\d+) && !p\.head_split", gemm)),
-                big_k=int(one(r"t128 >= t64_below && p\.K >= (\d+);", gemm)),
-                split=tuple(int(x) for x in one(r"if \(!p\.Er && HD >= (\d+) && HD <= (\d+) && grid\.x < (\d+) && p\.Lk >= (\d+)\)", attn)),
-                QB=int(one(r"constexpr int QB\s*=\s*(\d+)\s*;", attn)))
-
-
-def gemm_route(M, N, K, act=0, resid=False, ldc=None):
-    """(kernel, epilogue) that `amt_launch_gemm` takes for y (M, N) = act(x (M, K) w (N, K)^T + b) (+ resid) as `ops.linear_ex` calls it
-    (ldc = ldr = N): kernel 'skinny' / 'tile64' / 'tile128'; epilogue the activation, '+resid', and 'elementwise' or 'vector' stores."""
-    t = thresholds()
-    assert K % 32 == 0
-    cdiv = lambda a, b: -(-a // b)
-    if M <= t["small_m"] and M * N <= t["small_mn"] and K <= t["skinny_k"] and act in (0, 1):
-        kernel = "skinny"
-    else:
-        kernel = "tile128" if cdiv(M, 128) * cdiv(N, 128) >= t["t64_below"] and K >= t["big_k"] else "tile64"
-    epi = {0: "none", 1: "relu", 2: "sigmoid"}[act] + ("+resid" if resid else "")
-    if kernel != "skinny":
-        epi += ":vector" if N % 4 == 0 else ":elementwise"
-    return kernel, epi
-
-
-def attn_route(B, H, Lq, Lk, hd, er):
-    """The forward attention kernel of `launch_hd`: 'splitk' (32-row blocks, keys split over the waves) or 'rows128'."""
-    lo, hi, grid_below, lk_min = thresholds()["split"]
-    grid = -(-Lq // thresholds()["QB"]) * H * B
-    return "splitk" if (not er and lo <= hd <= hi and grid < grid_below and Lk >= lk_min) else "rows128"
-
+# ---- what one training step launches ----
 
 def products(cfg, B, S, L):
     """Every dense product of one training step as (pass, name, M, N, K, act): the forward's LinearFn calls of `_forward_train` and what
@@ -428,8 +382,15 @@ def attentions(cfg, B, S, L):
             ("dec.multihead_attn", B, H, L, S, hd, False)]
 
 
+def gemm_kernel_and_epilogue(M, N, K, act=0):
+    """(the library's route, activation and on the tiled kernels 'vector' / 'elementwise' stores) of `ops.linear_ex` (ldc = N, no residual)."""
+    kernel = R.gemm_route(M, N, K, act)
+    epi = {0: "none", 1: "relu", 2: "sigmoid"}[act]
+    return kernel, epi if kernel == "skinny" else epi + (":vector" if R.vec_ok(N, N) else ":elementwise")
+
+
 def routes(cfg, B, S, L):
-    """{(pass, kernel, epilogue)} of the GEMMs and {(name, kernel, head_dim, Er)} of the forward attentions of one training step."""
-    g = {(ps, name): gemm_route(M, N, K, act) for ps, name, M, N, K, act in products(cfg, B, S, L)}
-    a = {name: (attn_route(b, H, Lq, Lk, hd, er), hd, er) for name, b, H, Lq, Lk, hd, er in attentions(cfg, B, S, L)}
+    """{(pass, name): (kernel, epilogue)} of the GEMMs and {name: (kernel, head_dim, Er)} of the forward attentions of one training step."""
+    g = {(ps, name): gemm_kernel_and_epilogue(M, N, K, act) for ps, name, M, N, K, act in products(cfg, B, S, L)}
+    a = {name: (R.attn_route(b, H, Lq, Lk, hd, er), hd, er) for name, b, H, Lq, Lk, hd, er in attentions(cfg, B, S, L)}
     return g, a

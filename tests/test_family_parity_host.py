@@ -7,6 +7,7 @@ import torch
 
 from oracle import amt_oracle as O
 from tests import helpers_family_parity as HF
+from tests import launch_routes as R
 
 
 def test_table_covers_every_family_member():
@@ -41,7 +42,7 @@ def test_substring_version_rules():
 
 @pytest.mark.parametrize("name", HF.NAMES)
 def test_route_claims(name):
-    """The attention kernel of every launch and the GEMM routes the case's edge names are what the dispatch rules give."""
+    """The attention kernel of every launch and the GEMM routes the case's edge names are what the library's launchers answer."""
     c = HF.BY_NAME[name]
     s = HF.SHAPES[c.shape]
     attn, gemm = HF.routes(c)
@@ -57,9 +58,9 @@ def test_route_claims(name):
     if c.shape == "s4":
         assert calls["self"].hd == 16
     if c.shape == "s6":
-        plain = [q for q in HF.gemm_calls(c) if q.act == 0]
-        assert max(q.M * q.N for q in plain) <= 650000 and all(HF.gemm_expected_route(q) == "skinny" for q in plain)
-        assert any(q.act == 3 and q.N == 1024 for q in HF.gemm_calls(c))
+        plain = [q for q in HF.gemm_calls(c) if q.act == 0 and not q.other_forms]
+        assert max(q.M * q.N for q in plain) <= R.BOUNDARIES["small_mn"] and all(R.route_of(q) == "skinny" for q in plain)
+        assert any((q.act == 3 or q.other_forms) and q.N == 1024 and R.route_of(q) == "tile64" for q in HF.gemm_calls(c))
 
 
 @pytest.mark.parametrize("name", HF.NAMES)

@@ -1,5 +1,5 @@
-"""Input conditions of the operator edge tests, checked on the CPU (no library call): every case takes the route its comment
-names, the case tables cover the edges they are meant to, the steered MoE routing is not a rounding question, and on each
+"""Input conditions of the operator edge tests, checked on the CPU (the library is asked for launch routes only, which needs no
+GPU): every case takes the route its comment names, the case tables cover the edges they are meant to, the steered MoE routing is not a rounding question, and on each
 case's inputs the plain fp32 restatement is within a quarter of the bound of the fp64 one -- so a GPU test that misses its bound
 cannot blame its inputs.  The computed tolerances are printed (pytest -s)."""
 import numpy as np
@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from tests import helpers_ops_edges as H
+from tests import launch_routes as R
 
 
 # ---- A. GEMM -----------------------------------------------------------------------------------------------------------
@@ -14,7 +15,7 @@ from tests import helpers_ops_edges as H
 def test_gemm_case_route_and_condition(name):
     c = H.GEMM_BY_NAME[name]
     assert c.edge, "every case names the route or edge it exists for"
-    assert H.gemm_expected_route(c) == c.route
+    assert R.route_of(c) == c.route
     assert c.K % 32 == 0 and (c.K + c.dx) % 4 == 0 and (c.K + c.dw) % 4 == 0 and c.xcol % 4 == 0      # what the launcher accepts
     inp = H.gemm_inputs(name)
     assert inp["ldy"] >= c.N and inp["ldr"] >= c.N
@@ -28,16 +29,17 @@ def test_gemm_case_route_and_condition(name):
 
 def test_gemm_table_covers_the_named_edges():
     C = H.GEMM_CASES
-    for route in ("t64", "t128"):
+    B = R.BOUNDARIES
+    for route in ("tile64", "tile128"):
         assert {c.vec for c in C if c.route == route} == {True, False}, f"both epilogues on {route}"
-    nk = {c.K // 32 for c in C if c.route == "t64"}
+    nk = {c.K // 32 for c in C if c.route == "tile64"}
     assert 1 in nk and any(n % 2 == 1 and n > 1 for n in nk)
-    assert any(c.route == "skinny" and 650000 - 4096 < c.M * c.N <= 650000 for c in C)
-    assert any(c.route == "t64" and c.M <= 4096 and 650000 < c.M * c.N < 650000 + 4096 and c.K <= 1536 and c.act == 0 for c in C)
-    assert any(c.route == "t64" and c.M == 4097 for c in C)
+    assert any(c.route == "skinny" and B["small_mn"] - B["small_m"] < c.M * c.N <= B["small_mn"] for c in C)
+    assert any(c.route == "tile64" and c.M <= B["small_m"] and B["small_mn"] < c.M * c.N < B["small_mn"] + B["small_m"] and c.K <= B["skinny_k"] and c.act == 0 for c in C)
+    assert any(c.route == "tile64" and c.M == B["small_m"] + 1 for c in C)
     assert any(c.route == "skinny" and c.dx and c.dw and c.dy and c.dr and c.xcol for c in C)
-    assert {c.act for c in C if c.route == "t64"} == {0, 2, 3}
-    t128 = [c for c in C if c.route == "t128"]
+    assert {c.act for c in C if c.route == "tile64"} == {0, 2, 3}
+    t128 = [c for c in C if c.route == "tile128"]
     assert all((-(-c.M // 128) * -(-c.N // 128)) % 8 != 0 and c.M % 128 and c.N % 128 for c in t128)
     vec = {c.name: c.vec for c in C if c.name.startswith("vec_")}
     assert vec == {"vec_all_mult4": True, "vec_ldy_odd": False, "vec_ldr_odd": False, "vec_padded": True}
@@ -61,7 +63,7 @@ def test_gemm_tolerances():
 @pytest.mark.parametrize("name", [c.name for c in H.ATTN_CASES])
 def test_attn_case_kernel_and_condition(name):
     c = H.ATTN_BY_NAME[name]
-    assert c.edge and H.attn_expected_kernel(c) == c.kernel
+    assert c.edge and R.attn_route(c.B, c.H, c.Lq, c.Lk, c.hd) == c.kernel
     assert c.H % c.g == 0 and c.hd in (16, 32, 64, 128)
     inp = H.attn_inputs(name)
     st = inp["strides"]

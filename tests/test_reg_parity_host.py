@@ -60,7 +60,7 @@ def test_key_lists_routes_and_inputs(name):
     routes = HR.routes(c)
     assert set(routes.values()) == set(c.gemm)
     calls = {g.name: g for g in HR.gemm_calls(c)}
-    t64 = {k for k, v in routes.items() if v == "t64"}
+    t64 = {k for k, v in routes.items() if v == "tile64"}
     assert "classifier" in t64 and all(k == "classifier" or ".moe." in k or ".ffn." in k or k == "conv7.tap6" for k in t64), t64
     assert routes["regressor"] == "skinny" and calls["regressor"].N == 2 and calls["regressor"].M == c.B * c.S
     assert all(g.K % 32 == 0 for g in calls.values())

@@ -1,14 +1,15 @@
 """Input conditions of the training edge cases (tests/helpers_train_edges.py), on the CPU, before any GPU run: every case takes the
-kernels it is named for (the launch rules of gemm_f32.hip and attn_prefill.hip written out, their thresholds read from the sources, so
-that a retuned threshold fails here), the fixture of tests/helpers_train.py takes none of the 64-tile GEMMs, each case's fp32 noise is
-in the range its bounds assume, and each wrong variant of the restatement misses those bounds by at least 10 times in every case named
-for it."""
+kernels it is named for (the library is asked, tests/launch_routes.py; each boundary the table is built around is proved through the
+same queries, so that a retuned threshold fails here), the fixture of tests/helpers_train.py takes none of the 64-tile GEMMs, each
+case's fp32 noise is in the range its bounds assume, and each wrong variant of the restatement misses those bounds by at least 10
+times in every case named for it."""
 import numpy as np
 import pytest
 import torch
 
 from tests import helpers_train as T
 from tests import helpers_train_edges as E
+from tests import launch_routes as R
 from video2music_amd.utilities import constants as C
 
 NAMES = list(E.CASES)
@@ -19,17 +20,33 @@ def routes_of(name):
     return E.routes(c["cfg"], c["B"], c["S"], c["L"])
 
 
-def test_launch_thresholds_are_read_from_the_sources():
-    t = E.thresholds()
-    assert t["small_m"] > 0 and t["small_mn"] > 0 and t["skinny_k"] % 32 == 0 and t["QB"] == 128 and t["split"][:2] == (32, 64)
-    # the rule itself at its edges
-    assert E.gemm_route(t["small_m"], 32, 32) == ("skinny", "none") and E.gemm_route(t["small_m"] + 1, 32, 32)[0] == "tile64"
-    assert E.gemm_route(64, 64, t["skinny_k"])[0] == "skinny" and E.gemm_route(64, 64, t["skinny_k"] + 32)[0] == "tile64"
-    assert E.gemm_route(1000, t["small_mn"] // 1000, 64)[0] == "skinny" and E.gemm_route(1000, t["small_mn"] // 1000 + 1, 64)[0] == "tile64"
-    assert E.gemm_route(64, 65, 2048) == ("tile64", "none:elementwise") and E.gemm_route(128 * t["t64_below"], 128, t["big_k"])[0] == "tile128"
-    assert E.attn_route(2, 2, 300, 300, 32, False) == "splitk" and E.attn_route(2, 2, 300, 255, 32, False) == "rows128"
-    assert E.attn_route(2, 2, 300, 300, 32, True) == "rows128" and E.attn_route(2, 2, 300, 300, 128, False) == "rows128"
-    assert E.attn_route(t["split"][2], 1, 32, 256, 64, False) == "rows128"
+def test_launch_boundaries_are_the_librarys():
+    """Every entry of R.BOUNDARIES is where the launcher's own rule flips (K moves in steps of 32, the head dims over the four built)."""
+    b, g, a = R.BOUNDARIES, R.gemm_route, R.attn_route
+    tiles = lambda n: (128 * n, 128)                                             # (M, N) of n 128x128 tiles
+    lo, hi = b["split_hd"]
+    flips = {            # name: (routes at the boundary and one step past it, what they must be)
+        "small_m": ((g(b["small_m"], 32, 32), g(b["small_m"] + 1, 32, 32)), ("skinny", "tile64")),
+        "small_mn": ((g(1, b["small_mn"], 32), g(1, b["small_mn"] + 1, 32)), ("skinny", "tile64")),
+        "skinny_k": ((g(64, 64, b["skinny_k"]), g(64, 64, b["skinny_k"] + 32)), ("skinny", "tile64")),
+        "t64_below": ((g(*tiles(b["t64_below"] - 1), b["big_k"]), g(*tiles(b["t64_below"]), b["big_k"])), ("tile64", "tile128")),
+        "big_k": ((g(*tiles(b["t64_below"]), b["big_k"] - 32), g(*tiles(b["t64_below"]), b["big_k"])), ("tile64", "tile128")),
+        "attn_row_block": ((a(1, b["split_grid"] - 1, b["attn_row_block"], b["split_lk"], lo),
+                            a(1, b["split_grid"] - 1, b["attn_row_block"] + 1, b["split_lk"], lo)), ("splitk", "rows128")),
+        "split_grid": ((a(b["split_grid"] - 1, 1, 32, b["split_lk"], hi), a(b["split_grid"], 1, 32, b["split_lk"], hi)), ("splitk", "rows128")),
+        "split_lk": ((a(2, 2, 300, b["split_lk"] - 1, lo), a(2, 2, 300, b["split_lk"], lo)), ("rows128", "splitk")),
+        "split_hd": ((a(2, 2, 300, 300, lo // 2), a(2, 2, 300, 300, lo), a(2, 2, 300, 300, hi), a(2, 2, 300, 300, 2 * hi)),
+                     ("rows128", "splitk", "splitk", "rows128")),
+    }
+    assert set(flips) == set(b)
+    for name, (got, want) in flips.items():
+        assert got == want, f"{name} = {b[name]} of tests/launch_routes.py is not where the launcher's route flips: {got} instead of {want}"
+    # further edges; a relative position table, a form only the library's own callers set, sigmoid and SiLU keep a shape off the fast route
+    assert g(1000, b["small_mn"] // 1000, 64) == "skinny" and g(1000, b["small_mn"] // 1000 + 1, 64) == "tile64"
+    assert E.gemm_kernel_and_epilogue(b["small_m"], 32, 32) == ("skinny", "none")
+    assert E.gemm_kernel_and_epilogue(64, 65, b["big_k"]) == ("tile64", "none:elementwise")
+    assert a(2, 2, 300, 300, 32, True) == "rows128" and g(64, 64, 64, 0, other_forms=True) == "tile64"
+    assert [g(64, 64, 64, act) for act in (0, 1, 2, 3)] == ["skinny", "skinny", "tile64", "tile64"]
 
 
 def test_the_fixture_reaches_no_64_tile_product_and_no_128_row_er_free_attention():
@@ -63,14 +80,14 @@ def test_every_case_takes_the_kernels_it_is_named_for():
     assert E.D96["d_model"] % 64 and E.D96["total_vf_dim"] % 32 == 5 and E.D96["max_sequence_chord"] - 37 == 27
     g, a = routes_of("rows_gt_4096")
     c = E.CASES["rows_gt_4096"]
-    assert c["B"] * c["L"] > E.thresholds()["small_m"] and c["B"] * c["L"] * 3 * 32 < E.thresholds()["small_mn"] and c["B"] * c["L"] > 2048
+    assert c["B"] * c["L"] > R.BOUNDARIES["small_m"] and c["B"] * c["L"] * 3 * 32 < R.BOUNDARIES["small_mn"] and c["B"] * c["L"] > 2048
     assert g["fwd", "dec0.linear1"] == ("tile64", "relu:vector") and g["fwd", "Wout"] == ("tile64", "none:elementwise")
     assert g["bwd", "Linear_chord.dx"] == ("tile64", "none:elementwise") and g["bwd", "dec0.linear1.dw"] == ("tile64", "none:elementwise")
     assert g["fwd", "enc0.self_attn.qkv"] == ("skinny", "none")                  # its 560 video rows stay on the skinny GEMM
     g, a = routes_of("k_gt_1536")
     fwd = {v[0] for (ps, _), v in g.items() if ps == "fwd"}
     dw = {v for (ps, n), v in g.items() if n.endswith(".dw")}
-    assert fwd == {"skinny"} and dw == {("tile64", "none:elementwise")} and (13 * 129 + 31) // 32 * 32 > E.thresholds()["skinny_k"]
+    assert fwd == {"skinny"} and dw == {("tile64", "none:elementwise")} and (13 * 129 + 31) // 32 * 32 > R.BOUNDARIES["skinny_k"]
     g, a = routes_of("plain_noncausal")
     assert a == {"enc.self_attn": ("splitk", 32, False), "dec.self_attn": ("rows128", 32, False), "dec.multihead_attn": ("splitk", 32, False)}
     assert not E.CASES["plain_noncausal"]["causal"] and not E.CASES["plain_noncausal"]["cfg"]["rpr"]

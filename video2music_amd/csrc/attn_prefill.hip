@@ -418,22 +418,34 @@ __global__ __launch_bounds__(256) void attn_prefill_splitk_kernel(AttnParams p) 
     }
 }
 
+}  // namespace
+
+// fewer than two 128-row blocks per CU and a long key range: one 32-row block per workgroup, keys split over its waves
+AttnRoute amt_attn_route_of(const AttnParams& p) {
+    const int grid = cdiv(p.Lq, QB) * p.H * p.B;
+    return !p.Er && p.hd >= 32 && p.hd <= 64 && grid < 512 && p.Lk >= 256 ? AttnRoute::SplitK : AttnRoute::Rows128;
+}
+
+namespace {
+
 template <int HD, bool TRAIN>
-int32_t launch_hd(const AttnParams& p, hipStream_t stream) {
-    dim3 grid(cdiv(p.Lq, QB) * p.H * p.B);
-    // fewer than two 128-row blocks per CU and a long key range: one 32-row block per workgroup, keys split over its waves
-    if (!p.Er && HD >= 32 && HD <= 64 && grid.x < 512 && p.Lk >= 256) {
+int32_t launch_hd(const AttnParams& p, hipStream_t stream) {       // p.hd == HD
+    const dim3 grid(cdiv(p.Lq, QB) * p.H * p.B);
+    switch (amt_attn_route_of(p)) {
+    case AttnRoute::SplitK:                 // head_dim 32 / 64 only; at 16 / 128 the name below is an instantiation never launched
         hipLaunchKernelGGL((attn_prefill_splitk_kernel<(HD >= 32 && HD <= 64 ? HD : 64), TRAIN>), dim3(cdiv(p.Lq, 32) * p.H * p.B), dim3(256), 0, stream, p);
-        return 0;
+        break;
+    case AttnRoute::Rows128:
+        if constexpr (TRAIN) {              // relative positions in training: causal only (checked by the caller)
+            if (p.Er) hipLaunchKernelGGL((attn_prefill_kernel<HD, true, false, true>), grid, dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((attn_prefill_kernel<HD, false, false, true>), grid, dim3(256), 0, stream, p);
+        } else {
+            if (p.Er && !p.causal) hipLaunchKernelGGL((attn_prefill_kernel<HD, true, true>), grid, dim3(256), 0, stream, p);
+            else if (p.Er) hipLaunchKernelGGL((attn_prefill_kernel<HD, true>), grid, dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((attn_prefill_kernel<HD, false>), grid, dim3(256), 0, stream, p);
+        }
+        break;
     }
-    if constexpr (TRAIN) {                  // relative positions in training: causal only (checked by the caller)
-        if (p.Er) hipLaunchKernelGGL((attn_prefill_kernel<HD, true, false, true>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((attn_prefill_kernel<HD, false, false, true>), grid, dim3(256), 0, stream, p);
-        return 0;
-    }
-    if (p.Er && !p.causal) hipLaunchKernelGGL((attn_prefill_kernel<HD, true, true>), grid, dim3(256), 0, stream, p);
-    else if (p.Er) hipLaunchKernelGGL((attn_prefill_kernel<HD, true>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((attn_prefill_kernel<HD, false>), grid, dim3(256), 0, stream, p);
     return 0;
 }
 

@@ -241,40 +241,47 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
 
 }  // namespace
 
+// Which kernel amt_launch_gemm launches: the whole rule, also what amt_gemm_route (ops_api.hip) answers.
+// Small products (one decode row, the 300 frames of one clip, a table, a few thousand rows of a narrow layer): a 128x128
+// tile costs its full MFMA time on one CU whatever part of it is real rows (27 us at K = 512; ~50 us measured), and with
+// fewer tiles than CUs nothing hides it.  With a plain epilogue they go to the skinny GEMM (16x16 output tiles, all of a
+// workgroup's weight loads in flight at once): ~10 us up to M*N = 256k outputs, break-even with the 64x64-tile variant below
+// near 650k outputs (tools/bench_small_gemm.py).
+// Of the tiled instantiations, 64x64 tiles (one accumulator per wave, four times the workgroups) measure faster than 128x128 on every shape of this
+// model (K <= 1312; 114-126 TFLOP/s at M = 32768, 111 at M = 9600 since the loads of the k loop are branch-free and two
+// k-tiles ahead: tools/bench_gemm.py; 103-110 before); the big tile is kept for long-K products with many tiles.
+GemmRoute amt_gemm_route_of(const GemmParams& p) {
+    const long small_m = amt_tuning().gemm_small_m, small_mn = amt_tuning().gemm_small_mn;
+    if (p.M <= small_m && (long)p.M * p.N <= small_mn && p.K % 32 == 0 && p.K <= 1536 && !p.head_split && !p.rowadd && !p.silu_mul &&
+        !p.sigmoid && !p.tile_group && !p.a_gather && p.relu != 2)
+        return GemmRoute::Skinny;
+    const int t128 = cdiv(p.M, 128) * cdiv(p.N, 128);
+    return t128 >= amt_tuning().gemm_t64_below && p.K >= 2048 ? GemmRoute::Tile128 : GemmRoute::Tile64;
+}
+
 int32_t amt_launch_gemm(const GemmParams& p, hipStream_t stream) {
     AMT_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0, "gemm: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
     AMT_CHECK_ARG(p.K % BK == 0, "gemm: K=%d must be a multiple of %d (pad the operands)", p.K, BK);
     AMT_CHECK_ARG(p.lda % 4 == 0 && p.ldw % 4 == 0, "gemm: leading dimensions must be multiples of 4 floats");
     AMT_CHECK_ARG(p.lda >= p.K && p.ldw >= p.K, "gemm: leading dimension smaller than K");
     AMT_CHECK_ARG(((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.W & 15) == 0, "gemm: operands must be 16-byte aligned");
-    // Small products (one decode row, the 300 frames of one clip, a table, a few thousand rows of a narrow layer): a 128x128
-    // tile costs its full MFMA time on one CU whatever part of it is real rows (27 us at K = 512; ~50 us measured), and with
-    // fewer tiles than CUs nothing hides it.  With a plain epilogue they go to the skinny GEMM (16x16 output tiles, all of a
-    // workgroup's weight loads in flight at once): ~10 us up to M*N = 256k outputs, break-even with the 64x64-tile variant below
-    // near 650k outputs (tools/bench_small_gemm.py).
-    const long small_m = amt_tuning().gemm_small_m, small_mn = amt_tuning().gemm_small_mn;
-    if (p.M <= small_m && (long)p.M * p.N <= small_mn && p.K % 32 == 0 && p.K <= 1536 && !p.head_split && !p.rowadd && !p.silu_mul &&
-        !p.sigmoid && !p.tile_group && !p.a_gather && p.relu != 2) {
+    const GemmRoute route = amt_gemm_route_of(p);
+    if (route == GemmRoute::Skinny) {
         DecodeGemmParams g{};
         g.B = p.M; g.eps = 1e-5f; g.x = p.A; g.ldx = p.lda; g.Wp = p.W; g.ldw = p.ldw; g.bias = p.bias; g.N = p.N; g.K = p.K;
         g.resid = p.resid; g.ldr = p.ldr; g.relu = p.relu; g.scale = p.scale; g.scale_cols = p.scale_cols; g.y = p.C; g.ldy = p.ldc;
         return amt_launch_decode_gemm(g, stream);
     }
-    // 64x64 tiles (one accumulator per wave, four times the workgroups) measure faster than 128x128 on every shape of this
-    // model (K <= 1312; 114-126 TFLOP/s at M = 32768, 111 at M = 9600 since the loads of the k loop are branch-free and two
-    // k-tiles ahead: tools/bench_gemm.py; 103-110 before); the big tile is kept for long-K products with many tiles.
-    const int t128 = cdiv(p.M, 128) * cdiv(p.N, 128);
-    const int t64_below = amt_tuning().gemm_t64_below;
+    const bool big = route == GemmRoute::Tile128;
     const int pf = amt_tuning().gemm_pf;                 // tens: big tile, units: small tile
-    const bool big = t128 >= t64_below && p.K >= 2048;
-    const dim3 g64(cdiv(p.M, 64) * cdiv(p.N, 64));
+    const dim3 g64(cdiv(p.M, 64) * cdiv(p.N, 64)), g128(cdiv(p.M, 128) * cdiv(p.N, 128));
     if (p.a_gather) {
-        if (big) hipLaunchKernelGGL((gemm_f32_kernel<2, 2, true, 1>), dim3(t128), dim3(256), 0, stream, p);
+        if (big) hipLaunchKernelGGL((gemm_f32_kernel<2, 2, true, 1>), g128, dim3(256), 0, stream, p);
         else if (pf % 10 == 2) hipLaunchKernelGGL((gemm_f32_kernel<1, 1, true, 2>), g64, dim3(256), 0, stream, p);
         else hipLaunchKernelGGL((gemm_f32_kernel<1, 1, true, 1>), g64, dim3(256), 0, stream, p);
     } else if (big) {
-        if (pf / 10 == 2) hipLaunchKernelGGL((gemm_f32_kernel<2, 2, false, 2>), dim3(t128), dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((gemm_f32_kernel<2, 2, false, 1>), dim3(t128), dim3(256), 0, stream, p);
+        if (pf / 10 == 2) hipLaunchKernelGGL((gemm_f32_kernel<2, 2, false, 2>), g128, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((gemm_f32_kernel<2, 2, false, 1>), g128, dim3(256), 0, stream, p);
     } else {
         if (pf % 10 == 2) hipLaunchKernelGGL((gemm_f32_kernel<1, 1, false, 2>), g64, dim3(256), 0, stream, p);
         else hipLaunchKernelGGL((gemm_f32_kernel<1, 1, false, 1>), g64, dim3(256), 0, stream, p);

@@ -30,6 +30,9 @@ static inline GemmParams gemm_params(const float* A, int lda, const float* W, in
     return p;
 }
 int32_t amt_launch_gemm(const GemmParams& p, hipStream_t stream);
+// the kernel amt_launch_gemm launches for p (the whole rule; p's pointers are tested for null only): the values are amt_gemm_route's codes
+enum class GemmRoute : int32_t { Skinny = 0, Tile64 = 1, Tile128 = 2 };
+GemmRoute amt_gemm_route_of(const GemmParams& p);
 
 // ---------------- normalisation / elementwise (norm.hip) ----------------
 // y = LayerNorm(x (+ resid)) * w + b ; optional second LayerNorm (w2,b2) applied on top (decoder.norm)
@@ -73,6 +76,9 @@ struct AttnParams {
 };
 int32_t amt_launch_attn_prefill(const AttnParams& p, hipStream_t stream);
 int32_t amt_launch_attn_train(const AttnParams& p, hipStream_t stream);
+// the kernel both launchers take for p's shape (Er tested for null only): the values are amt_attn_route's codes
+enum class AttnRoute : int32_t { Rows128 = 0, SplitK = 1 };
+AttnRoute amt_attn_route_of(const AttnParams& p);
 
 // ---------------- attention, backward (attn_bwd.hip) ----------------
 struct AttnBwdParams {

@@ -95,20 +95,6 @@ extern "C" int32_t amt_cross_attn_fwd(const float* q, const float* k, const floa
     return amt_launch_attn_prefill(a, (hipStream_t)stream);
 }
 
-extern "C" int32_t amt_attn_fwd(const float* q, const float* k, const float* v, float* o, const int64_t* strides,
-                                int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t causal, int32_t kv_group,
-                                float q_scale, void* stream) {
-    AMT_CHECK_ARG(q && k && v && o && strides, "amt_attn_fwd: null pointer");
-    AttnParams a{};
-    a.q = q; a.k = k; a.v = v; a.o = o;
-    a.q_bs = strides[0]; a.q_hs = strides[1]; a.q_ls = strides[2];
-    a.k_bs = strides[3]; a.k_hs = strides[4]; a.k_ls = strides[5];
-    a.v_bs = strides[6]; a.v_hs = strides[7]; a.v_ls = strides[8];
-    a.o_bs = strides[9]; a.o_hs = strides[10]; a.o_ls = strides[11];
-    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.hd = hd; a.causal = causal; a.kv_group = kv_group > 0 ? kv_group : 1; a.q_scale = q_scale;
-    return amt_launch_attn_prefill(a, (hipStream_t)stream);
-}
-
 static AttnParams strided_params(const float* q, const float* k, const float* v, float* o, const int64_t* strides, int B, int H, int Lq,
                                  int Lk, int hd, int causal, int kv_group, float q_scale) {
     AttnParams a{};
@@ -119,6 +105,30 @@ static AttnParams strided_params(const float* q, const float* k, const float* v,
     a.o_bs = strides[9]; a.o_hs = strides[10]; a.o_ls = strides[11];
     a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.hd = hd; a.causal = causal; a.kv_group = kv_group > 0 ? kv_group : 1; a.q_scale = q_scale;
     return a;
+}
+
+extern "C" int32_t amt_attn_fwd(const float* q, const float* k, const float* v, float* o, const int64_t* strides,
+                                int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t causal, int32_t kv_group,
+                                float q_scale, void* stream) {
+    AMT_CHECK_ARG(q && k && v && o && strides, "amt_attn_fwd: null pointer");
+    return amt_launch_attn_prefill(strided_params(q, k, v, o, strides, B, H, Lq, Lk, hd, causal, kv_group, q_scale), (hipStream_t)stream);
+}
+
+// the launch routes, for callers that must know which kernel a shape reaches: no device, no stream, a code instead of a status
+extern "C" int32_t amt_gemm_route(int32_t M, int32_t N, int32_t K, int32_t act, int32_t other_forms) {
+    if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0 || act < 0 || act > 3) return -1;      // what amt_linear_ex_fwd refuses
+    GemmParams g = gemm_params(nullptr, K, nullptr, K, nullptr, N, M, N, K, nullptr);
+    g.relu = act == 1 ? 1 : (act == 3 ? 2 : 0); g.sigmoid = act == 2;                     // as amt_linear_ex_fwd sets them
+    g.head_split = other_forms != 0;        // one of the forms only internal callers set; the route treats them all alike
+    return (int32_t)amt_gemm_route_of(g);
+}
+
+extern "C" int32_t amt_attn_route(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t has_er) {
+    if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || (hd != 16 && hd != 32 && hd != 64 && hd != 128)) return -1;   // what the launcher refuses
+    static const float er = 0.f;            // the route asks only whether a table is there
+    AttnParams a = blh_params(nullptr, nullptr, nullptr, nullptr, B, H, Lq, Lk, hd);
+    if (has_er) a.Er = &er;
+    return (int32_t)amt_attn_route_of(a);
 }
 
 extern "C" int32_t amt_attn_train_fwd(const float* q, const float* k, const float* v, float* o, const int64_t* strides,

@@ -144,6 +144,23 @@ def linear_ex(x, w, b=None, resid=None, act=0, x_col=0, K=None, out=None):
     return y
 
 
+def gemm_route(M, N, K, act=0, other_forms=False):
+    """'skinny' / 'tile64' / 'tile128': the kernel `linear` / `linear_ex` reach for this shape and act (amt_gemm_route; needs no GPU).
+    other_forms: a head-split, row-addend, silu-multiply, grouped or gathered product of the library's own."""
+    rc = _lib.call("amt_gemm_route", M, N, K, int(act), int(other_forms))
+    if rc < 0:
+        raise _lib.AmtError(f"amt_gemm_route: the GEMM launcher refuses M={M} N={N} K={K} act={act}")
+    return ("skinny", "tile64", "tile128")[rc]
+
+
+def attn_route(B, H, Lq, Lk, hd, has_er=False):
+    """'rows128' / 'splitk': the prefill kernel `attention` / `attention_train` reach for this shape (amt_attn_route; needs no GPU)."""
+    rc = _lib.call("amt_attn_route", B, H, Lq, Lk, hd, int(has_er))
+    if rc < 0:
+        raise _lib.AmtError(f"amt_attn_route: the attention launcher refuses B={B} H={H} Lq={Lq} Lk={Lk} hd={hd}")
+    return ("rows128", "splitk")[rc]
+
+
 def layernorm_post(x, w, b, resid=None, post=None, eps=1e-5):
     """LayerNorm(x (+ resid)) + post."""
     rows, dim = x.shape
