@@ -37,7 +37,7 @@
 #define AMT_HIP_H
 #include <stdint.h>
 
-#define AMT_ABI_VERSION 9    /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
+#define AMT_ABI_VERSION 10   /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
                                 3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights;
                                 4: amt_chord_metrics_fwd;
                                 5: amt_reg_metrics_fwd;
@@ -46,7 +46,8 @@
                                    amt_chord_loss_ws_floats;
                                 8: amt_selective_scan_train_fwd, amt_selective_scan_bwd, amt_selective_scan_bwd_ws_floats,
                                    amt_dwconv1d_silu_bwd, amt_dwconv1d_silu_bwd_ws_floats;
-                                9: amt_gemm_route, amt_attn_route */
+                                9: amt_gemm_route, amt_attn_route;
+                                10: amt_moe_train_scratch_floats, amt_moe_train_fwd, amt_moe_bwd_ws_floats, amt_moe_bwd */
 
 #ifdef __cplusplus
 extern "C" {
@@ -316,6 +317,38 @@ int32_t amt_moe_topk_fwd(const float* x, const float* gate_w, const float* gate_
                     const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
                     float* out, int32_t* idx_out, float* w_out, float* scratch,
                     int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp, int32_t k, void* stream);
+
+/* Training of the same layer (csrc/moe_bwd.hip).  amt_moe_train_fwd issues amt_moe_topk_fwd's launches (the fused gate of the up
+ * projection becomes a launch of its own, so that the up branch can be kept) and leaves in the caller-owned `saved`
+ * (amt_moe_train_scratch_floats; glu = 1 when w1 is given) what amt_moe_bwd reads: per slot row of the plan G (gate pre-activation), U
+ * (the up branch before gating, GLU experts only), H (as fed to the down projection, dropout multiplier included) and Y (as it enters
+ * the combine: output dropout multiplier included); the same four of the shared expert; perm, slot_pos, tile_group, the slot ->
+ * assignment map, the segment offsets; idx and wts (also copied to idx_out / w_out when given).
+ * Dropout multipliers (0 or 1 / (1 - p)), each optional, indexed by ASSIGNMENT a = token * k + j (j the position in idx_out's order):
+ * mask_h (n_tok k, dff_raw) on U silu(G) (silu(G) for SiLU experts), mask_y (n_tok k, d) on the expert's output before the routing
+ * weight, mask_hs (n_tok, dff_raw) inside the shared expert.  dff_raw <= dff: the experts' own hidden width (dff its zero-padded
+ * multiple of 32).  With the three masks null, out / idx_out / w_out are the bits of amt_moe_topk_fwd.
+ * amt_moe_bwd: dout (n_tok, d) -> dx (n_tok, d), dgate_w (n_exp, d), dgate_b (n_exp), dw1 (n_exp, dff, d; null for SiLU experts) db1
+ * (n_exp, dff) dwg dbg dw2 (n_exp, d, dff) db2 (n_exp, d) and the shared expert's six (null without one), all at the padded width dff
+ * (the padding's rows / columns come out zero).  w1t / wgt (n_exp, d, dff) and w2t (n_exp, dff, d) are the TRANSPOSED stacked weights
+ * (sw1t, swgt (d, dff), sw2t (dff, d) the shared expert's), prepared by the caller.  An expert without rows gets exact zeros.  No
+ * floating-point atomics and a fixed order of every sum: the same inputs give the same bits.  ws: amt_moe_bwd_ws_floats. */
+int64_t amt_moe_train_scratch_floats(int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp, int32_t k, int32_t glu);
+int32_t amt_moe_train_fwd(const float* x, const float* gate_w, const float* gate_b,
+                    const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
+                    const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
+                    const float* mask_h, const float* mask_y, const float* mask_hs,
+                    float* out, int32_t* idx_out, float* w_out, float* saved,
+                    int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, void* stream);
+int64_t amt_moe_bwd_ws_floats(int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp, int32_t k);
+int32_t amt_moe_bwd(const float* dout, const float* x, const float* gate_w, const float* saved,
+                    const float* w1t, const float* wgt, const float* w2t, const float* sw1t, const float* swgt, const float* sw2t,
+                    const float* mask_h, const float* mask_y, const float* mask_hs,
+                    float* dx, float* dgate_w, float* dgate_b,
+                    float* dw1, float* db1, float* dwg, float* dbg, float* dw2, float* db2,
+                    float* dsw1, float* dsb1, float* dswg, float* dsbg, float* dsw2, float* dsb2,
+                    float* ws, int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, int32_t glu,
+                    int32_t has_shared, float temperature, void* stream);
 
 /* Pieces of the same layer for expert-parallel execution (config 5: one expert group per GPU; the token rows
  * travel by all_to_all between amt_moe_route_fwd and amt_moe_combine_fwd, see video2music_amd/model/moe.py):

@@ -1,0 +1,186 @@
+"""Training-test infrastructure for the mixture-of-experts layer and the two mixture regression heads: a restatement of MoELayer /
+SharedMoELayer (reference model/moe.py:36-49, 150-302; the Linear -> SiLU -> Dropout -> Linear experts of
+video_music_transformer.py:80-85) with optional dropout multipliers on torch's CPU tensors in any precision, differentiated by torch's
+own autograd, and the whole head VideoRegression(regModel = 'moe_bimamba+' / 'sharedmoe_bimamba+') composed with the pieces of
+tests/helpers_reg_mamba_train.py.  Without multipliers `moe_layer` is `oracle.amt_oracle.moe_forward`.  In double it is the yardstick
+of tests/test_moe_bwd_gpu.py and tests/test_reg_moe_train_gpu.py; tests/test_reg_moe_train_host.py pins it to the reference's recorded
+figures first."""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from tests import helpers_reg_mamba_train as T
+from tests.helpers_reg_train import ADAM_LR, ADAM_STEPS, SGD_LR, SGD_STEPS, U, rel_err      # noqa: F401
+
+# g_reg_moe_train*.npz: both mixture heads, one layer each; both clips of the miniature dataset in one batch
+MODELS = {"moe_bimamba+": dict(regModel="moe_bimamba+", d_model=32, n_layers=1, dim_feedforward=64),
+          "sharedmoe_bimamba+": dict(regModel="sharedmoe_bimamba+", d_model=32, n_layers=1, dim_feedforward=64)}
+FULL64 = ("sharedmoe_bimamba+",)  # its full fp64 gradients are recorded
+N_EXPERTS, TOP_K = 6, 2           # video_regression.py:143-178
+SEED = 0                          # of video2music_amd.synthetic for the fixture's weights
+GAP = 1e-4                        # smallest admitted gap between a token's k-th and (k+1)-th gate logit, relative to the largest |logit|
+
+
+def expert(P, pre, x, mask_h=None):
+    """One expert on rows x: GLUExpert W2(((W1 x + b1) silu(Wg x + bg)) mask_h) + b2, or the SiLU expert W2((silu(W0 x + b0)) mask_h) + b3."""
+    if pre + "linear1.weight" in P:
+        h = (x @ P[pre + "linear1.weight"].T + P[pre + "linear1.bias"]) * F.silu(x @ P[pre + "gate.weight"].T + P[pre + "gate.bias"])
+        w2, b2 = P[pre + "linear2.weight"], P[pre + "linear2.bias"]
+    else:
+        h = F.silu(x @ P[pre + "0.weight"].T + P[pre + "0.bias"])
+        w2, b2 = P[pre + "3.weight"], P[pre + "3.bias"]
+    if mask_h is not None:
+        h = h * mask_h
+    return h @ w2.T + b2
+
+
+def gate_logits(P, pre, x):
+    return x @ P[pre + "gate.weight"].T + P[pre + "gate.bias"]
+
+
+def gate_gap(logits, k):
+    """min over tokens of (k-th largest - (k+1)-th largest logit) / max|logit|; inf when k is the number of experts."""
+    if k >= logits.shape[-1]:
+        return float("inf")
+    top = torch.topk(logits.detach().double(), k + 1, dim=-1).values
+    return float((top[..., k - 1] - top[..., k]).min() / logits.detach().abs().max())
+
+
+def moe_layer(P, pre, x, n_experts, k, shared, masks=None, routing=None):
+    """x (n_tok, d) -> (n_tok, d).  masks = (mask_h (n_tok k, dff), mask_y (n_tok k, d), mask_hs (n_tok, dff)), each a multiplier
+    tensor or None, rows by assignment token * k + j with j the position in topk's order.  routing (dict) receives idx, weights and
+    the gate logits."""
+    mask_h, mask_y, mask_hs = masks if masks is not None else (None, None, None)
+    n_tok = x.shape[0]
+    logits = gate_logits(P, pre, x)
+    top, idx = torch.topk(logits, k, dim=-1)
+    w = torch.softmax(top, dim=-1)
+    out = torch.zeros_like(x)
+    for e in range(n_experts):
+        tok, j = torch.where(idx == e)
+        if tok.numel() == 0:
+            continue
+        a = tok * k + j
+        y = expert(P, f"{pre}experts.{e}.", x[tok], None if mask_h is None else mask_h.reshape(n_tok * k, -1)[a])
+        if mask_y is not None:
+            y = y * mask_y.reshape(n_tok * k, -1)[a]
+        out = out.index_add(0, tok, w[tok, j].unsqueeze(1) * y)
+    if shared:
+        out = out + (1.0 / k) * expert(P, pre + "shared_expert.", x, None if mask_hs is None else mask_hs.reshape(n_tok, -1))
+    if routing is not None:
+        routing["idx"], routing["weights"], routing["logits"] = idx.detach(), w.detach(), logits.detach()
+    return out
+
+
+# ---- the whole head ----
+
+def mask_shapes(reg_model, n_layers, rows, d_model, p_model, p_inner=0.1):
+    """Shapes of the dropout multipliers a training step consumes, in use order: in_proj, then per layer the two blocks, the mixture
+    layer's [inside the experts, on their outputs, inside the shared expert] and the FFN output's.  Sites with rate 0 take none."""
+    raw, k = 2 * d_model + 1, TOP_K
+    out = [(rows, d_model)] if p_model > 0 else []
+    for _ in range(n_layers):
+        out += [(rows, d_model)] * 2 if p_model > 0 else []
+        out += [(rows * k, raw)] if p_inner > 0 else []
+        out += [(rows * k, d_model)] if p_model > 0 else []
+        out += [(rows, raw)] if p_inner > 0 and reg_model.startswith("shared") else []
+        out += [(rows, d_model)] if p_model > 0 else []
+    return out
+
+
+def model_forward(P, reg_model, n_layers, sem, emo, masks=None, sites=(True, True), routing=None):
+    """-> ln_nd (B, S, 2), p (B, S, 40) of the training-state forward.  masks: the multipliers in `mask_shapes`' order (None: every
+    rate 0); sites = (model rate > 0, the experts' inner rate > 0).  routing (list) receives one dict per layer."""
+    masks = list(masks) if masks is not None else None
+    shared = reg_model.startswith("shared")
+    vf = torch.cat([sem, emo], dim=-1)
+    B, S, _ = vf.shape
+
+    def take(on):
+        return masks.pop(0) if masks is not None and on else None
+
+    def drop(t, on=sites[0]):
+        m = take(on)
+        return t if m is None else t * m.reshape(t.shape)
+
+    def ln(t, pre):
+        return F.layer_norm(t, t.shape[-1:], P[pre + ".weight"], P[pre + ".bias"], 1e-5)
+
+    x = drop(vf @ P["in_proj.0.weight"].T + P["in_proj.0.bias"])
+    for i in range(n_layers):
+        pre = f"model.layers.{i}."
+        xf = ln(drop(T.mamba_block(P, pre + "mamba_forward.", x, 1, False)) + x, pre + "norm1")
+        xb = ln(drop(T.mamba_block(P, pre + "mamba_backward.", x, 1, True)) + x, pre + "norm2")
+        s = xf + xb
+        lm = (take(sites[1]), take(sites[0]), take(sites[1] and shared))
+        r = {}
+        f = moe_layer(P, pre + "ffn.", s.reshape(B * S, -1), N_EXPERTS, TOP_K, shared, lm, r).reshape(s.shape)
+        if routing is not None:
+            routing.append(r)
+        x = ln(drop(f) + s, pre + "norm3")
+    assert not masks
+    ln_nd = x @ P["regressor.weight"].T + P["regressor.bias"]
+    p = torch.sigmoid(x @ P["classifier.0.weight"].T + P["classifier.0.bias"])
+    return ln_nd, p
+
+
+def model_grads(sd, reg_model, n_layers, sem, emo, note_density, loudness, instrument, masks=None, sites=(True, True), dtype=torch.float64):
+    """The training loss and its gradient for every key of the state dict `sd` (numpy arrays) in `dtype`.
+    Returns {"loss", "ln_nd", "p", "grads": {key: float64 array}, "routing": [per layer {idx, weights, logits}]}."""
+    with torch.enable_grad():
+        P = {k: torch.as_tensor(np.asarray(v)).to(dtype).requires_grad_(True) for k, v in sd.items()}
+        t = lambda a: torch.as_tensor(np.asarray(a)).to(dtype)
+        routing = []
+        ln_nd, p = model_forward(P, reg_model, n_layers, t(sem), t(emo), None if masks is None else [t(m) for m in masks], sites, routing)
+        loss = T.train_loss(ln_nd, p, t(note_density), t(loudness), t(instrument))
+        loss.backward()
+    return {"loss": float(loss.detach()), "ln_nd": ln_nd.detach().numpy().astype(np.float64), "p": p.detach().numpy().astype(np.float64),
+            "grads": {k: v.grad.numpy().astype(np.float64) for k, v in P.items()}, "routing": routing}
+
+
+def sgd_updates(sd, steps, lr, *args, dtype=torch.float64, routings=None, **kw):
+    """theta_steps - theta_0 per key after `steps` plain SGD steps on `model_grads`' gradients; routings (list) receives every step's."""
+    P = {k: np.asarray(v, dtype=np.float64).copy() for k, v in sd.items()}
+    for _ in range(steps):
+        o = model_grads(P, *args, dtype=dtype, **kw)
+        if routings is not None:
+            routings.append(o["routing"])
+        P = {k: P[k] - lr * o["grads"][k] for k in P}
+    return {k: P[k] - np.asarray(sd[k], dtype=np.float64) for k in P}
+
+
+# ---- the layer alone (tests/test_moe_bwd_gpu.py) ----
+
+def layer_params(n_tok, d, dff_raw, n_exp, k, shared, glu, seed, force_expert0=False):
+    """Inputs and parameters of one mixture layer as float32 numpy arrays with the modules' key names: x, dout, and P.  force_expert0:
+    the gate's bias puts expert 0 into every token's top-k."""
+    rng = np.random.default_rng(seed)
+    f = lambda *s, scale=1.0: (rng.standard_normal(s) * scale).astype(np.float32)
+    P = {"gate.weight": f(n_exp, d, scale=d ** -0.5), "gate.bias": f(n_exp, scale=0.1)}
+    if force_expert0:
+        P["gate.bias"][0] = 8.0         # the other logits are N(0, 1.01): none of a few hundred tokens' reaches it
+    names = ["experts.%d." % e for e in range(n_exp)] + (["shared_expert."] if shared else [])
+    for pre in names:
+        if glu:
+            P[pre + "linear1.weight"], P[pre + "linear1.bias"] = f(dff_raw, d, scale=d ** -0.5), f(dff_raw, scale=0.1)
+            P[pre + "gate.weight"], P[pre + "gate.bias"] = f(dff_raw, d, scale=d ** -0.5), f(dff_raw, scale=0.1)
+            P[pre + "linear2.weight"], P[pre + "linear2.bias"] = f(d, dff_raw, scale=dff_raw ** -0.5), f(d, scale=0.1)
+        else:
+            P[pre + "0.weight"], P[pre + "0.bias"] = f(dff_raw, d, scale=d ** -0.5), f(dff_raw, scale=0.1)
+            P[pre + "3.weight"], P[pre + "3.bias"] = f(d, dff_raw, scale=dff_raw ** -0.5), f(d, scale=0.1)
+    return f(n_tok, d), f(n_tok, d), P
+
+
+def layer_grads(x, dout, P, n_exp, k, shared, masks=None, dtype=torch.float64):
+    """out and the gradients of <out, dout> for x and every parameter, in `dtype`; plus the routing."""
+    with torch.enable_grad():
+        t = lambda a: None if a is None else torch.as_tensor(np.asarray(a)).to(dtype)
+        Pt = {key: t(v).requires_grad_(True) for key, v in P.items()}
+        xt = t(x).requires_grad_(True)
+        r = {}
+        out = moe_layer(Pt, "", xt, n_exp, k, shared, None if masks is None else tuple(t(m) for m in masks), r)
+        (out * t(dout)).sum().backward()
+    g = {key: (torch.zeros_like(v) if v.grad is None else v.grad).numpy().astype(np.float64) for key, v in Pt.items()}   # None: an expert without a token
+    g["x"] = xt.grad.numpy().astype(np.float64)
+    return {"out": out.detach().numpy().astype(np.float64), "grads": g, "idx": r["idx"].numpy(), "weights": r["weights"].numpy().astype(np.float64),
+            "gap": gate_gap(r["logits"], k)}

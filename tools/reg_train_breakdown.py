@@ -10,7 +10,10 @@ import json
 import sqlite3
 import sys
 
-KINDS = (("selective_scan_bwd", "scan backward (selective_scan_bwd_kernel)"), ("scan_bwd_reduce", "scan backward's ordered sums (scan_bwd_reduce_kernel)"),
+KINDS = (("moe_wgrad", "mixture layer: grouped weight-gradient product (moe_wgrad_kernel / _reduce)"),
+         ("moe_bwd", "mixture layer: backward's row kernels (moe_bwd_dy / dlogit / act / dx)"),
+         ("moe_", "mixture layer: router, plan, gating, combine"),
+         ("selective_scan_bwd", "scan backward (selective_scan_bwd_kernel)"), ("scan_bwd_reduce", "scan backward's ordered sums (scan_bwd_reduce_kernel)"),
          ("selective_scan_kernel", "scan forward (selective_scan_kernel<16, true>)"), ("dwconv_silu_bwd", "conv backward (dwconv_silu_bwd / _reduce)"),
          ("dwconv_silu_dacc", "conv backward (dwconv_silu_dacc_kernel)"), ("dwconv_silu", "conv forward (dwconv_silu_kernel)"),
          ("layernorm_bwd", "LayerNorm backward"), ("norm_kernel", "LayerNorm forward"),

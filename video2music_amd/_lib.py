@@ -92,6 +92,10 @@ SIGNATURES = {
     "amt_moe_fwd": [_P] * 19 + [_I] * 4 + [_P],
     "amt_moe_topk_scratch_floats": [_I, _I, _I, _I, _I],
     "amt_moe_topk_fwd": [_P] * 19 + [_I] * 5 + [_P],
+    "amt_moe_train_scratch_floats": [_I, _I, _I, _I, _I, _I],
+    "amt_moe_train_fwd": [_P] * 22 + [_I] * 6 + [_P],
+    "amt_moe_bwd_ws_floats": [_I, _I, _I, _I, _I],
+    "amt_moe_bwd": [_P] * 29 + [_I] * 8 + [_F, _P],
     "amt_moe_route_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "amt_glu_expert_fwd": [_P] * 9 + [_I, _I, _I, _P],
     "amt_moe_combine_fwd": [_P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
@@ -134,10 +138,10 @@ SIGNATURES = {
 _RESTYPES = {"amt_last_error": C.c_char_p, "amt_decode_step_bytes": C.c_int64, "amt_moe_scratch_floats": C.c_int64, "amt_moe_topk_scratch_floats": C.c_int64,
              "amt_v2_step_ws_floats": C.c_int64, "amt_v2_step_batch_ws_floats": C.c_int64, "amt_moe_ep_expert_scratch_floats": C.c_int64,
              "amt_chord_loss_ws_floats": C.c_int64, "amt_attn_bwd_ws_floats": C.c_int64, "amt_selective_scan_bwd_ws_floats": C.c_int64,
-             "amt_dwconv1d_silu_bwd_ws_floats": C.c_int64}
+             "amt_dwconv1d_silu_bwd_ws_floats": C.c_int64, "amt_moe_train_scratch_floats": C.c_int64, "amt_moe_bwd_ws_floats": C.c_int64}
 _NO_STATUS = set(_RESTYPES) | {"amt_abi_version", "amt_v2_last_step_launches", "amt_gemm_route", "amt_attn_route"}
 
-ABI_VERSION = 9         # AMT_ABI_VERSION of include/amt_hip.h these prototypes were written against
+ABI_VERSION = 10        # AMT_ABI_VERSION of include/amt_hip.h these prototypes were written against
 
 _lib = None
 

@@ -1,5 +1,5 @@
 """`torch.autograd.Function`s over the library calls: what `VideoRegression` is built from in the training state
-(regModel 'lstm' / 'bilstm' / 'gru' / 'bigru' / 'bimamba+' / 'bimamba'), so that `loss.backward()` and any torch optimiser work on the
+(regModel 'lstm' / 'bilstm' / 'gru' / 'bigru' / 'bimamba+' / 'bimamba' / 'moe_bimamba+' / 'sharedmoe_bimamba+'), so that `loss.backward()` and any torch optimiser work on the
 module's own parameters.
 
     LinearFn          y = act(x w^T + b) (+ resid), act 0 none / 1 ReLU / 2 sigmoid   amt_linear_ex_fwd; backward: two GEMMs
@@ -9,6 +9,8 @@ module's own parameters.
                       backward: amt_rnn_seq_bwd + GEMMs
     MambaBlockFn      one MambaBlock (+ the layer's residual)           amt_linear_ex_fwd, amt_dwconv1d_silu_fwd,
                       amt_selective_scan_train_fwd; backward: amt_selective_scan_bwd, amt_dwconv1d_silu_bwd + GEMMs
+    MoEFn             one MoELayer / SharedMoELayer (the mixture heads' FFN)  amt_moe_train_fwd; backward: amt_moe_bwd (grouped GEMMs
+                      for the data gradients, the grouped weight-gradient product of csrc/moe_bwd.hip for the experts' parameters)
     RegLossFn         SmoothL1 + BCE and both gradients                 amt_reg_loss_fwd_bwd
 
 and the pieces of the chord model's training that do not depend on the model (losses.chord_train_loss):
@@ -339,6 +341,52 @@ class ChordLossFn(torch.autograd.Function):
         if ctx.width > d.shape[2]:                              # columns past the 159 classes take no part
             d = torch.nn.functional.pad(d, (0, ctx.width - d.shape[2]))
         return d, None, None, None, None
+
+
+class MoEFn(torch.autograd.Function):
+    """One MoELayer / SharedMoELayer on rows x (n_tok, d): amt_moe_train_fwd, backward amt_moe_bwd.
+
+    apply(x, plan, gate_w, gate_b, *params): `plan` a dict of what is not differentiated -- k, n_exp, dff_raw, masks = (mask_h, mask_y,
+    mask_hs) (multiplier tensors or None, rows by assignment token * k + j), stacked = the experts' (w1, b1, wg, bg, w2, b2) stacked at the
+    padded width, shared = the shared expert's six padded tensors or None; it receives "routing" = (idx, wts).  `params`: per expert its
+    own parameters in the order linear1.weight, linear1.bias, gate.weight, gate.bias, linear2.weight, linear2.bias (a SiLU expert: its
+    first Linear in the gate's place, no linear1), then the shared expert's the same way; they receive the gradients at their own widths.
+
+    Saved: x and the library's `saved` buffer (per plan row G, U, H, Y, the shared expert's, the plan, the routing)."""
+
+    @staticmethod
+    def forward(ctx, x, plan, gate_w, gate_b, *params):
+        x = x.contiguous()
+        stacked, shared = plan["stacked"], plan["shared"]
+        out, idx, wts, saved = ops.moe_train(x, gate_w.detach().contiguous(), gate_b.detach().contiguous(), stacked,
+                                             shared if shared is not None else [None] * 6, plan["masks"], plan["k"], plan["dff_raw"])
+        plan["routing"] = (idx, wts)
+        t = lambda w: None if w is None else w.transpose(-1, -2).contiguous()
+        ctx.plan = plan
+        ctx.tensors_t = ((t(stacked[0]), t(stacked[2]), t(stacked[4])),
+                         None if shared is None else (t(shared[0]), t(shared[2]), t(shared[4])))
+        ctx.save_for_backward(x, gate_w, saved)
+        ctx.mark_non_differentiable(idx, wts)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, gate_w, saved = ctx.saved_tensors
+        plan = ctx.plan
+        experts_t, shared_t = ctx.tensors_t
+        raw, n_exp = plan["dff_raw"], plan["n_exp"]
+        dx, dgw, dgb, de, ds = ops.moe_bwd(dout.contiguous(), x, gate_w.detach().contiguous(), saved, experts_t, shared_t, plan["masks"],
+                                           plan["k"], raw, n_exp)
+
+        def own(g, e=None):              # one expert's six at the parameters' own widths; the hidden padding's gradient is dropped
+            w1, b1, wg, bg, w2, b2 = (g if e is None else [None if t is None else t[e] for t in g])
+            six = [None if w1 is None else w1[:raw], None if b1 is None else b1[:raw], wg[:raw], bg[:raw], w2[:, :raw], b2]
+            return [t.contiguous() for t in six if t is not None]
+
+        grads = [t for e in range(n_exp) for t in own(de, e)]
+        if shared_t is not None:
+            grads += own(ds)
+        return (dx if ctx.needs_input_grad[0] else None, None, dgw, dgb, *grads)
 
 
 def dropout_mask(shape, p, device):

@@ -208,6 +208,12 @@ int32_t amt_decode_gemm_init();
 // dense_B > 0: Y holds every expert's output for every token ([expert][dense_B][d]), slot_pos is not read
 int32_t amt_launch_moe_combine(const float* y_rows, const int32_t* slot_pos, const int32_t* idx, const float* wts, const float* shared,
                                float shared_scale, const float* resid, float* out, int n_tok, int d, hipStream_t stream, int dense_B = 0);
+// the mixture layer's router + plan and its combine for any k, as moe_fwd_impl launches them (moe.hip; the training forward of moe_bwd.hip)
+int32_t amt_launch_moe_route_plan(const float* x, const float* gate_w, const float* gate_b, int32_t* idx, float* wts, int32_t* plan_ints,
+                                  int32_t* perm, int32_t* slot_pos, int32_t* tile_group, int n_tok, int d, int n_exp, int k, int Mp,
+                                  hipStream_t stream);
+int32_t amt_launch_moe_combine_k(const float* y_rows, const int32_t* slot_pos, const int32_t* idx, const float* wts, const float* shared,
+                                 float* out, int n_tok, int d, int k, hipStream_t stream);
 // decision + next chord-stream row + position advance of the lockstep V1/V2 step, one launch (sample.hip)
 int32_t amt_launch_v2_decide_fused(const float* logits, int ld_logits, int32_t* state_dev, int64_t* tokens, int64_t* roots, int64_t* attrs,
                                    int B, int T, int n_primer, int beam, int max_conseq_N, int max_conseq_chord, float temperature,

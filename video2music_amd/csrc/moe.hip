@@ -191,6 +191,36 @@ __global__ __launch_bounds__(256) void moe_place_kernel(const int* __restrict__ 
     }
 }
 
+// The placement in assignment order, for training: expert e's rows ascend with the assignment index token * k + j, so that a sum over
+// a segment's rows (the backward's weight gradients) has one order whatever the scheduling -- moe_place_kernel's order inside a segment
+// follows its atomics.  One block per expert walks the assignments 256 at a time (ballot + prefix of the four waves' counts).
+__global__ __launch_bounds__(256) void moe_place_stable_kernel(const int* __restrict__ idx, int n_assign, const int* __restrict__ offsets,
+                                                               int* __restrict__ perm, int* __restrict__ slot_pos, int k) {
+    __shared__ int wsum[4];
+    const int e = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int base = offsets[e];
+    for (int i0 = 0; i0 < n_assign; i0 += 256) {             // the trip count is the block's: the barriers are uniform
+        const int i = i0 + threadIdx.x;
+        const bool mine = i < n_assign && idx[i] == e;
+        const unsigned long long b = __ballot(mine);
+        const int before = __popcll(b & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[wave] = __popcll(b);
+        __syncthreads();
+        int off = 0, total = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) off += wsum[w];
+            total += wsum[w];
+        }
+        if (mine) {
+            const int pos = base + off + before;
+            perm[pos] = i / k;
+            slot_pos[i] = pos;
+        }
+        base += total;
+        __syncthreads();
+    }
+}
+
 __global__ void moe_combine_kernel(const float* __restrict__ Y, const int* __restrict__ slot_pos,
                                    const int* __restrict__ idx, const float* __restrict__ wts,
                                    const float* __restrict__ shared, float shared_scale, float* __restrict__ out, int d,
@@ -475,6 +505,31 @@ int32_t amt_launch_moe_route_combine(const float* x, const float* gate_w, const 
     AMT_CHECK_ARG(n_tok > 0 && n_exp >= 2 && n_exp <= 64 && d % 4 == 0, "moe_route_combine: bad shape");
     hipLaunchKernelGGL(moe_route_combine_kernel, dim3(n_tok), dim3(128), 0, stream, x, gate_w, gate_b, n_exp, y_all, shared, shared_scale, resid, out,
                        n_tok, d);
+    AMT_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the layer's first and last launches for the training forward (moe_bwd.hip): moe_fwd_impl's kernels in its order, but for the
+//      placement, which is the stable one (every output row is computed independently: the forward's values do not depend on it) ----
+// router + plan: idx / wts (n_tok, k), perm (Mp), slot_pos (n_tok k), tile_group (Mp / 128), plan_ints (256: [64..128] keeps the segment offsets)
+int32_t amt_launch_moe_route_plan(const float* x, const float* gate_w, const float* gate_b, int32_t* idx, float* wts, int32_t* plan_ints,
+                                  int32_t* perm, int32_t* slot_pos, int32_t* tile_group, int n_tok, int d, int n_exp, int k, int Mp,
+                                  hipStream_t s) {
+    AMT_HIP(hipMemsetAsync(plan_ints, 0, 64 * sizeof(int), s));
+    if (k == 2) hipLaunchKernelGGL(moe_route_kernel, dim3(cdiv(n_tok, 4)), dim3(256), 0, s, x, gate_w, gate_b, n_tok, d, n_exp, idx, wts);
+    else hipLaunchKernelGGL(moe_route_k_kernel, dim3(cdiv(n_tok, 4)), dim3(256), 0, s, x, gate_w, gate_b, n_tok, d, n_exp, k, idx, wts);
+    AMT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(moe_count_kernel, dim3(cdiv(k * n_tok, 256)), dim3(256), 0, s, idx, k * n_tok, plan_ints);
+    hipLaunchKernelGGL(moe_offsets_kernel, dim3(1), dim3(1024), 0, s, plan_ints, plan_ints + 64, plan_ints + 192, n_exp, perm, tile_group, Mp);
+    hipLaunchKernelGGL(moe_place_stable_kernel, dim3(n_exp), dim3(256), 0, s, idx, k * n_tok, plan_ints + 64, perm, slot_pos, k);
+    AMT_LAUNCH_CHECK();
+    return 0;
+}
+
+int32_t amt_launch_moe_combine_k(const float* y_rows, const int32_t* slot_pos, const int32_t* idx, const float* wts, const float* shared,
+                                 float* out, int n_tok, int d, int k, hipStream_t s) {
+    if (k == 2) hipLaunchKernelGGL(moe_combine_kernel, dim3(n_tok), dim3(128), 0, s, y_rows, slot_pos, idx, wts, shared, 0.5f, out, d);
+    else hipLaunchKernelGGL(moe_combine_k_kernel, dim3(n_tok), dim3(128), 0, s, y_rows, slot_pos, idx, wts, shared, 1.0f / (float)k, out, d, k);
     AMT_LAUNCH_CHECK();
     return 0;
 }

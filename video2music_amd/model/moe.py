@@ -1,11 +1,11 @@
 """``GLUExpert`` / ``MoELayer`` / ``SharedMoELayer`` on the HIP path (reference ``model/moe.py:36-49,
-150-200, 202-302``), eval mode.
+150-200, 202-302``).
 
 Same parameter names (``experts.{e}.linear1|linear2|gate``, ``gate``, ``shared_expert``, buffer
 ``bias`` when ``balancing``).  The reference's module-global logging side effects
 (``update_maxvio`` / ``update_expert_counts``) are deliberately not replicated.
-Training-time behaviour (top-k / temperature schedulers, balancing-bias updates) is out of scope:
-``forward`` raises in training mode.
+In training mode ``forward`` goes through ``autograd.MoEFn`` (``amt_moe_train_fwd`` / ``amt_moe_bwd``) with fixed k and
+temperature 1; top-k / temperature schedulers, balancing-bias updates and expert-parallel execution are refused there with the reason.
 """
 import copy
 
@@ -307,9 +307,70 @@ class _MoEBase(nn.Module):
             self._stack_sig = sig
         return self._stack
 
+    def _train_refusal(self):
+        """Why this layer does not train here, or None: the reference's callers train with fixed k and temperature 1."""
+        if hasattr(self, "topk_scheduler") or hasattr(self, "temperature_scheduler"):
+            return "MoE training with a top-k / temperature scheduler is not built (no reference caller trains with one)"
+        if getattr(self, "balancing", False):
+            return "MoE training with balancing=True (the routing-bias update) is not built"
+        if self.expert_parallel:
+            return "MoE training under expert-parallel execution is not built"
+        return None
+
+    def dropout_rates(self):
+        """(inside the experts, on a chosen expert's output, inside the shared expert): the three dropout sites' rates, 0 where the
+        layer has no such site.  The inner rate is the expert's own (GLUExpert's default 0.1 unless its builder said otherwise)."""
+        inner = lambda e: float(e[2].p if isinstance(e, SiLUExpert) else e.dropout.p)
+        return inner(self.experts[0]), float(self.dropout.p), inner(self.shared_expert) if self.shared else 0.0
+
+    def _run_train(self, x):
+        """Training mode (moe.py:167-200, 231-302 with fixed k, temperature 1): `autograd.MoEFn` on the module's own parameters.
+        Dropout sits where the reference has it -- inside every expert (GLUExpert.dropout on linear1 * silu(gate); the Dropout at
+        index 2 of a SiLU expert), on each chosen expert's output before its routing weight (self.dropout, :199 / :298), inside the
+        shared expert (whose output has none, :301).  The multipliers, rows by assignment token * k + j, are drawn by torch on the
+        device or taken in the order [mask_h, mask_y, mask_hs] from `self.dropout_masks` when that is a list; sites with p = 0 are
+        skipped; the ones used are kept in `self.last_dropout_masks`."""
+        from .. import autograd as AG
+        why = self._train_refusal()
+        if why:
+            raise NotImplementedError(why)
+        if x.dim() != 3:
+            raise ValueError("MoE layers take (L, B, d) input (moe.py:193,292 unpack three indices)")
+        if x.device.type != "cuda":
+            raise _lib.AmtError("MoE layers run on an MI355X only; video2music_amd has no CPU fallback")
+        k = int(self.n_experts_per_token)
+        if not 1 <= k <= min(8, self.n_experts):
+            raise NotImplementedError(f"n_experts_per_token={k}: the gfx950 MoE path routes to 1..8 experts per token")
+        L, B, d = x.shape
+        n_tok = L * B
+        raw = expert_parts(self.experts[0])["gate"].out_features
+        p_in, p_out, p_shared = self.dropout_rates()
+        given = list(self.dropout_masks) if getattr(self, "dropout_masks", None) is not None else None
+        used = []
+
+        def mask(shape, p):
+            if p <= 0.0:
+                return None
+            m = given.pop(0) if given is not None else AG.dropout_mask(shape, p, x.device)
+            used.append(m)
+            return m.to(torch.float32).reshape(shape).contiguous()
+
+        masks = [mask((n_tok * k, raw), p_in), mask((n_tok * k, d), p_out), mask((n_tok, raw), p_shared)]
+        shared = expert_tensors(self.shared_expert) if self.shared else None
+        plan = {"k": k, "n_exp": self.n_experts, "dff_raw": raw, "masks": tuple(masks), "stacked": self._stacked_expert_weights(),
+                "shared": shared}
+        own = lambda e: [q for name in ("linear1", "gate", "linear2") for lin in [expert_parts(e)[name]] if lin is not None
+                         for q in (lin.weight, lin.bias)]
+        params = [q for e in self.experts for q in own(e)] + (own(self.shared_expert) if self.shared else [])
+        out = AG.MoEFn.apply(x.to(torch.float32).reshape(n_tok, d), plan, self.gate.weight, self.gate.bias, *params)
+        idx, wts = plan.pop("routing")
+        self.last_routing = (idx.view(L, B, k), wts.view(L, B, k))
+        self.__dict__["last_dropout_masks"] = used
+        return out.view(L, B, d)
+
     def _run(self, x):
         if self.training:
-            raise NotImplementedError("MoE training (schedulers, balancing updates) is outside the hot path")
+            return self._run_train(x)
         if x.dim() != 3:
             raise ValueError("MoE layers take (L, B, d) input (moe.py:193,292 unpack three indices)")
         if x.device.type != "cuda":
@@ -354,8 +415,8 @@ class MoELayer(_MoEBase):
         self.dropout = nn.Dropout(dropout)
         self.experts = nn.ModuleList([copy.deepcopy(expert) for _ in range(n_experts)])    # _get_clones, :157
         self.gate = nn.Linear(d_model, n_experts)
-        # moe.py:167-179: both schedulers act under `self.training` only; this build is inference-only (forward refuses
-        # training mode), so they are kept as attributes like the reference does and have no effect
+        # moe.py:167-179: both schedulers act under `self.training` only; training with one is refused here, so they are kept as
+        # attributes like the reference does and have no effect
         if topk_scheduler is not None:
             self.topk_scheduler = topk_scheduler
         if temperature_scheduler is not None:

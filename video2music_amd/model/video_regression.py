@@ -22,7 +22,8 @@ Training: for 'lstm' / 'bilstm' / 'gru' / 'bigru' and for 'bimamba+' / 'bimamba'
 state with gradients enabled build their result through the autograd Functions of `video2music_amd/autograd.py` on the module's own
 parameters (amt_rnn_seq_train_fwd / amt_rnn_seq_bwd; amt_selective_scan_train_fwd / amt_selective_scan_bwd / amt_dwconv1d_silu_bwd /
 amt_layernorm_bwd; the same GEMMs), so `loss.backward()` and a torch optimiser work; every other state and regModel runs the
-inference path above on detached parameters ('mamba' / 'mamba+' lack an RMSNorm backward, the mixture heads the mixture layer's).
+inference path above on detached parameters ('mamba' / 'mamba+' and 'moemamba' lack an RMSNorm backward).  'moe_bimamba+' /
+'sharedmoe_bimamba+' train too: their mixture layer goes through autograd.MoEFn (amt_moe_train_fwd / amt_moe_bwd).
 """
 import math
 
@@ -272,9 +273,10 @@ class VideoRegression(nn.Module):
         return ops.linear_ex(g, m.out_proj.weight.detach(), m.out_proj.bias.detach(), resid=resid)
 
     def _train_path(self):
-        """The state in which the four recurrent regModels and 'bimamba+' / 'bimamba' build an autograd graph
+        """The state in which the four recurrent regModels, 'bimamba+' / 'bimamba' and the two mixture heads build an autograd graph
         (video2music_amd/autograd.py); every other state and regModel runs the inference kernels on detached parameters."""
-        return self.training and torch.is_grad_enabled() and self.regModel in ("lstm", "bilstm", "gru", "bigru", "bimamba+", "bimamba")
+        return self.training and torch.is_grad_enabled() and self.regModel in ("lstm", "bilstm", "gru", "bigru", "bimamba+", "bimamba",
+                                                                                "moe_bimamba+", "sharedmoe_bimamba+")
 
     def _get_feature_train(self, vf, B, S):
         """get_feature's recurrent and bidirectional-Mamba branches through the autograd Functions, on the module's own parameters.
@@ -296,6 +298,8 @@ class VideoRegression(nn.Module):
             mask = given.pop(0) if given is not None else AG.dropout_mask(x.shape, p, x.device)
             used.append(mask)
             return x * mask
+
+        drop.given, drop.used = given, used       # a mixture layer takes its own masks from, and leaves them in, the same two lists
 
         lin = self.in_proj[0]
         x = drop(AG.LinearFn.apply(vf, lin.weight, lin.bias, 0, self._Win), self.in_proj[1].p)
@@ -332,6 +336,14 @@ class VideoRegression(nn.Module):
                 return AG.LinearFn.apply(h, f[3].weight, f[3].bias, 0, None, resid), None
             return drop(AG.LinearFn.apply(h, f[3].weight, f[3].bias), p_out), resid
 
+        def mixture(x, layer, p_out):            # dropout(mixture(x)), the residual left to the norm; the layer's masks [inside the
+            n = sum(q > 0.0 for q in layer.dropout_rates())     # experts, on their outputs, inside the shared expert] come before p_out's
+            layer.dropout_masks = [drop.given.pop(0) for _ in range(n)] if drop.given is not None else None
+            f = layer(x.view(B, S, self.d_model)).reshape(B * S, self.d_model)
+            layer.dropout_masks = None
+            drop.used.extend(layer.last_dropout_masks)
+            return drop(f, p_out), x
+
         ln = lambda t, r, n: AG.LayerNormFn.apply(t, r, n.weight, n.bias, n.eps)
         p = self.in_proj[1].p                    # the model's one dropout rate: the encoder and its FFNs get the same (video_regression.py:159-167)
         for i, lyr in enumerate(self.model.layers):
@@ -344,7 +356,7 @@ class VideoRegression(nn.Module):
                 xf = ln(*block(x, lyr.mamba_forward, 2 * i, False, p), lyr.norm1)
                 xb = ln(*block(x, lyr.mamba_backward, 2 * i + 1, True, p), lyr.norm2)
                 s = xb + xf
-                x = ln(*ffn(s, lyr.ffn, s, p, p), lyr.norm3)
+                x = ln(*(ffn(s, lyr.ffn, s, p, p) if isinstance(lyr.ffn, nn.Sequential) else mixture(s, lyr.ffn, p)), lyr.norm3)
         return x
 
     def get_feature(self, feature_semantic_list, feature_scene_offset, feature_motion, feature_emotion):

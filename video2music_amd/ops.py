@@ -381,3 +381,53 @@ def reg_metrics(feat, w_heads, note_density, loudness, instrument, return_rows=F
     _lib.call("amt_reg_metrics_fwd", C.c_void_p(feat.data_ptr()), ld, W, p(w_heads), p(note_density), p(loudness), p(instrument), B, S,
               p(clip), p(ln_nd), p(inst), _st())
     return (clip, ln_nd, inst) if return_rows else clip
+
+
+def moe_train(x, gate_w, gate_b, experts, shared, masks, k, dff_raw):
+    """amt_moe_train_fwd on x (n_tok, d): `experts` = (w1, b1, wg, bg, w2, b2) stacked over the experts at the padded hidden width
+    (w1 / b1 None: SiLU experts), `shared` the shared expert's six or six Nones, `masks` = (mask_h (n_tok k, dff_raw), mask_y
+    (n_tok k, d), mask_hs (n_tok, dff_raw)), each a multiplier tensor or None.  Returns out (n_tok, d), idx (n_tok, k) int32,
+    wts (n_tok, k) and `saved`, the buffer `moe_bwd` reads."""
+    n_tok, d = x.shape
+    n_exp, dff = experts[2].shape[0], experts[2].shape[1]
+    mask_h, mask_y, mask_hs = masks
+    assert mask_h is None or mask_h.shape == (n_tok * k, dff_raw)
+    assert mask_y is None or mask_y.shape == (n_tok * k, d)
+    assert mask_hs is None or mask_hs.shape == (n_tok, dff_raw)
+    for t in (x, gate_w, *experts, *shared, *masks):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    glu = int(experts[0] is not None)
+    out = torch.empty(n_tok, d, device=x.device, dtype=torch.float32)
+    idx = torch.empty(n_tok, k, device=x.device, dtype=torch.int32)
+    wts = torch.empty(n_tok, k, device=x.device, dtype=torch.float32)
+    saved = torch.empty(_lib.call("amt_moe_train_scratch_floats", n_tok, d, dff, n_exp, k, glu), device=x.device, dtype=torch.float32)
+    _lib.call("amt_moe_train_fwd", p(x), p(gate_w), p(gate_b), *[p(t) for t in experts], *[p(t) for t in shared], p(mask_h), p(mask_y),
+              p(mask_hs), p(out), p(idx), p(wts), p(saved), n_tok, d, dff, dff_raw, n_exp, k, _st())
+    return out, idx, wts, saved
+
+
+def moe_bwd(dout, x, gate_w, saved, experts_t, shared_t, masks, k, dff_raw, n_exp, temperature=1.0):
+    """amt_moe_bwd: the backward of `moe_train` from dout (n_tok, d) and its `saved`.  `experts_t` = (w1t, wgt, w2t), the stacked
+    weights transposed ((n_exp, d, dff), (n_exp, d, dff), (n_exp, dff, d); w1t None: SiLU experts), `shared_t` the shared expert's three
+    or None.  Returns dx, dgate_w, dgate_b, the experts' (dw1, db1, dwg, dbg, dw2, db2) stacked at the padded width and the shared
+    expert's six (None where the layer has no such tensor)."""
+    n_tok, d = x.shape
+    w1t, wgt, w2t = experts_t
+    dff = w2t.shape[1]
+    glu, has_shared = int(w1t is not None), int(shared_t is not None)
+    sw1t, swgt, sw2t = shared_t if has_shared else (None, None, None)
+    for t in (dout, x, gate_w, saved, *experts_t, sw1t, swgt, sw2t, *masks):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    assert dout.shape == x.shape and wgt.shape == (n_exp, d, dff) and w2t.shape == (n_exp, dff, d)
+    new = lambda *shape: torch.empty(*shape, device=x.device, dtype=torch.float32)
+    dx, dgw, dgb = new(n_tok, d), new(n_exp, d), new(n_exp)
+    dw1, db1 = (new(n_exp, dff, d), new(n_exp, dff)) if glu else (None, None)
+    dwg, dbg, dw2, db2 = new(n_exp, dff, d), new(n_exp, dff), new(n_exp, d, dff), new(n_exp, d)
+    dsh = [None] * 6
+    if has_shared:
+        dsh = [new(dff, d) if glu else None, new(dff) if glu else None, new(dff, d), new(dff), new(d, dff), new(d)]
+    ws = new(_lib.call("amt_moe_bwd_ws_floats", n_tok, d, dff, n_exp, k))                # a call's own scratch (stream-ordered reuse)
+    _lib.call("amt_moe_bwd", p(dout), p(x), p(gate_w), p(saved), p(w1t), p(wgt), p(w2t), p(sw1t), p(swgt), p(sw2t), *[p(t) for t in masks],
+              p(dx), p(dgw), p(dgb), p(dw1), p(db1), p(dwg), p(dbg), p(dw2), p(db2), *[p(t) for t in dsh], p(ws), n_tok, d, dff, dff_raw,
+              n_exp, k, glu, has_shared, float(temperature), _st())
+    return dx, dgw, dgb, (dw1, db1, dwg, dbg, dw2, db2), tuple(dsh)

@@ -63,7 +63,8 @@ class LrStepTracker:
 
 UNBUILT = {"mamba": "the RMSNorm backward is not built", "mamba+": "the RMSNorm backward is not built",
            "moemamba": "the mixture layer's and the RMSNorm backward are not built (nor the backward of its wide-state scan)",
-           "moe_bimamba+": "the mixture layer's backward is not built", "sharedmoe_bimamba+": "the mixture layer's backward is not built",
+           "moe_bimamba+": "the mixture heads train through python -m video2music_amd.train_regression_moe",
+           "sharedmoe_bimamba+": "the mixture heads train through python -m video2music_amd.train_regression_moe",
            "cnngru": "the backward of its convolution front is not built", "cnnbigru": "the backward of its convolution front is not built"}
 
 

@@ -4,8 +4,8 @@ callers build by default and its original-gate sibling, and the four recurrent h
 Flags, loop, output files, CSV header and ``weights_regression_<regModel>/`` naming are ``train_regression``'s; ``-regModel``
 defaults to ``bimamba+`` here.  A step runs ``autograd.MambaBlockFn`` (``amt_selective_scan_train_fwd``, ``amt_selective_scan_bwd``,
 ``amt_dwconv1d_silu_bwd`` and the library's GEMMs), ``LayerNormFn`` and ``LinearFn``.  Still refused, with the reason: ``mamba`` /
-``mamba+`` (no RMSNorm backward), ``moemamba`` / ``moe_bimamba+`` / ``sharedmoe_bimamba+`` (no mixture-layer backward), ``cnngru`` /
-``cnnbigru``.
+``mamba+`` / ``moemamba`` (no RMSNorm backward), ``moe_bimamba+`` / ``sharedmoe_bimamba+`` (they train through
+``python -m video2music_amd.train_regression_moe``), ``cnngru`` / ``cnnbigru``.
 
     python -m video2music_amd.train_regression_mamba -dataset_dir ./dataset/ -epochs 50
 """
