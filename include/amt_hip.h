@@ -37,7 +37,7 @@
 #define AMT_HIP_H
 #include <stdint.h>
 
-#define AMT_ABI_VERSION 10   /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
+#define AMT_ABI_VERSION 11   /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
                                 3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights;
                                 4: amt_chord_metrics_fwd;
                                 5: amt_reg_metrics_fwd;
@@ -47,7 +47,8 @@
                                 8: amt_selective_scan_train_fwd, amt_selective_scan_bwd, amt_selective_scan_bwd_ws_floats,
                                    amt_dwconv1d_silu_bwd, amt_dwconv1d_silu_bwd_ws_floats;
                                 9: amt_gemm_route, amt_attn_route;
-                                10: amt_moe_train_scratch_floats, amt_moe_train_fwd, amt_moe_bwd_ws_floats, amt_moe_bwd */
+                                10: amt_moe_train_scratch_floats, amt_moe_train_fwd, amt_moe_bwd_ws_floats, amt_moe_bwd;
+                                11: amt_moe_wgrad_splits */
 
 #ifdef __cplusplus
 extern "C" {
@@ -349,6 +350,11 @@ int32_t amt_moe_bwd(const float* dout, const float* x, const float* gate_w, cons
                     float* dsw1, float* dsb1, float* dswg, float* dsbg, float* dsw2, float* dsb2,
                     float* ws, int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, int32_t glu,
                     int32_t has_shared, float temperature, void* stream);
+/* Into how many runs amt_moe_bwd cuts each group's 128-row tiles in its weight-gradient products for this shape (1: no second pass):
+ * dense = 0 the experts' products over the plan's k n_tok assignments, dense != 0 the one-group products over the tokens (shared
+ * expert, router).  The launcher's own plan function, evaluated on the host: no device, no stream; a count, not a status; negative
+ * for a shape amt_moe_bwd refuses. */
+int32_t amt_moe_wgrad_splits(int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp, int32_t k, int32_t dense);
 
 /* Pieces of the same layer for expert-parallel execution (config 5: one expert group per GPU; the token rows
  * travel by all_to_all between amt_moe_route_fwd and amt_moe_combine_fwd, see video2music_amd/model/moe.py):

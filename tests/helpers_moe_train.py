@@ -19,6 +19,7 @@ FULL64 = ("sharedmoe_bimamba+",)  # its full fp64 gradients are recorded
 N_EXPERTS, TOP_K = 6, 2           # video_regression.py:143-178
 SEED = 0                          # of video2music_amd.synthetic for the fixture's weights
 GAP = 1e-4                        # smallest admitted gap between a token's k-th and (k+1)-th gate logit, relative to the largest |logit|
+TILE = 128                        # rows of a plan tile (csrc/moe.hip, csrc/moe_bwd.hip)
 
 
 def expert(P, pre, x, mask_h=None):
@@ -38,21 +39,28 @@ def gate_logits(P, pre, x):
     return x @ P[pre + "gate.weight"].T + P[pre + "gate.bias"]
 
 
+def gate_gaps(logits, k):
+    """Per token (k-th largest - (k+1)-th largest logit) / max|logit| over all tokens."""
+    top = torch.topk(logits.detach().double(), k + 1, dim=-1).values
+    return (top[..., k - 1] - top[..., k]) / logits.detach().abs().max()
+
+
 def gate_gap(logits, k):
     """min over tokens of (k-th largest - (k+1)-th largest logit) / max|logit|; inf when k is the number of experts."""
     if k >= logits.shape[-1]:
         return float("inf")
-    top = torch.topk(logits.detach().double(), k + 1, dim=-1).values
-    return float((top[..., k - 1] - top[..., k]).min() / logits.detach().abs().max())
+    return float(gate_gaps(logits, k).min())
 
 
-def moe_layer(P, pre, x, n_experts, k, shared, masks=None, routing=None):
+def moe_layer(P, pre, x, n_experts, k, shared, masks=None, routing=None, temperature=1.0):
     """x (n_tok, d) -> (n_tok, d).  masks = (mask_h (n_tok k, dff), mask_y (n_tok k, d), mask_hs (n_tok, dff)), each a multiplier
     tensor or None, rows by assignment token * k + j with j the position in topk's order.  routing (dict) receives idx, weights and
-    the gate logits."""
+    the gate logits.  temperature: the logits are divided by it before the top-k and the softmax (moe.py:288)."""
     mask_h, mask_y, mask_hs = masks if masks is not None else (None, None, None)
     n_tok = x.shape[0]
     logits = gate_logits(P, pre, x)
+    if temperature != 1.0:
+        logits = logits / temperature
     top, idx = torch.topk(logits, k, dim=-1)
     w = torch.softmax(top, dim=-1)
     out = torch.zeros_like(x)
@@ -135,7 +143,8 @@ def model_grads(sd, reg_model, n_layers, sem, emo, note_density, loudness, instr
         loss = T.train_loss(ln_nd, p, t(note_density), t(loudness), t(instrument))
         loss.backward()
     return {"loss": float(loss.detach()), "ln_nd": ln_nd.detach().numpy().astype(np.float64), "p": p.detach().numpy().astype(np.float64),
-            "grads": {k: v.grad.numpy().astype(np.float64) for k, v in P.items()}, "routing": routing}
+            "grads": {k: (torch.zeros_like(v) if v.grad is None else v.grad).numpy().astype(np.float64) for k, v in P.items()},      # None: an expert without a token
+            "routing": routing}
 
 
 def sgd_updates(sd, steps, lr, *args, dtype=torch.float64, routings=None, **kw):
@@ -151,14 +160,15 @@ def sgd_updates(sd, steps, lr, *args, dtype=torch.float64, routings=None, **kw):
 
 # ---- the layer alone (tests/test_moe_bwd_gpu.py) ----
 
-def layer_params(n_tok, d, dff_raw, n_exp, k, shared, glu, seed, force_expert0=False):
+def layer_params(n_tok, d, dff_raw, n_exp, k, shared, glu, seed, force_expert0=False, redraw=None):
     """Inputs and parameters of one mixture layer as float32 numpy arrays with the modules' key names: x, dout, and P.  force_expert0:
-    the gate's bias puts expert 0 into every token's top-k."""
+    True: the gate's bias (8) puts expert 0 into every token's top-k; a number: that bias for expert 0.  redraw = (seed, min_gap): the
+    rows of x whose fp64 gate gap is below min_gap are drawn again, pass after pass, until none is."""
     rng = np.random.default_rng(seed)
     f = lambda *s, scale=1.0: (rng.standard_normal(s) * scale).astype(np.float32)
     P = {"gate.weight": f(n_exp, d, scale=d ** -0.5), "gate.bias": f(n_exp, scale=0.1)}
-    if force_expert0:
-        P["gate.bias"][0] = 8.0         # the other logits are N(0, 1.01): none of a few hundred tokens' reaches it
+    if force_expert0:                   # at 8 the other logits are N(0, 1.01): none of a few hundred tokens' reaches it
+        P["gate.bias"][0] = 8.0 if force_expert0 is True else float(force_expert0)
     names = ["experts.%d." % e for e in range(n_exp)] + (["shared_expert."] if shared else [])
     for pre in names:
         if glu:
@@ -168,17 +178,37 @@ def layer_params(n_tok, d, dff_raw, n_exp, k, shared, glu, seed, force_expert0=F
         else:
             P[pre + "0.weight"], P[pre + "0.bias"] = f(dff_raw, d, scale=d ** -0.5), f(dff_raw, scale=0.1)
             P[pre + "3.weight"], P[pre + "3.bias"] = f(d, dff_raw, scale=dff_raw ** -0.5), f(d, scale=0.1)
-    return f(n_tok, d), f(n_tok, d), P
+    x, dout = f(n_tok, d), f(n_tok, d)
+    if redraw is not None:
+        rng2, gw, gb = np.random.default_rng(redraw[0]), torch.from_numpy(P["gate.weight"]).double(), torch.from_numpy(P["gate.bias"]).double()
+        for _ in range(8):
+            close = np.nonzero((gate_gaps(torch.from_numpy(x).double() @ gw.T + gb, k) < redraw[1]).numpy())[0]
+            if close.size == 0:
+                break
+            x[close] = rng2.standard_normal((close.size, d)).astype(np.float32)
+    return x, dout, P
 
 
-def layer_grads(x, dout, P, n_exp, k, shared, masks=None, dtype=torch.float64):
+def split_plan(idx, n_exp, S):
+    """How the grouped weight-gradient product walks the routing idx (n_tok, k) at S runs per group: per expert (rows, 128-row tiles,
+    [tiles of run 0, ..., run S - 1]).  A run holds ceil(tiles / S) tiles; what is left once the tiles run out is short or empty."""
+    out = []
+    for e in range(n_exp):
+        rows = int((np.asarray(idx) == e).sum())
+        tiles = -(-rows // TILE)
+        per = -(-tiles // S)                                     # tiles per run = ceil(tiles / S)
+        out.append((rows, tiles, [max(0, min(per, tiles - z * per)) for z in range(S)]))
+    return out
+
+
+def layer_grads(x, dout, P, n_exp, k, shared, masks=None, dtype=torch.float64, temperature=1.0):
     """out and the gradients of <out, dout> for x and every parameter, in `dtype`; plus the routing."""
     with torch.enable_grad():
         t = lambda a: None if a is None else torch.as_tensor(np.asarray(a)).to(dtype)
         Pt = {key: t(v).requires_grad_(True) for key, v in P.items()}
         xt = t(x).requires_grad_(True)
         r = {}
-        out = moe_layer(Pt, "", xt, n_exp, k, shared, None if masks is None else tuple(t(m) for m in masks), r)
+        out = moe_layer(Pt, "", xt, n_exp, k, shared, None if masks is None else tuple(t(m) for m in masks), r, temperature)
         (out * t(dout)).sum().backward()
     g = {key: (torch.zeros_like(v) if v.grad is None else v.grad).numpy().astype(np.float64) for key, v in Pt.items()}   # None: an expert without a token
     g["x"] = xt.grad.numpy().astype(np.float64)

@@ -48,15 +48,19 @@ def scan_gate(x, draw, dt_bias, A_log, Bm, Cm, D, z, version, reverse=False):
 
 # ---- the whole model ----
 
-def mamba_block(P, pre, x, version, reverse):
-    """MambaBlock.forward (no inner layernorms) with the parameters P[pre + ...] on x (B, L, d)."""
+def mamba_block(P, pre, x, version, reverse, wrong=()):
+    """MambaBlock.forward (no inner layernorms) with the parameters P[pre + ...] on x (B, L, d).  wrong: names of deliberate errors
+    (the sensitivity checks of tests/test_reg_train_edges_host.py): "ddbc_dt_columns_zero" sends no gradient from the dt projection
+    back into the x projection's first dt_rank columns; "reverse_conv_taps_unflipped" gives the time-flipped branch the taps in the
+    forward branch's order."""
     ED, R = P[pre + "D"].shape[0], P[pre + "dt_proj.weight"].shape[1]
     N = P[pre + "A_log"].shape[1]
     xz = x @ P[pre + "in_proj.weight"].T + P[pre + "in_proj.bias"]
     xi, z = xz[..., :ED], xz[..., ED:]
-    xc = conv_silu(xi, P[pre + "conv1d.weight"][:, 0], P[pre + "conv1d.bias"], reverse)
+    taps = P[pre + "conv1d.weight"][:, 0]
+    xc = conv_silu(xi, taps.flip(1) if reverse and "reverse_conv_taps_unflipped" in wrong else taps, P[pre + "conv1d.bias"], reverse)
     dbc = xc @ P[pre + "x_proj.weight"].T
-    draw = dbc[..., :R] @ P[pre + "dt_proj.weight"].T
+    draw = (dbc.detach() if "ddbc_dt_columns_zero" in wrong else dbc)[..., :R] @ P[pre + "dt_proj.weight"].T
     g = scan_gate(xc, draw, P[pre + "dt_proj.bias"], P[pre + "A_log"], dbc[..., R:R + N], dbc[..., R + N:R + 2 * N], P[pre + "D"], z,
                   version, reverse)
     return g @ P[pre + "out_proj.weight"].T + P[pre + "out_proj.bias"]
@@ -69,8 +73,9 @@ def mask_widths(reg_model, n_layers, d_model, d_hidden):
     return [d_model] + per * n_layers
 
 
-def model_forward(P, reg_model, n_layers, sem, emo, masks=None):
-    """-> ln_nd (B, S, 2), p (B, S, 40) of the training-state forward; masks: the dropout multipliers in use order (None: dropout 0)."""
+def model_forward(P, reg_model, n_layers, sem, emo, masks=None, wrong=(), pre_relu=None):
+    """-> ln_nd (B, S, 2), p (B, S, 40) of the training-state forward; masks: the dropout multipliers in use order (None: dropout 0).
+    wrong: see `mamba_block`; pre_relu (list) receives every feed-forward's pre-activation, in forward order."""
     masks = list(masks) if masks is not None else None
     version = 1 if reg_model.endswith("+") else 0
     vf = torch.cat([sem, emo], dim=-1)
@@ -83,20 +88,23 @@ def model_forward(P, reg_model, n_layers, sem, emo, masks=None):
         return F.layer_norm(t, t.shape[-1:], P[pre + ".weight"], P[pre + ".bias"], 1e-5)
 
     def ffn(t, pre):
-        return drop(drop(torch.relu(t @ P[pre + ".0.weight"].T + P[pre + ".0.bias"])) @ P[pre + ".3.weight"].T + P[pre + ".3.bias"])
+        z = t @ P[pre + ".0.weight"].T + P[pre + ".0.bias"]
+        if pre_relu is not None:
+            pre_relu.append(z.detach())
+        return drop(drop(torch.relu(z)) @ P[pre + ".3.weight"].T + P[pre + ".3.bias"])
 
     x = drop(vf @ P["in_proj.0.weight"].T + P["in_proj.0.bias"])
     for i in range(n_layers):
         pre = f"model.layers.{i}."
         if version == 1:                                                  # BiMambaEncoderLayer_V1, norm_first False
-            xf = ln(drop(mamba_block(P, pre + "mamba_forward.", x, 1, False)) + x, pre + "norm1")
-            xb = ln(drop(mamba_block(P, pre + "mamba_backward.", x, 1, True)) + x, pre + "norm2")
+            xf = ln(drop(mamba_block(P, pre + "mamba_forward.", x, 1, False, wrong)) + x, pre + "norm1")
+            xb = ln(drop(mamba_block(P, pre + "mamba_backward.", x, 1, True, wrong)) + x, pre + "norm2")
             s = xf + xb
             x = ln(ffn(s, pre + "ffn") + s, pre + "norm3")
         else:                                                             # BiMambaEncoderLayer: ffn2 reads x_f
-            xf = ln(drop(mamba_block(P, pre + "mamba_forward.", x, 0, False)) + x, pre + "norm1")
+            xf = ln(drop(mamba_block(P, pre + "mamba_forward.", x, 0, False, wrong)) + x, pre + "norm1")
             xf = ln(ffn(xf, pre + "ffn1") + xf, pre + "norm2")
-            xb = ln(drop(mamba_block(P, pre + "mamba_backward.", x, 0, True)) + x, pre + "norm3")
+            xb = ln(drop(mamba_block(P, pre + "mamba_backward.", x, 0, True, wrong)) + x, pre + "norm3")
             xb = ln(ffn(xf, pre + "ffn2") + xb, pre + "norm4")
             x = xf + xb
     assert not masks
@@ -111,13 +119,13 @@ def train_loss(ln_nd, p, note_density, loudness, instrument):
     return F.smooth_l1_loss(ln_nd.reshape(-1, 2), tgt) + F.binary_cross_entropy(p, instrument)
 
 
-def model_grads(sd, reg_model, n_layers, sem, emo, note_density, loudness, instrument, masks=None, dtype=torch.float64):
+def model_grads(sd, reg_model, n_layers, sem, emo, note_density, loudness, instrument, masks=None, dtype=torch.float64, wrong=(), pre_relu=None):
     """The training loss and its gradient for every key of the state dict `sd` (numpy arrays) in `dtype`.
-    Returns {"loss", "ln_nd", "p", "grads": {key: float64 array}}."""
+    Returns {"loss", "ln_nd", "p", "grads": {key: float64 array}}.  wrong, pre_relu: `model_forward`'s."""
     with torch.enable_grad():
         P = {k: torch.as_tensor(np.asarray(v)).to(dtype).requires_grad_(True) for k, v in sd.items()}
         t = lambda a: torch.as_tensor(np.asarray(a)).to(dtype)
-        ln_nd, p = model_forward(P, reg_model, n_layers, t(sem), t(emo), None if masks is None else [t(m) for m in masks])
+        ln_nd, p = model_forward(P, reg_model, n_layers, t(sem), t(emo), None if masks is None else [t(m) for m in masks], wrong, pre_relu)
         loss = train_loss(ln_nd, p, t(note_density), t(loudness), t(instrument))
         loss.backward()
     return {"loss": float(loss.detach()), "ln_nd": ln_nd.detach().numpy().astype(np.float64), "p": p.detach().numpy().astype(np.float64),

@@ -60,8 +60,8 @@ def rnn_dir_fwd(G, X, Wi, bi, Wh, bh, reverse):
     """X (B, L, in) -> Y (B, L, d) and what the backward needs."""
     B, L, _ = X.shape
     d = Wh.shape[1]
-    h, c = np.zeros((B, d)), np.zeros((B, d))
-    Y, keep = np.zeros((B, L, d)), {}
+    h, c = np.zeros((B, d), X.dtype), np.zeros((B, d), X.dtype)
+    Y, keep = np.zeros((B, L, d), X.dtype), {}
     for t in _steps(L, reverse):
         ax, ah = X[:, t] @ Wi.T + bi, h @ Wh.T + bh
         if G == 4:
@@ -80,14 +80,15 @@ def rnn_dir_fwd(G, X, Wi, bi, Wh, bh, reverse):
     return Y, (X, Wi, Wh, keep, reverse)
 
 
-def rnn_dir_bwd(G, dY, cache):
-    """-> dX, dWi, dbi, dWh, dbh."""
+def rnn_dir_bwd(G, dY, cache, wrong=()):
+    """-> dX, dWi, dbi, dWh, dbh.  wrong: names of deliberate errors (the sensitivity checks of tests/test_reg_train_edges_host.py):
+    "gru_hidden_n_without_r" hands the n gate's gradient to the hidden side without the reset gate."""
     X, Wi, Wh, keep, reverse = cache
     B, L, _ = X.shape
     d = Wh.shape[1]
     dX, dWi, dWh = np.zeros_like(X), np.zeros_like(Wi), np.zeros_like(Wh)
-    dbi, dbh = np.zeros(G * d), np.zeros(G * d)
-    dh, dc = np.zeros((B, d)), np.zeros((B, d))
+    dbi, dbh = np.zeros(G * d, X.dtype), np.zeros(G * d, X.dtype)
+    dh, dc = np.zeros((B, d), X.dtype), np.zeros((B, d), X.dtype)
     for t in reversed(list(_steps(L, reverse))):
         dh = dh + dY[:, t]
         if G == 4:
@@ -104,7 +105,7 @@ def rnn_dir_bwd(G, dY, cache):
             daz = dh * (h_prev - n) * z * (1 - z)
             dar = dan * hl * r * (1 - r)
             dax = np.concatenate([dar, daz, dan], axis=1)
-            dah = np.concatenate([dar, daz, dan * r], axis=1)
+            dah = np.concatenate([dar, daz, dan if "gru_hidden_n_without_r" in wrong else dan * r], axis=1)
             dh = dah @ Wh + dh * z
         dX[:, t] = dax @ Wi
         dWi += dax.T @ X[:, t]
@@ -116,19 +117,22 @@ def rnn_dir_bwd(G, dY, cache):
 
 # ---- the whole model ----
 
-def model_grads64(sd, reg_model, n_layers, sem, emo, note_density, loudness, instrument, masks=None):
+def model_grads64(sd, reg_model, n_layers, sem, emo, note_density, loudness, instrument, masks=None, dtype=np.float64, wrong=(), collect=None):
     """The training loss of VideoRegression(regModel in lstm / bilstm / gru / bigru) and its gradient for every key of the state
     dict `sd`, in fp64.  masks: the dropout multipliers in use order (after in_proj (B, S, d), then after every recurrent layer but
-    the last (B, S, dirs d)); None = dropout 0.  Returns {"loss", "ln_nd", "p", "grads": {key: array}}."""
-    P = {k: np.asarray(v, dtype=np.float64) for k, v in sd.items()}
+    the last (B, S, dirs d)); None = dropout 0.  Returns {"loss", "ln_nd", "p", "grads": {key: array}}.
+    dtype: the precision of the arithmetic through the stack and the heads (np.float32: the noise level a bound is made of; the loss
+    and its two gradients are formed in fp64 from those values and rounded).  wrong: see `rnn_dir_bwd`.  collect (dict) receives
+    "d_x0", the gradient (B S, d) of the in-projection's output rows, and "vf", its input rows."""
+    P = {k: np.asarray(v, dtype=dtype) for k, v in sd.items()}
     G, dirs = (4 if "lstm" in reg_model else 3), (2 if "bi" in reg_model else 1)
     masks = list(masks) if masks is not None else None
-    vf = np.concatenate([np.asarray(sem, dtype=np.float64), np.asarray(emo, dtype=np.float64)], axis=-1)
+    vf = np.concatenate([np.asarray(sem, dtype=dtype), np.asarray(emo, dtype=dtype)], axis=-1)
     B, S, _ = vf.shape
     grads = {}
 
     x0 = vf @ P["in_proj.0.weight"].T + P["in_proj.0.bias"]
-    m0 = np.asarray(masks.pop(0), dtype=np.float64).reshape(x0.shape) if masks is not None else None
+    m0 = np.asarray(masks.pop(0), dtype=dtype).reshape(x0.shape) if masks is not None else None
     x = x0 * m0 if m0 is not None else x0
     caches, layer_masks = [], []
     for l in range(n_layers):
@@ -142,13 +146,15 @@ def model_grads64(sd, reg_model, n_layers, sem, emo, note_density, loudness, ins
         caches.append(cs)
         m = None
         if l < n_layers - 1 and masks is not None:
-            m = np.asarray(masks.pop(0), dtype=np.float64).reshape(x.shape)
+            m = np.asarray(masks.pop(0), dtype=dtype).reshape(x.shape)
             x = x * m
         layer_masks.append(m)
     rows = x.reshape(B * S, -1)
     ln_nd = rows @ P["regressor.weight"].T + P["regressor.bias"]
     p = sigmoid(rows @ P["classifier.0.weight"].T + P["classifier.0.bias"])
     lo = loss64(ln_nd, p, note_density, loudness, instrument)
+    if dtype != np.float64:
+        lo = dict(lo, d_ln_nd=lo["d_ln_nd"].astype(dtype), d_logit=lo["d_logit"].astype(dtype))
 
     grads["regressor.weight"], grads["regressor.bias"] = lo["d_ln_nd"].T @ rows, lo["d_ln_nd"].sum(0)
     grads["classifier.0.weight"], grads["classifier.0.bias"] = lo["d_logit"].T @ rows, lo["d_logit"].sum(0)
@@ -160,7 +166,7 @@ def model_grads64(sd, reg_model, n_layers, sem, emo, note_density, loudness, ins
         dprev = 0.0
         for r in range(dirs):
             sfx = f"_l{l}" + ("_reverse" if r else "")
-            dX, dWi, dbi, dWh, dbh = rnn_dir_bwd(G, dx[..., r * d:(r + 1) * d], caches[l][r])
+            dX, dWi, dbi, dWh, dbh = rnn_dir_bwd(G, dx[..., r * d:(r + 1) * d], caches[l][r], wrong)
             for n, g in (("weight_ih", dWi), ("bias_ih", dbi), ("weight_hh", dWh), ("bias_hh", dbh)):
                 grads["model." + n + sfx] = g
             dprev = dprev + dX
@@ -168,6 +174,8 @@ def model_grads64(sd, reg_model, n_layers, sem, emo, note_density, loudness, ins
     if m0 is not None:
         dx = dx * m0
     dx = dx.reshape(B * S, -1)
+    if collect is not None:
+        collect["d_x0"], collect["vf"] = dx, vf.reshape(B * S, -1)
     grads["in_proj.0.weight"], grads["in_proj.0.bias"] = dx.T @ vf.reshape(B * S, -1), dx.sum(0)
     return {"loss": lo["loss"], "ln_nd": ln_nd.reshape(B, S, 2), "p": p.reshape(B, S, N_INST), "grads": grads}
 

@@ -91,13 +91,24 @@ def test_selective_scan_backward(shape, reverse, version):
     assert not bad, (bad, report)
 
 
-@pytest.mark.parametrize("reverse", [0, 1])
-@pytest.mark.parametrize("shape,K", [(s, 4) for s in SHAPES] + [((2, 33, 64), 8)])
-def test_dwconv_silu_backward(shape, K, reverse):
+# the kernel's block is 64 channels x 64 rows.  (3, 50, 80): three row slices, the last of 22 rows, and a second channel block of 16;
+# (1, 3, 130) at K = 8: fewer steps than taps, a third channel block of 2; K = 1: no neighbour at all
+DWCONV = [(s, 4) for s in SHAPES] + [((2, 33, 64), 8), ((3, 50, 80), 4), ((1, 3, 130), 8), ((2, 33, 24), 1)]
+
+
+def dwconv_case(shape, K):
     B, L, C = shape
     g = torch.Generator().manual_seed(L * 10 + K)
     M = B * L
-    xz, w, bias, dy = torch.randn(M, 2 * C, generator=g), 0.5 * torch.randn(C, K, generator=g), torch.randn(C, generator=g), torch.randn(M, C, generator=g)
+    return torch.randn(M, 2 * C, generator=g), 0.5 * torch.randn(C, K, generator=g), torch.randn(C, generator=g), torch.randn(M, C, generator=g)
+
+
+@pytest.mark.parametrize("reverse", [0, 1])
+@pytest.mark.parametrize("shape,K", DWCONV)
+def test_dwconv_silu_backward(shape, K, reverse):
+    B, L, C = shape
+    M = B * L
+    xz, w, bias, dy = dwconv_case(shape, K)
 
     def autograd(dtype):
         x, w_, b_ = (t.to(dtype).clone().requires_grad_(True) for t in (xz[:, :C].reshape(B, L, C), w, bias))
@@ -122,6 +133,40 @@ def test_dwconv_silu_backward(shape, K, reverse):
             bad.append(k)
     print(shape, "K", K, "reverse", reverse, " ".join(report))
     assert not bad, (bad, report)
+
+
+@pytest.mark.parametrize("reverse", [0, 1])
+def test_dwconv_silu_backward_without_a_bias(reverse):
+    """bias = dbias = null at the library call (ops.dwconv1d_silu_bwd always passes one): against autograd of the convolution without
+    a bias; and a bias without its gradient is refused."""
+    shape, K = (3, 50, 80), 4
+    B, L, C = shape
+    M = B * L
+    xz, w, _, dy = dwconv_case(shape, K)
+
+    def autograd(dtype):
+        x, w_ = (t.to(dtype).clone().requires_grad_(True) for t in (xz[:, :C].reshape(B, L, C), w))
+        (T.conv_silu(x, w_, torch.zeros(C, dtype=dtype), bool(reverse)) * dy.view(B, L, C).to(dtype)).sum().backward()
+        return {"dx": x.grad.reshape(M, C).numpy().astype(np.float64), "dw": w_.grad.numpy().astype(np.float64)}
+
+    P = _lib.ptr
+    dyd, xzd, wd = dy.to(DEV), xz.to(DEV), w.to(DEV)
+    dxz, dw = torch.full((M, 2 * C), float("nan"), device=DEV), torch.full((C, K), float("nan"), device=DEV)
+    ws = torch.empty(_lib.call("amt_dwconv1d_silu_bwd_ws_floats", B, L, C, K), device=DEV)
+    _lib.call("amt_dwconv1d_silu_bwd", P(dyd), C, P(xzd), 2 * C, P(wd), None, P(dxz), 2 * C, P(dw), None, P(ws), B, L, C, K, reverse,
+              _lib.stream_ptr())
+    assert torch.isnan(dxz[:, C:]).all()
+    got = {"dx": dxz[:, :C], "dw": dw}
+    g64, g32 = autograd(torch.float64), autograd(torch.float32)
+    report = []
+    for k, want in g64.items():
+        bound = max(8 * err(g32[k], want), (K if k == "dx" else M) * T.U)
+        e = err(got[k].cpu().numpy(), want)
+        report.append(f"{k} {e:.2e}/{bound:.2e}")
+        assert e <= bound, (k, e, bound)
+    print(shape, "K", K, "reverse", reverse, "no bias", " ".join(report))
+    with pytest.raises(_lib.AmtError, match="go together"):
+        _lib.call("amt_dwconv1d_silu_bwd", P(dyd), C, P(xzd), 2 * C, P(wd), P(wd), P(dxz), 2 * C, P(dw), None, P(ws), B, L, C, K, reverse, None)
 
 
 def test_refusals():

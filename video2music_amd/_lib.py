@@ -134,14 +134,15 @@ SIGNATURES = {
     "amt_dwconv1d_silu_bwd": [_P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "amt_gemm_route": [_I, _I, _I, _I, _I],
     "amt_attn_route": [_I, _I, _I, _I, _I, _I],
+    "amt_moe_wgrad_splits": [_I, _I, _I, _I, _I, _I],
 }
 _RESTYPES = {"amt_last_error": C.c_char_p, "amt_decode_step_bytes": C.c_int64, "amt_moe_scratch_floats": C.c_int64, "amt_moe_topk_scratch_floats": C.c_int64,
              "amt_v2_step_ws_floats": C.c_int64, "amt_v2_step_batch_ws_floats": C.c_int64, "amt_moe_ep_expert_scratch_floats": C.c_int64,
              "amt_chord_loss_ws_floats": C.c_int64, "amt_attn_bwd_ws_floats": C.c_int64, "amt_selective_scan_bwd_ws_floats": C.c_int64,
              "amt_dwconv1d_silu_bwd_ws_floats": C.c_int64, "amt_moe_train_scratch_floats": C.c_int64, "amt_moe_bwd_ws_floats": C.c_int64}
-_NO_STATUS = set(_RESTYPES) | {"amt_abi_version", "amt_v2_last_step_launches", "amt_gemm_route", "amt_attn_route"}
+_NO_STATUS = set(_RESTYPES) | {"amt_abi_version", "amt_v2_last_step_launches", "amt_gemm_route", "amt_attn_route", "amt_moe_wgrad_splits"}
 
-ABI_VERSION = 10        # AMT_ABI_VERSION of include/amt_hip.h these prototypes were written against
+ABI_VERSION = 11        # AMT_ABI_VERSION of include/amt_hip.h these prototypes were written against
 
 _lib = None
 

@@ -314,6 +314,11 @@ int wgrad_splits(long row_tiles, int n_groups, int cap) {
     const long per = row_tiles / n_groups;
     return (int)(per < 1 ? 1 : per > cap ? cap : per);
 }
+// amt_moe_bwd's S: of the experts' products over the plan's k n_tok assignments, or (dense) of the one-group products over the tokens
+int wgrad_plan_splits(int n_tok, int d, int dff, int n_exp, int k, int dense) {
+    const int cap = wgrad_split_cap(n_exp, d, dff);
+    return dense ? wgrad_splits(((long)n_tok + TILE - 1) / TILE, 1, cap) : wgrad_splits(((long)k * n_tok + TILE - 1) / TILE, n_exp, cap);
+}
 
 int32_t launch_wgrad(WgradParams p, float* ws, hipStream_t s) {
     float* out = p.out;
@@ -363,6 +368,11 @@ extern "C" int64_t amt_moe_train_scratch_floats(int32_t n_tok, int32_t d, int32_
 
 extern "C" int64_t amt_moe_bwd_ws_floats(int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp, int32_t k) {
     return (int64_t)bwd_layout(nullptr, n_tok, d, dff, n_exp, k).floats;
+}
+
+extern "C" int32_t amt_moe_wgrad_splits(int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp, int32_t k, int32_t dense) {
+    if (n_tok <= 0 || d <= 0 || dff <= 0 || n_exp < 2 || n_exp > 64 || k < 1 || k > KMAX || k > n_exp) return -1;
+    return wgrad_plan_splits(n_tok, d, dff, n_exp, k, dense);
 }
 
 extern "C" int32_t amt_moe_train_fwd(const float* x, const float* gate_w, const float* gate_b,
@@ -479,10 +489,8 @@ extern "C" int32_t amt_moe_bwd(const float* dout, const float* x, const float* g
         if ((rc = amt_launch_gemm(gx, s))) return rc;
     }
     // 6: the experts' weight gradients, over their own segments only
-    const int cap = wgrad_split_cap(n_exp, d, dff);
-    const int S = wgrad_splits(((long)A + TILE - 1) / TILE, n_exp, cap);
     WgradParams p{};
-    p.seg = seg; p.n_groups = n_exp; p.S = S;
+    p.seg = seg; p.n_groups = n_exp; p.S = wgrad_plan_splits(n_tok, d, dff, n_exp, k, 0);
     p.P = w.dY; p.ldp = d; p.N = d; p.Q = sv.H; p.ldq = dff; p.K = dff; p.q_gather = nullptr; p.out = dw2; p.bias = db2;
     if ((rc = launch_wgrad(p, w.split, s))) return rc;
     p.P = w.dG; p.ldp = dff; p.N = dff; p.Q = x; p.ldq = d; p.K = d; p.q_gather = sv.perm; p.out = dwg; p.bias = dbg;
@@ -493,7 +501,7 @@ extern "C" int32_t amt_moe_bwd(const float* dout, const float* x, const float* g
     }
     // 7: the shared expert on every token, from dout / k
     WgradParams q{};
-    q.rows = n_tok; q.n_groups = 1; q.S = wgrad_splits(((long)n_tok + TILE - 1) / TILE, 1, cap);
+    q.rows = n_tok; q.n_groups = 1; q.S = wgrad_plan_splits(n_tok, d, dff, n_exp, k, 1);
     if (has_shared) {
         hipLaunchKernelGGL(moe_scale_kernel, dim3((unsigned)(((long)n_tok * d / 4 + 255) / 256)), dim3(256), 0, s, dout, w.dYs, (long)n_tok * d / 4,
                            1.0f / (float)k);

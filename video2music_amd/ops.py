@@ -431,3 +431,12 @@ def moe_bwd(dout, x, gate_w, saved, experts_t, shared_t, masks, k, dff_raw, n_ex
               p(dx), p(dgw), p(dgb), p(dw1), p(db1), p(dwg), p(dbg), p(dw2), p(db2), *[p(t) for t in dsh], p(ws), n_tok, d, dff, dff_raw,
               n_exp, k, glu, has_shared, float(temperature), _st())
     return dx, dgw, dgb, (dw1, db1, dwg, dbg, dw2, db2), tuple(dsh)
+
+
+def moe_wgrad_splits(n_tok, d, dff, n_exp, k, dense=False):
+    """The runs per group of `moe_bwd`'s weight-gradient products at this shape (amt_moe_wgrad_splits; needs no GPU): the experts'
+    over the k n_tok assignments, or with `dense` the shared expert's and the router's over the tokens.  dff: the padded width."""
+    S = _lib.call("amt_moe_wgrad_splits", n_tok, d, dff, n_exp, k, int(dense))
+    if S < 1:
+        raise _lib.AmtError(f"amt_moe_wgrad_splits: amt_moe_bwd refuses n_tok={n_tok} d={d} dff={dff} n_exp={n_exp} k={k}")
+    return S
