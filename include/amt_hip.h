@@ -37,7 +37,7 @@
 #define AMT_HIP_H
 #include <stdint.h>
 
-#define AMT_ABI_VERSION 11   /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
+#define AMT_ABI_VERSION 12   /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
                                 3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights;
                                 4: amt_chord_metrics_fwd;
                                 5: amt_reg_metrics_fwd;
@@ -48,7 +48,9 @@
                                    amt_dwconv1d_silu_bwd, amt_dwconv1d_silu_bwd_ws_floats;
                                 9: amt_gemm_route, amt_attn_route;
                                 10: amt_moe_train_scratch_floats, amt_moe_train_fwd, amt_moe_bwd_ws_floats, amt_moe_bwd;
-                                11: amt_moe_wgrad_splits */
+                                11: amt_moe_wgrad_splits;
+                                12: amt_rope_bwd, amt_rmsnorm_bwd, amt_rmsnorm_bwd_blocks, amt_glu_train_scratch_floats, amt_glu_train_fwd,
+                                    amt_glu_bwd_ws_floats, amt_glu_bwd */
 
 #ifdef __cplusplus
 extern "C" {
@@ -655,6 +657,43 @@ int32_t amt_attn_bwd(const float* dO, const float* q, const float* k, const floa
 #define AMT_LAYERNORM_BWD_WS_FLOATS(dim) (4 + 256 * (dim))
 int32_t amt_layernorm_bwd(const float* dy, const float* x, const float* resid, const float* w, float* dx, float* dw, float* db,
                           float* ws, int32_t rows, int32_t dim, float eps, void* stream);
+
+/* What the training of the V1 / V2 chord models adds to the above (csrc/family_train.hip).  All three are fp32 and stateless, use no
+ * floating-point atomic and fix the order of every addition by the shapes alone: the same inputs give the same bits.
+ *
+ * amt_rope_bwd: the adjoint of amt_rope_fwd under the same index rule and the same shape checks (both cache layouts: the broadcast
+ * slab 2 cache_half == hd, and the [seq][cache_half][2] cache read as [n0][seq][hd/2][2]); each pair of dy is rotated by the transpose
+ * of the forward's rotation: dx0 = dy0 cos + dy1 sin, dx1 = dy1 cos - dy0 sin.  dx may be dy.  dy / dx 8-byte aligned. */
+int32_t amt_rope_bwd(const float* dy, const float* cache, float* dx, int32_t n0, int32_t seq, int32_t n2, int32_t hd,
+                     int32_t cache_half, void* stream);
+/* Backward of y = RMSNorm(x (+ resid)) * w (amt_rmsnorm_resid_fwd) from the forward's own inputs.  dy, x, resid (null = none), dx:
+ * (rows, dim); w, dw: (dim).  With u = x (+ resid), r = rsqrt(mean(u^2) + eps), xh = u r, g = dy w:
+ *   dx = r (g - xh mean(g xh))      (the gradient of x and of resid alike),   dw = sum over rows of dy xh
+ * dim a multiple of 4, at most 1024; any rows > 0.  ws: AMT_RMSNORM_BWD_WS_FLOATS(dim) floats of scratch, 16-byte aligned, used by this
+ * call alone until it has finished (a ticket counter, zeroed by the call, and one dw slab per workgroup).  amt_rmsnorm_bwd_blocks(rows)
+ * workgroups of 4 waves (the launcher's own rule, evaluated on the host: a count, not a status; negative for rows <= 0), workgroup b
+ * taking rows [b per, (b + 1) per) with per = ceil(rows / blocks), one wave per row: the two-stage sum of amt_layernorm_bwd. */
+#define AMT_RMSNORM_BWD_WS_FLOATS(dim) (4 + 128 * (dim))
+int32_t amt_rmsnorm_bwd_blocks(int32_t rows);
+int32_t amt_rmsnorm_bwd(const float* dy, const float* x, const float* resid, const float* w, float* dx, float* dw, float* ws,
+                        int32_t rows, int32_t dim, float eps, void* stream);
+/* Training of one GLUExpert on n rows (amt_glu_expert_fwd's layer): y = W2((W1 x + b1) * silu(Wg x + bg) * mask_h) + b2, or with
+ * w1 == NULL the Linear -> SiLU -> Dropout -> Linear expert y = W2(silu(Wg x + bg) * mask_h) + b2 (amt_moe_train_fwd's convention).
+ * x, out (n, d); w1 / wg (dff, d), b1 / bg (dff), w2 (d, dff), b2 (d) at the padded width dff (a multiple of 32, as d); mask_h
+ * (n, dff_raw) multipliers or null, dff_raw <= dff the expert's own hidden width.  `saved` (amt_glu_train_scratch_floats(n, dff, glu),
+ * glu = 1 when w1 is given; 16-byte aligned) receives what amt_glu_bwd reads: the gate pre-activation G, the up branch U (GLU only) and
+ * H as fed to the down projection.  With mask_h null, out is the bits of amt_glu_expert_fwd.
+ * amt_glu_bwd: dout (n, d) -> dx (n, d) and dw1 (dff, d; null for a SiLU expert) db1 dwg dbg dw2 (d, dff) db2 at the padded width (the
+ * padding's rows / columns come out zero).  w1t / wgt (d, dff) and w2t (dff, d) are the TRANSPOSED weights, prepared by the caller.
+ * ws: amt_glu_bwd_ws_floats(n, d, dff) floats, 16-byte aligned. */
+int64_t amt_glu_train_scratch_floats(int32_t n, int32_t dff, int32_t glu);
+int32_t amt_glu_train_fwd(const float* x, const float* w1, const float* b1, const float* wg, const float* bg, const float* w2,
+                          const float* b2, const float* mask_h, float* out, float* saved, int32_t n, int32_t d, int32_t dff,
+                          int32_t dff_raw, void* stream);
+int64_t amt_glu_bwd_ws_floats(int32_t n, int32_t d, int32_t dff);
+int32_t amt_glu_bwd(const float* dout, const float* x, const float* saved, const float* w1t, const float* wgt, const float* w2t,
+                    const float* mask_h, float* dx, float* dw1, float* db1, float* dwg, float* dbg, float* dw2, float* db2,
+                    float* ws, int32_t n, int32_t d, int32_t dff, int32_t dff_raw, int32_t glu, void* stream);
 
 /* Training loss of the chord model (reference utilities/run_model_vevo.py:101-119) and its gradient, one launch:
  *   total = lambda CrossEntropyLoss(ignore_index=CHORD_PAD, label_smoothing=smoothing)(y, tgt)

@@ -4,6 +4,8 @@ fused loss, backward, optimiser (not a test; run on the GPU box).
 
     python tools/bench_train.py --which ours            # the project's step alone
     python tools/bench_train.py --which both            # then, alternating with it, the comparison
+    python tools/bench_train.py --music_gen_version 1.2.3 2.2      # the base model's step, then the named V1 / V2 models' in the same
+                                                                   # session (chord_embed, the same shape and optimiser; --rms_norm)
 
 The comparison is the torch restatement of tests/helpers_train.py -- the same network written in torch operators, fp32 autograd on
 the same GPU, torch's two loss expressions, the same AdamW -- from the same state dict, with a mask drawn on the device for every one
@@ -48,6 +50,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--dropout", type=float, default=0.2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--music_gen_version", nargs="*", default=[], help="also time these V1 / V2 versions (train_families.TRAINABLE)")
+    ap.add_argument("--rms_norm", action="store_true", help="build the V1 versions with rms_norm=True")
+    ap.add_argument("--skip_base", action="store_true", help="with --music_gen_version: do not time the base model (kernel traces)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     B, L, S = a.clips, 299, 300
@@ -76,7 +81,31 @@ def main():
         chord_train_loss(y, d["tgt"], d["emo_class"], C.LOSS_LAMBDA, 0.1).backward()
         opt.step()
 
+    def family_step(version):
+        """One training step of the V1 / V2 model `version` (chord_embed, synthetic weights) on the same batch."""
+        from video2music_amd.model import video_music_transformer as M
+        kw = {k: v for k, v in cfg.items() if k != "rpr"}
+        if version[0] == "1":
+            fam = M.VideoMusicTransformer_V1(version_name=version, dropout=a.dropout, chord_embed=True, rms_norm=a.rms_norm, **kw)
+        else:
+            fam = M.VideoMusicTransformer_V2(version_name=version, dropout=a.dropout, chord_embed=True, **kw)
+        shapes = [(k, tuple(v.shape)) for k, v in fam.state_dict().items()]
+        fam.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic.synthetic_state_dict(shapes, seed=0).items()}, strict=False)
+        fam = fam.to(dev).train()
+        fopt = TR.make_optimizer(Args, [p for p in fam.parameters() if p.requires_grad], 1e-4)
+
+        def step():
+            fopt.zero_grad()
+            y = fam(d["x"], d["x_root"], d["x_attr"], d["semantic"], d["key"], d["scene_offset"], d["motion"], d["emotion"])
+            chord_train_loss(y, d["tgt"], d["emo_class"], C.LOSS_LAMBDA, 0.1).backward()
+            fopt.step()
+        return step
+
     res = {"shape": dict(cfg, clips=B, L=L, S=S, dropout=a.dropout), "steps": a.steps, "warmup": a.warmup, "ours_ms": [], "torch_ms": None}
+    families = {v: family_step(v) for v in a.music_gen_version}
+    if families:
+        res["family_ms"] = {v: [] for v in families}
+        res["rms_norm"] = bool(a.rms_norm)
     if a.which == "both":
         P = {k: torch.from_numpy(v).to(dev).requires_grad_(True) for k, v in sd.items()}
         used = [p for k, p in P.items() if k not in T.UNUSED]
@@ -106,10 +135,16 @@ def main():
             topt.step()
         res["torch_ms"] = []
     for _ in range(a.rounds):
-        res["ours_ms"].append(timed(step_ours, a.steps, a.warmup))
+        if not (families and a.skip_base):
+            res["ours_ms"].append(timed(step_ours, a.steps, a.warmup))
+        for v, step in families.items():
+            res["family_ms"][v].append(timed(step, a.steps, a.warmup))
         if a.which == "both":
             res["torch_ms"].append(timed(step_torch, a.steps, a.warmup))
-    res["ours_ms_best"] = min(res["ours_ms"])
+    if res["ours_ms"]:
+        res["ours_ms_best"] = min(res["ours_ms"])
+    if families:
+        res["family_ms_best"] = {v: min(t) for v, t in res["family_ms"].items()}
     if res["torch_ms"]:
         res["torch_ms_best"] = min(res["torch_ms"])
     res["peak_memory_gb"] = torch.cuda.max_memory_allocated() / 2 ** 30

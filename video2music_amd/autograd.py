@@ -10,7 +10,7 @@ module's own parameters.
     MambaBlockFn      one MambaBlock (+ the layer's residual)           amt_linear_ex_fwd, amt_dwconv1d_silu_fwd,
                       amt_selective_scan_train_fwd; backward: amt_selective_scan_bwd, amt_dwconv1d_silu_bwd + GEMMs
     MoEFn             one MoELayer / SharedMoELayer (the mixture heads' FFN)  amt_moe_train_fwd; backward: amt_moe_bwd (grouped GEMMs
-                      for the data gradients, the grouped weight-gradient product of csrc/moe_bwd.hip for the experts' parameters)
+                      for the data gradients, the grouped weight-gradient product of csrc/moe_train_kernels.h for the experts' parameters)
     RegLossFn         SmoothL1 + BCE and both gradients                 amt_reg_loss_fwd_bwd
 
 and the pieces of the chord model's training that do not depend on the model (losses.chord_train_loss):
@@ -20,6 +20,12 @@ and the pieces of the chord model's training that do not depend on the model (lo
     LayerNormFn       LayerNorm(x (+ resid)); gradients of both addends   amt_layernorm_fwd; backward: amt_layernorm_bwd
     ChordLossFn       smoothed cross-entropy + BCE-with-logits            amt_chord_loss_fwd_bwd
     EmbeddingFn       rows of a table; the table's gradient is a one-hot product on the GEMM (deterministic), not index_add_
+
+and what the V1 / V2 chord models add to those (model/vmt_v2.py, `_forward_train`):
+
+    RopeFn            the rotary embedding of a (n0, seq, n2, hd) view          amt_rope_fwd; backward: amt_rope_bwd
+    GluFn             one plain GLUExpert / SiLUExpert with its hidden Dropout    amt_glu_train_fwd; backward: amt_glu_bwd
+    RMSNormFn         RMSNorm(x (+ resid)); gradients of both addends             amt_rmsnorm_resid_fwd; backward: amt_rmsnorm_bwd
 
 Every dense product of the backward runs on `amt_linear_ex_fwd` (y = x w^T, K a multiple of 32): `a b` and `a^T b` go there as
 transposed, zero-padded copies made by torch (`mm_nt`, `mm_tn`).  A bias gradient is the column of ones appended to the right
@@ -258,17 +264,32 @@ def blh_strides(Lq, Lk, H, hd, kv_group=1):
     return (Lq * E, hd, E, Lk * Ek, hd, Ek, Lk * Ek, hd, Ek, Lq * E, hd, E)
 
 
+def lbh_strides(B, H, hd, kv_group=1):
+    """The twelve strides of seq-first (L, B, heads * hd) row-major q / k / v / o: clip stride heads * hd, position stride B * heads * hd."""
+    E, Ek = H * hd, (H // kv_group) * hd
+    return (E, hd, B * E, Ek, hd, B * Ek, Ek, hd, B * Ek, E, hd, B * E)
+
+
 class AttentionFn(torch.autograd.Function):
     """apply(q (B, Lq, H hd), k, v (B, Lk, (H / kv_group) hd), Er (er_len, hd) or None, keep (B, H, Lq, Lk) uint8 or None, H, causal,
-    q_scale, keep_scale, kv_group) -> O (B, Lq, H hd).  Saves q, k, v, O, the rows' log-sum-exp and the keep mask; the backward
-    returns the gradients of q (q_scale included), k, v and Er."""
+    q_scale, keep_scale, kv_group, strides) -> O (B, Lq, H hd).  Saves q, k, v, O, the rows' log-sum-exp and the keep mask; the backward
+    returns the gradients of q (q_scale included), k, v and Er.
+    `strides` (the twelve of amt_attn_fwd; None = `blh_strides`): with `lbh_strides` q, k, v are the seq-first (Lq, B, H hd) /
+    (Lk, B, (H / kv_group) hd) buffers of the V1 / V2 stacks and O, dq, dk, dv come out seq-first too, without a transposed copy."""
 
     @staticmethod
-    def forward(ctx, q, k, v, Er, keep, H, causal, q_scale, keep_scale=1.0, kv_group=1):
+    def forward(ctx, q, k, v, Er, keep, H, causal, q_scale, keep_scale=1.0, kv_group=1, strides=None):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        B, Lq, E = q.shape
-        Lk, hd = k.shape[1], E // H
-        strides = blh_strides(Lq, Lk, H, hd, kv_group)
+        if strides is None:
+            B, Lq, E = q.shape
+            Lk = k.shape[1]
+            strides = blh_strides(Lq, Lk, H, E // H, kv_group)
+        else:
+            strides = tuple(int(st) for st in strides)
+            Lq, B, E = q.shape
+            Lk = k.shape[0]
+            assert strides == lbh_strides(B, H, E // H, kv_group), "AttentionFn: explicit strides are the seq-first ones (lbh_strides)"
+        hd = E // H
         Er_ = None if Er is None else Er.detach().contiguous()
         o, lse = ops.attention_train(q, k, v, strides, B, H, Lq, Lk, hd, causal, q_scale, torch.empty_like(q), kv_group=kv_group,
                                      Er=Er_, keep=keep, keep_scale=keep_scale)
@@ -283,7 +304,7 @@ class AttentionFn(torch.autograd.Function):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         dEr = ops.attention_bwd(dO.contiguous(), q, k, v, o, lse, strides, B, H, Lq, Lk, hd, causal, q_scale, dq, dk, dv, kv_group=kv_group,
                                 Er=Er, keep=keep, keep_scale=keep_scale, need_dEr=Er is not None and ctx.needs_input_grad[3])
-        return dq, dk, dv, dEr, None, None, None, None, None, None
+        return dq, dk, dv, dEr, None, None, None, None, None, None, None
 
 
 class LayerNormFn(torch.autograd.Function):
@@ -304,6 +325,71 @@ class LayerNormFn(torch.autograd.Function):
         x, resid, w = ctx.saved_tensors
         dx, dw, db = ops.layernorm_bwd(dy.contiguous(), x, w.detach(), resid=resid, eps=ctx.eps)
         return (dx if ctx.needs_input_grad[0] else None, dx if resid is not None and ctx.needs_input_grad[1] else None, dw, db, None)
+
+
+class RMSNormFn(torch.autograd.Function):
+    """apply(x, resid, w, eps) -> RMSNorm(x (+ resid)) * w over rows x (rows, dim); resid may be None.  The forward's inputs are what is
+    saved; the backward forms the row's scale again and hands the same gradient to both addends."""
+
+    @staticmethod
+    def forward(ctx, x, resid, w, eps=1e-6):
+        x = x.contiguous()
+        resid = None if resid is None else resid.contiguous()
+        y = ops.rmsnorm(x, w.detach(), resid=resid, eps=eps)
+        ctx.eps = eps
+        ctx.save_for_backward(x, resid, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, resid, w = ctx.saved_tensors
+        dx, dw = ops.rmsnorm_bwd(dy.contiguous(), x, w.detach(), resid=resid, eps=ctx.eps)
+        return (dx if ctx.needs_input_grad[0] else None, dx if resid is not None and ctx.needs_input_grad[1] else None, dw, None)
+
+
+class RopeFn(torch.autograd.Function):
+    """apply(x (n0, seq, n2, hd), cache (>= seq, cache_half, 2)) -> the rotary embedding of x on cache rows 0..seq-1 (`ops.rope`); the
+    backward rotates every pair of dy back by the same angle (`ops.rope_bwd`).  The cache gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, cache):
+        ctx.save_for_backward(cache)
+        return ops.rope(x.contiguous(), cache)
+
+    @staticmethod
+    def backward(ctx, dy):
+        cache, = ctx.saved_tensors
+        return ops.rope_bwd(dy.contiguous(), cache), None
+
+
+class GluFn(torch.autograd.Function):
+    """One plain GLUExpert / SiLUExpert on rows x (n, d): amt_glu_train_fwd, backward amt_glu_bwd.
+
+    apply(x, tensors, mask_h, dff_raw, *params): `tensors` = (w1, b1, wg, bg, w2, b2) at the padded hidden width (model.moe.expert_tensors;
+    w1 / b1 None: a SiLU expert), mask_h (n, dff_raw) the hidden Dropout's multipliers or None; `params` the expert's own parameters in
+    the order linear1.weight, linear1.bias, gate.weight, gate.bias, linear2.weight, linear2.bias (a SiLU expert: its first Linear in the
+    gate's place, no linear1); they receive the gradients at their own widths.
+
+    Saved: x and the library's buffer (G, U, H as fed to the down projection: 3 n dff floats, 2 n dff for a SiLU expert).  Recomputed
+    by the backward: silu(G) and its derivative, and the masked hidden's gradient; the transposed weights are made when it runs."""
+
+    @staticmethod
+    def forward(ctx, x, tensors, mask_h, dff_raw, *params):
+        x = x.contiguous()
+        out, saved = ops.glu_train(x, tensors, mask_h, dff_raw)
+        ctx.tensors, ctx.mask_h, ctx.dff_raw = tensors, mask_h, dff_raw
+        ctx.save_for_backward(x, saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, saved = ctx.saved_tensors
+        raw = ctx.dff_raw
+        w1, _, wg, _, w2, _ = ctx.tensors
+        t = lambda w: None if w is None else w.t().contiguous()
+        dx, (dw1, db1, dwg, dbg, dw2, db2) = ops.glu_bwd(dout.contiguous(), x, saved, (t(w1), t(wg), t(w2)), ctx.mask_h, raw)
+        six = [None if dw1 is None else dw1[:raw], None if db1 is None else db1[:raw], dwg[:raw], dbg[:raw], dw2[:, :raw], db2]
+        return (dx if ctx.needs_input_grad[0] else None, None, None, None, *[g.contiguous() for g in six if g is not None])
 
 
 class EmbeddingFn(torch.autograd.Function):

@@ -7,14 +7,15 @@ from .vmt_v2 import VideoMusicTransformer_V2, _TransformerParamsV2
 
 
 class VideoMusicTransformer_V1(VideoMusicTransformer_V2):
-    """Reference ``VideoMusicTransformer_V1`` (model/video_music_transformer.py:22-314), eval mode.  Learned positional
+    """Reference ``VideoMusicTransformer_V1`` (model/video_music_transformer.py:22-314).  Learned positional
     tables on both streams (:63-65,198-206); every layer's feed-forward a 6-expert top-2 mixture -- ``MoELayer`` for
     '1.0', '1.1', '1.3.4', else ``SharedMoELayer`` -- over ``GLUExpert(d, d_ff)`` ('1.1', '1.3') or
     ``Linear(d, 2d) -> SiLU -> Linear(2d, d)`` experts (:77-85); '1.3.3' / '1.3.4' put three plain GLU layers first
     (:108-125); RoPE inside the attentions when ``version_name in '1.2.3'`` -- the reference's substring test (:86), so
     '1.2' gets it too; ``rms_norm=True`` swaps every LayerNorm for RMSNorm (:69-72).  ``nn.MultiheadAttention`` and
     ``CustomMultiheadAttention`` carry the same parameter names and compute the same attention without RoPE, so one
-    code path serves both.  forward / generate / the KV-cached decode step are inherited from the V2 class.
+    code path serves both.  forward / generate / the KV-cached decode step and the training-state forward (``_forward_train``: every
+    version trains; ``rms_norm`` through ``autograd.RMSNormFn``) are inherited from the V2 class.
     """
 
     def __init__(self, version_name="1.1", n_layers=6, num_heads=8, d_model=512, dim_feedforward=1024, dropout=0.1,

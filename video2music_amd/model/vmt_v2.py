@@ -56,7 +56,9 @@ class VideoMusicTransformer_V2(nn.Module):
     three SharedMoELayer(6 experts, top-2) layers in both stacks, post-norm; optionally ``chord_embed=True`` (chord ids
     through a frozen table, the configuration of the Video2music app).  A composition of the library's operator kernels
     (``video2music_amd/ops.py``): ``generate`` runs the video encoder once and the decoder one token at a time over
-    cached keys/values (the reference re-runs both stacks on the whole prefix every step, :547-548).
+    cached keys/values (the reference re-runs both stacks on the whole prefix every step, :547-548).  In training mode with
+    gradients enabled ``forward`` builds an autograd graph on the module's own parameters instead (``_forward_train``; '2.2' trains,
+    '2.0' / '2.1' are refused there with the reason).
     """
 
     def __init__(self, version_name="2.0", n_layers=6, num_heads=8, d_model=512, dim_feedforward=1024, dropout=0.1,
@@ -369,8 +371,176 @@ class VideoMusicTransformer_V2(nn.Module):
         st["logits"].copy_(self._decode_step(r, a, torch.tensor([float(key)], device=dev), int(t), st))
         return st["logits"]
 
+    # ---- training ------------------------------------------------------------------------------------------------------------------
+    def _train_path(self):
+        """The one state in which `forward` builds an autograd graph on the module's own parameters (video2music_amd/autograd.py):
+        training mode with gradients enabled, the rule of `VideoMusicTransformer._train_path`.  Every other state runs the operator
+        composition on detached weights, as before."""
+        return self.training and torch.is_grad_enabled()
+
+    def _train_refusal(self):
+        """Why this model does not train here, or None."""
+        from ..utilities.constants import IS_SEPERATED
+        from .moe import _MoEBase
+        if IS_SEPERATED:
+            return "IS_SEPERATED: training the separate root / attr heads is not built"
+        if self.version_name.startswith("3"):
+            return f"version {self.version_name!r}: the differential attention of the V3 family has no backward"
+        if self.version_name in ("2.0", "2.1"):
+            return (f"version {self.version_name!r}: the reference gives it a TopKScheduler that acts in training, and the mixture layers "
+                    "do not train with one")
+        if any(getattr(m, "balancing", False) for m in self.modules() if isinstance(m, _MoEBase)):
+            return "balancing=True: the routing-bias update of the mixture layers in training is not built"
+        hd = self.d_model // self.nhead
+        if hd not in (32, 64, 128):
+            return f"head_dim {hd}: the attention backward (amt_attn_bwd) is built for head dims 32 / 64 / 128"
+        return None
+
+    def _forward_train(self, x, x_root, x_attr, sem, key, scene, motion, emotion, mask):
+        """`_encode_memory`, `_decode`, `_enc_layer` and `_dec_layer` line for line (post-norm, no residual dropout) on seq-first rows,
+        composed through `autograd`'s Functions, so that `loss.backward()` reaches every parameter that takes part: `embedding` and
+        `condition_linear` do not, nor -- with chord_embed -- `embedding_root` / `embedding_attr`, as in the reference; the frozen chord
+        table is gathered without a gradient.
+
+        RoPE goes through the raw (H, L, B, hd) view of the q and k buffers (`RopeFn`): for B > 1 this ties the clips of a batch together
+        exactly as the reference's training does.
+
+        Dropout multipliers are drawn by torch on the device (`autograd.dropout_mask`; uint8 keep tensors (B, H, Lq, Lk) for the
+        attention probabilities, which the reference drops with dropout_p in training) or taken, in the order of use, from
+        `self.dropout_masks` when that is a list; the ones used are kept in `self.last_dropout_masks`.  The order: the dropTokenRate
+        row mask (B, S) of 0 / 1 first (only when dropTokenRate != 0; drawn, it is the reference's `torch.rand(B, S) > rate` on the
+        default CPU generator); then per encoder layer the attention's keep mask and, for a plain GLU layer, its hidden multipliers
+        (S B, d_ff) by seq-first row; then per decoder layer the self-attention's keep mask, the cross-attention's, and a plain GLU
+        layer's hidden multipliers (L B, d_ff).  Sites with dropout 0 are skipped.  The mixture layers keep their own lists
+        (`MoELayer.dropout_masks`, rows by seq-first token)."""
+        from .. import autograd as AG
+        from .moe import GLUExpert, SiLUExpert, expert_parts, expert_tensors
+        why = self._train_refusal()
+        if why:
+            raise NotImplementedError(why)
+        dev = self.Wout.weight.device
+        if dev.type != "cuda":
+            raise _lib.AmtError("VideoMusicTransformer_V2 runs on an MI355X only; video2music_amd has no CPU fallback")
+        f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+        sem, scene, emotion, motion = f32(sem), f32(scene), f32(emotion), f32(motion)
+        if motion.dim() == 2:
+            motion = motion.unsqueeze(-1).contiguous()
+        B, S, d, H = sem.shape[0], sem.shape[1], self.d_model, self.nhead
+        hd = d // H
+        ids = x if self.chord_embed else x_root                 # the chord ids themselves index the frozen table (:431-432)
+        assert ids.shape[0] == B, f"{ids.shape[0]} chord sequences but {B} clips of video features"
+        L = ids.shape[1]
+        if S > self.max_seq_video and (self._use_rope or self._learned_pos):
+            raise ValueError(f"video longer than the positional table ({self.max_seq_video}), like in the reference")
+        if L > self._max_dec:
+            raise ValueError(f"chord sequence longer than the positional table ({self._max_dec}), like in the reference")
+        p = float(self.dropout)
+        given = list(self.dropout_masks) if getattr(self, "dropout_masks", None) is not None else None
+        used = []
+        keep_scale = 1.0 / (1.0 - p) if p < 1.0 else 0.0
+
+        def take(draw):
+            m = given.pop(0) if given is not None else draw()
+            used.append(m)
+            return m
+
+        def keep(Lq, Lk):
+            if p <= 0.0:
+                return None
+            return take(lambda: (torch.rand(B, H, Lq, Lk, device=dev) >= p).to(torch.uint8)).to(device=dev, dtype=torch.uint8).contiguous()
+
+        def padded_w(w):
+            Kp = (w.shape[1] + 31) // 32 * 32
+            return None if Kp == w.shape[1] else torch.nn.functional.pad(w.detach(), (0, Kp - w.shape[1])).contiguous()
+
+        def seq_first(t, n):                                    # (B, n, ...) -> rows (n B, ...)
+            return t.transpose(0, 1).reshape(n * B, *t.shape[2:]).contiguous()
+
+        def attn(a, x_q, x_kv, Lq, Lk, causal):
+            w, b_ = a.in_proj_weight, a.in_proj_bias
+            if x_kv is None:                                    # self-attention: one packed product
+                qkv = AG.LinearFn.apply(x_q, w, b_)
+                q, k, v = (qkv[:, i * d:(i + 1) * d].contiguous() for i in range(3))
+            else:
+                q = AG.LinearFn.apply(x_q, w[:d], b_[:d])
+                kv = AG.LinearFn.apply(x_kv, w[d:], b_[d:])
+                k, v = (kv[:, i * d:(i + 1) * d].contiguous() for i in range(2))
+            if self._rope_cache is not None:                    # raw (H, L, B, hd) view of the (L, B, E) buffers (:1041-1053)
+                q = AG.RopeFn.apply(q.view(H, Lq, B, hd), self._rope_cache).view(Lq * B, d)
+                k = AG.RopeFn.apply(k.view(H, Lk, B, hd), self._rope_cache).view(Lk * B, d)
+            o = AG.AttentionFn.apply(q.view(Lq, B, d), k.view(Lk, B, d), v.view(Lk, B, d), None, keep(Lq, Lk), H, causal, hd ** -0.5,
+                                     keep_scale, 1, AG.lbh_strides(B, H, hd))
+            return AG.LinearFn.apply(o.view(Lq * B, d), a.out_proj.weight, a.out_proj.bias)
+
+        def ffn(ff, t, n):
+            if not isinstance(ff, (GLUExpert, SiLUExpert)):
+                return ff(t.view(n, B, d)).reshape(n * B, d)    # the mixture's own training forward (`_MoEBase._run_train`)
+            parts = expert_parts(ff)
+            raw = parts["gate"].out_features
+            p_in = float(ff[2].p if isinstance(ff, SiLUExpert) else ff.dropout.p)
+            m = None
+            if p_in > 0.0:
+                m = take(lambda: AG.dropout_mask((n * B, raw), p_in, dev)).to(device=dev, dtype=torch.float32).reshape(n * B, raw).contiguous()
+            params = [q for name in ("linear1", "gate", "linear2") if parts[name] is not None for q in (parts[name].weight, parts[name].bias)]
+            return AG.GluFn.apply(t, expert_tensors(ff), m, raw, *params)
+
+        def norm(n, t, resid=None):
+            if isinstance(n, nn.LayerNorm):
+                return AG.LayerNormFn.apply(t, resid, n.weight, n.bias, n.eps)
+            return AG.RMSNormFn.apply(t, resid, n.weight, n.eps)
+
+        # video rows (:455-492): Linear_vis over [semantic | scene | motion | emotion] (no scene column with scene_embed), + the scene
+        # embedding, x the row mask, + the learned positions
+        cols = [sem] + ([] if self.scene_embed else [scene.unsqueeze(-1)]) + [motion, emotion]
+        F_in = sum(c.shape[2] for c in cols)
+        assert F_in == self.total_vf_dim, f"{F_in} feature columns, Linear_vis takes {self.total_vf_dim}"
+        Fp = (F_in + 31) // 32 * 32
+        vfc = seq_first(torch.cat(cols + [torch.zeros(B, S, Fp - F_in, device=dev)], dim=2), S)
+        vf = AG.LinearFn.apply(vfc, self.Linear_vis.weight, self.Linear_vis.bias, 0, padded_w(self.Linear_vis.weight))
+        if self.scene_embed:
+            vf = vf + AG.EmbeddingFn.apply(self.scene_embedding.weight, seq_first(scene.to(torch.int32).long(), S))
+        if self.dropTokenRate != 0.0:
+            rows = take(lambda: (torch.rand(B, S) > self.dropTokenRate).float())
+            vf = vf * seq_first(rows.to(device=dev, dtype=torch.float32).reshape(B, S), S).unsqueeze(1)
+        if self._learned_pos:
+            pos = torch.arange(S, device=dev).repeat_interleave(B)
+            vf = vf + AG.EmbeddingFn.apply(self.positional_embedding_video.weight, pos)
+        # chord rows (:437-452): Linear_chord over [embedding | key], + the learned positions
+        ids = seq_first(ids.to(device=dev, dtype=torch.long), L)
+        if self.chord_embed:
+            e = self.chord_embedding_model.weight.detach().index_select(0, ids)
+        else:
+            e = AG.EmbeddingFn.apply(self.embedding_root.weight, ids) + \
+                AG.EmbeddingFn.apply(self.embedding_attr.weight, seq_first(x_attr.to(device=dev, dtype=torch.long), L))
+        kk = key.to(device=dev, dtype=torch.float32).reshape(-1)
+        kk = kk.expand(B) if kk.numel() == 1 else kk
+        Kc = (d + 1 + 31) // 32 * 32
+        xin = torch.cat([e, kk.view(1, B).expand(L, B).reshape(L * B, 1), torch.zeros(L * B, Kc - d - 1, device=dev)], dim=1)
+        t = AG.LinearFn.apply(xin, self.Linear_chord.weight, self.Linear_chord.bias, 0, padded_w(self.Linear_chord.weight))
+        if self._learned_pos:
+            t = t + AG.EmbeddingFn.apply(self.positional_embedding.weight, torch.arange(L, device=dev).repeat_interleave(B))
+
+        tr = self.transformer
+        mem = vf
+        for lyr in tr.encoder.layers:
+            mem = norm(lyr.norm1, attn(lyr.self_attn, mem, None, S, S, False), mem)
+            mem = norm(lyr.norm2, ffn(lyr.ff, mem, S), mem)
+        mem = norm(tr.encoder.norm, mem)
+        for lyr in tr.decoder.layers:
+            t = norm(lyr.norm1, attn(lyr.self_attn, t, None, L, L, mask is True), t)
+            t = norm(lyr.norm2, attn(lyr.cross_attn, t, mem, L, S, False), t)
+            t = norm(lyr.norm3, ffn(lyr.ff, t, L), t)
+        t = norm(tr.decoder.norm, t)
+        logits = AG.LinearFn.apply(t, self.Wout.weight, self.Wout.bias)
+        assert given is None or not given, f"{len(given)} dropout masks were not used"
+        self.__dict__["last_dropout_masks"] = used
+        return logits.view(L, B, CHORD_SIZE).transpose(0, 1).contiguous()
+
     def forward(self, x, x_root, x_attr, feature_semantic_list, feature_key, feature_scene_offset, feature_motion,
                 feature_emotion, mask=True):
+        if self._train_path():
+            return self._forward_train(x, x_root, x_attr, feature_semantic_list, feature_key, feature_scene_offset, feature_motion,
+                                       feature_emotion, mask)
         memory, B, S = self._encode_memory(feature_semantic_list, feature_scene_offset, feature_motion, feature_emotion)
         assert x_root.shape[0] == B, f"{x_root.shape[0]} chord sequences but {B} clips of video features"
         if self.chord_embed:                     # the chord ids themselves index the frozen table (:431-432)

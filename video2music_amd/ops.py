@@ -440,3 +440,71 @@ def moe_wgrad_splits(n_tok, d, dff, n_exp, k, dense=False):
     if S < 1:
         raise _lib.AmtError(f"amt_moe_wgrad_splits: amt_moe_bwd refuses n_tok={n_tok} d={d} dff={dff} n_exp={n_exp} k={k}")
     return S
+
+
+def rope_bwd(dy, cache, pos=0, out=None):
+    """amt_rope_bwd: the adjoint of `rope(x, cache, pos)` on dy (n0, seq, n2, hd) contiguous; `out` may be dy itself."""
+    n0, seq, n2, hd = dy.shape
+    assert dy.dtype == torch.float32
+    dx = torch.empty_like(dy) if out is None else out
+    c = cache[pos:pos + seq].contiguous()
+    _lib.call("amt_rope_bwd", p(dy), p(c), p(dx), n0, seq, n2, hd, cache.shape[1], _st())
+    return dx
+
+
+def rmsnorm_bwd_blocks(rows):
+    """The workgroups `rmsnorm_bwd` launches for this many rows (amt_rmsnorm_bwd_blocks; needs no GPU): workgroup b takes the rows
+    [b per, (b + 1) per), per = ceil(rows / blocks), and the gain's gradient is the sum of the workgroups' slabs in that order."""
+    n = _lib.call("amt_rmsnorm_bwd_blocks", rows)
+    if n < 1:
+        raise _lib.AmtError(f"amt_rmsnorm_bwd_blocks: amt_rmsnorm_bwd refuses rows={rows}")
+    return n
+
+
+def rmsnorm_bwd(dy, x, w, resid=None, eps=1e-6):
+    """amt_rmsnorm_bwd: the backward of `rmsnorm(x, w, resid, eps)` from dy and the forward's own inputs.  Returns dx (the gradient of
+    x and of resid alike) and dw."""
+    rows, dim = x.shape
+    assert dy.shape == x.shape and (resid is None or resid.shape == x.shape) and w.shape == (dim,)
+    for t in (dy, x, w) + (() if resid is None else (resid,)):
+        assert t.dtype == torch.float32
+    dx, dw = torch.empty_like(x), torch.empty_like(w)
+    ws = torch.empty(4 + 128 * dim, device=x.device, dtype=torch.float32)       # AMT_RMSNORM_BWD_WS_FLOATS(dim); a call's own scratch
+    _lib.call("amt_rmsnorm_bwd", p(dy), p(x), p(resid), p(w), p(dx), p(dw), p(ws), rows, dim, float(eps), _st())
+    return dx, dw
+
+
+def glu_train(x, tensors, mask_h, dff_raw):
+    """amt_glu_train_fwd on x (n, d): `tensors` = (w1, b1, wg, bg, w2, b2) at the padded hidden width (w1 / b1 None: a SiLU expert),
+    mask_h (n, dff_raw) multipliers or None.  Returns out (n, d) and `saved`, the buffer `glu_bwd` reads."""
+    n, d = x.shape
+    dff = tensors[2].shape[0]
+    assert mask_h is None or mask_h.shape == (n, dff_raw)
+    for t in (x, *tensors, mask_h):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    glu = int(tensors[0] is not None)
+    out = torch.empty(n, d, device=x.device, dtype=torch.float32)
+    saved = torch.empty(_lib.call("amt_glu_train_scratch_floats", n, dff, glu), device=x.device, dtype=torch.float32)
+    _lib.call("amt_glu_train_fwd", p(x), *[p(t) for t in tensors], p(mask_h), p(out), p(saved), n, d, dff, dff_raw, _st())
+    return out, saved
+
+
+def glu_bwd(dout, x, saved, tensors_t, mask_h, dff_raw):
+    """amt_glu_bwd: the backward of `glu_train` from dout (n, d) and its `saved`.  `tensors_t` = (w1t, wgt, w2t), the weights transposed
+    ((d, dff), (d, dff), (dff, d); w1t None: a SiLU expert).  Returns dx and (dw1, db1, dwg, dbg, dw2, db2) at the padded width (None
+    where the expert has no such tensor)."""
+    n, d = x.shape
+    w1t, wgt, w2t = tensors_t
+    dff = w2t.shape[0]
+    glu = int(w1t is not None)
+    for t in (dout, x, saved, *tensors_t, mask_h):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    assert dout.shape == x.shape and wgt.shape == (d, dff) and w2t.shape == (dff, d)
+    new = lambda *shape: torch.empty(*shape, device=x.device, dtype=torch.float32)
+    dx = new(n, d)
+    dw1, db1 = (new(dff, d), new(dff)) if glu else (None, None)
+    dwg, dbg, dw2, db2 = new(dff, d), new(dff), new(d, dff), new(d)
+    ws = new(_lib.call("amt_glu_bwd_ws_floats", n, d, dff))                              # a call's own scratch (stream-ordered reuse)
+    _lib.call("amt_glu_bwd", p(dout), p(x), p(saved), p(w1t), p(wgt), p(w2t), p(mask_h), p(dx), p(dw1), p(db1), p(dwg), p(dbg), p(dw2),
+              p(db2), p(ws), n, d, dff, dff_raw, glu, _st())
+    return dx, (dw1, db1, dwg, dbg, dw2, db2)

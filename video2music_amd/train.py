@@ -1,5 +1,6 @@
 """``train.py`` entry point (reference ``train.py:46-380``, ``utilities/run_model_vevo.py:20-196``): trains the base
-``VideoMusicTransformer`` (``-music_gen_version None -chord_embed ""``, ``rpr`` on or off) on the GPU.
+``VideoMusicTransformer`` (``-music_gen_version None -chord_embed ""``, ``rpr`` on or off) on the GPU; ``train_families`` trains the
+V1 / V2 chord models through the same code.
 
 A step is the model's training-state forward (``VideoMusicTransformer._forward_train``: the library's GEMMs, attention and
 LayerNorm kernels through ``video2music_amd/autograd.py``), the fused loss (``losses.chord_train_loss``), ``backward()`` and a torch
@@ -14,6 +15,10 @@ Refused, with the reason: ``-music_gen_version`` 1.x / 2.x / 3.x, ``-is_video Fa
 ``-auxiliary_loss``, ``-drop_loss``, ``-augmentation``, tensorboard, ``--force_cpu``, optimisers other than Adam / AdamW, one of
 ``-continue_weights`` / ``-continue_epoch`` without the other.  The parser keeps the reference's defaults (``music_gen_version
 '1.2.3'``, ``chord_embed True``), so the bare command refuses and names the two flags that select the base model.
+
+``main(argv, families=...)`` / ``refuse(args, families=...)`` admit the listed V1 / V2 versions as well (``train_families`` is that
+entry point): the class the reference's ``train.py:136-168`` builds, trained through ``VideoMusicTransformer_V2._forward_train`` with
+the same loop, files and schedule.  With the default empty ``families`` every answer is the one above.
 
     python -m video2music_amd.train -dataset_dir ./dataset/ -music_gen_version None -chord_embed "" -motion_type 1
 """
@@ -74,18 +79,46 @@ def parse_args(argv=None):
     return args
 
 
-def refuse(args):
-    """The reason this build does not run `args`, or None."""
+def refuse_family(args, families):
+    """`refuse` for a -music_gen_version other than None when the entry point admits `families`."""
+    v = args.music_gen_version
+    if v not in families:
+        why = {"2.0": "the reference gives it a TopKScheduler that acts in training, and the mixture layers do not train with one",
+               "2.1": "the reference gives it a TopKScheduler that acts in training, and the mixture layers do not train with one",
+               "2.3": "it swaps the experts for efficient_kan.KANLinear, a package the reference does not vendor"}.get(
+                   v, "the differential attention of the V3 family has no backward" if v.startswith("3.") else "the reference builds no such model")
+        return f"-music_gen_version {v}: {why}; the versions that train are {', '.join(families)}"
+    if args.balancing:
+        return "-balancing: the routing-bias update of the mixture layers in training is not built"
+    if args.chord_embed and not (args.chord_embed_table or args.synthetic_weights or args.continue_weights):
+        return ("-chord_embed: the frozen chord table needs a source -- --chord_embed_table PATH (.npy, (n_chords, d_model) float32), "
+                "--synthetic_weights, or -continue_weights (the reference reads a gensim Word2Vec file, which is not available here)")
+    if args.chord_embed_table and not args.chord_embed:
+        return "--chord_embed_table without -chord_embed: the model would not read the table"
+    hd = args.d_model // max(1, args.num_heads)
+    if hd not in (32, 64, 128) or hd * args.num_heads != args.d_model:
+        return f"-d_model {args.d_model} -num_heads {args.num_heads}: the attention backward is built for head dims 32 / 64 / 128"
+    return None
+
+
+def refuse(args, families=()):
+    """The reason this build does not run `args`, or None.  families: the -music_gen_version strings the caller trains beside the base
+    model (`train_families.TRAINABLE`); empty, the answers are the base entry point's."""
+    family = bool(families) and args.music_gen_version is not None
     if args.force_cpu:
         return "--force_cpu: video2music_amd has no CPU path (the CPU oracle lives in oracle/ for tests only)"
     if not args.is_video:
         return "-is_video False (MusicTransformer) is not built"
-    if args.music_gen_version is not None:
+    if family:
+        why = refuse_family(args, families)
+        if why:
+            return why
+    if args.music_gen_version is not None and not family:
         return (f"-music_gen_version {args.music_gen_version}: training is built for the base model only (the V1 / V2 / V3 families run "
                 f"inference here); select it with {BASE_FLAGS}")
-    if args.chord_embed:
+    if args.chord_embed and not family:
         return f"-chord_embed: training with the frozen chord table is not built; select the base model with {BASE_FLAGS}"
-    if args.scene_embed:
+    if args.scene_embed and not family:
         return "-scene_embed: training with the scene-offset embedding is not built"
     if IS_SEPERATED:
         return "IS_SEPERATED: training the separate root / attr heads is not built"
@@ -119,9 +152,12 @@ def load(args, names, device):
     return {k: torch.from_numpy(v).to(device) for k, v in f.items()}
 
 
-def forward(model, f, Tc):
-    return model(f["chord"][:, :Tc - 1].contiguous(), f["chord_root"][:, :Tc - 1].contiguous(), f["chord_attr"][:, :Tc - 1].contiguous(),
-                 f["semantic"], f["key"], f["scene_offset"], f["motion"], f["emotion"])
+def forward(model, f, Tc, clips=False):
+    """The model on the batch `f`.  clips: every clip as a batch of one, as the reference's evaluation loaders feed them (the V1 / V2
+    classes' `forward_clips`: in a batch their raw rotary view ties the clips together; the base model's clips are independent)."""
+    fn = getattr(model, "forward_clips", model) if clips else model
+    return fn(f["chord"][:, :Tc - 1].contiguous(), f["chord_root"][:, :Tc - 1].contiguous(), f["chord_attr"][:, :Tc - 1].contiguous(),
+              f["semantic"], f["key"], f["scene_offset"], f["motion"], f["emotion"])
 
 
 def evaluate(model, data, batch_size, Tc, smoothing):
@@ -132,7 +168,7 @@ def evaluate(model, data, batch_size, Tc, smoothing):
     with torch.set_grad_enabled(False):
         for b0 in range(0, data["semantic"].shape[0], batch_size):
             f = {k: v[b0:b0 + batch_size] for k, v in data.items()}
-            y = forward(model, f, Tc)
+            y = forward(model, f, Tc, clips=True)
             m = metrics.chord_metrics(y, f["tgt"], f["emo_class"], f["emo_prob"])
             _, clip, _ = ops.chord_loss(y, f["tgt"].contiguous(), f["emo_class"].to(torch.int32).contiguous(), LOSS_LAMBDA, smoothing, backward=False)
             rows.append(torch.stack([m[k] for k in metrics.FIELDS], dim=1).cpu())
@@ -172,9 +208,35 @@ def train_epoch(cur_epoch, model, data, order, batch_size, Tc, smoothing, opt, l
             print("")
 
 
-def main(argv=None):
+def chord_table(args, d_model):
+    """The frozen chord table of -chord_embed as a (n_chords, d_model) float32 tensor, or None when it arrives with the weights."""
+    if args.chord_embed_table:
+        t = np.load(args.chord_embed_table)
+        if t.ndim != 2 or t.shape[1] != d_model or t.dtype != np.float32:
+            raise SystemExit(f"--chord_embed_table {args.chord_embed_table}: need a float32 array of shape (n_chords, {d_model}), got "
+                             f"{t.dtype} {t.shape}")
+        return torch.from_numpy(t)
+    return None
+
+
+def build_model(args, total_vf_dim):
+    """The class the reference's train.py:136-168 builds for args.music_gen_version."""
+    kw = dict(n_layers=args.n_layers, num_heads=args.num_heads, d_model=args.d_model, dim_feedforward=args.dim_feedforward, dropout=args.dropout,
+              max_sequence_midi=args.max_sequence_midi, max_sequence_video=args.max_sequence_video, max_sequence_chord=args.max_sequence_chord)
+    v = args.music_gen_version
+    if v is None:
+        return VideoMusicTransformer(total_vf_dim=total_vf_dim, rpr=bool(args.rpr), scene_embed=False, chord_embed=False, **kw)
+    from .model.video_music_transformer import VideoMusicTransformer_V1, VideoMusicTransformer_V2
+    fam = dict(version_name=v, total_vf_dim=total_vf_dim - int(bool(args.scene_embed)), rms_norm=bool(args.rms_norm),
+               scene_embed=bool(args.scene_embed), chord_embed=bool(args.chord_embed), dropTokenRate=args.droptoken, **kw)
+    if v.startswith("1."):
+        return VideoMusicTransformer_V1(**fam)
+    return VideoMusicTransformer_V2(balancing=bool(args.balancing), **fam)
+
+
+def main(argv=None, families=()):
     args = parse_args(argv)
-    why = refuse(args)
+    why = refuse(args, families)
     if why:
         raise SystemExit(why)
     device = get_device()
@@ -193,14 +255,14 @@ def main(argv=None):
     smoothing = float(args.ce_smoothing or 0.0)
     from .generate import total_vf_dim_of
     torch.manual_seed(args.seed)
-    model = VideoMusicTransformer(n_layers=args.n_layers, num_heads=args.num_heads, d_model=args.d_model, dim_feedforward=args.dim_feedforward,
-                                  dropout=args.dropout, max_sequence_midi=args.max_sequence_midi, max_sequence_video=args.max_sequence_video,
-                                  max_sequence_chord=args.max_sequence_chord, total_vf_dim=total_vf_dim_of(args, sem_dim=train["semantic"].shape[-1]),
-                                  rpr=bool(args.rpr), scene_embed=False, chord_embed=False)
+    model = build_model(args, total_vf_dim_of(args, sem_dim=train["semantic"].shape[-1]))
     if args.synthetic_weights:
         from . import synthetic
         shapes = [(k, tuple(v.shape)) for k, v in model.state_dict().items()]
         model.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic.synthetic_state_dict(shapes, seed=0).items()}, strict=False)
+    table = chord_table(args, args.d_model) if args.music_gen_version is not None else None
+    if table is not None:                                       # the pre-hook of the model resizes the frozen table to the file's rows
+        model.load_state_dict({"chord_embedding_model.weight": table}, strict=False)
     with open(paths["architecture"], "w") as fh:
         fh.write(str(model))
     start_epoch = BASELINE_EPOCH

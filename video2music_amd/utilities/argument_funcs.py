@@ -22,7 +22,7 @@ auxiliary_loss = False
 drop_loss = False
 balancing = False
 
-ADDED = ("seed", "train_ids", "val_ids", "synthetic_weights")      # flags the reference does not have
+ADDED = ("seed", "train_ids", "val_ids", "synthetic_weights", "chord_embed_table")      # flags the reference does not have
 
 
 def parse_train_args(argv=None):
@@ -71,4 +71,6 @@ def parse_train_args(argv=None):
                         help="clip ids to read from -dataset_dir, comma separated, or split:<name> for vevo_meta/split/v1/<name>.txt")
     parser.add_argument("--val_ids", type=str, default="split:val", help="as --train_ids, for the validation figures")
     parser.add_argument("--synthetic_weights", action="store_true", help="start from the procedural weights instead of torch's initialisation")
+    parser.add_argument("--chord_embed_table", type=str, default=None,
+                        help="the frozen chord table of -chord_embed: a .npy of shape (n_chords, d_model), float32 (train_families)")
     return parser.parse_known_args(argv)
