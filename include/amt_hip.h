@@ -651,15 +651,16 @@ int32_t amt_attn_bwd(const float* dO, const float* q, const float* k, const floa
  *   dw = sum over rows of dy xh,   db = sum over rows of dy
  * dim a multiple of 4, at most 1024; any rows > 0.  ws: AMT_LAYERNORM_BWD_WS_FLOATS(dim) floats of scratch, 16-byte aligned, used by
  * this call alone until it has finished (a ticket counter, zeroed by the call, and one [dw | db] slab per workgroup).
- * min(128, ceil(rows / 16)) workgroups of 4 waves, one wave per row; a workgroup adds its rows per wave in row order, its waves in
- * wave order, and the last workgroup to finish adds the slabs in workgroup order: the order of every addition is a function of
- * (rows, dim) alone and no floating-point atomic is used, so the same inputs give the same bits. */
+ * amt_rmsnorm_bwd_blocks(rows) workgroups of 4 waves (below: one rule, one kernel for both norms; csrc/norm_bwd.hip), one wave per
+ * row; a workgroup adds its rows per wave in row order, its waves in wave order, and the last workgroup to finish adds the slabs in
+ * workgroup order: the order of every addition is a function of (rows, dim) alone and no floating-point atomic is used, so the same
+ * inputs give the same bits. */
 #define AMT_LAYERNORM_BWD_WS_FLOATS(dim) (4 + 256 * (dim))
 int32_t amt_layernorm_bwd(const float* dy, const float* x, const float* resid, const float* w, float* dx, float* dw, float* db,
                           float* ws, int32_t rows, int32_t dim, float eps, void* stream);
 
-/* What the training of the V1 / V2 chord models adds to the above (csrc/family_train.hip).  All three are fp32 and stateless, use no
- * floating-point atomic and fix the order of every addition by the shapes alone: the same inputs give the same bits.
+/* What the training of the V1 / V2 chord models adds to the above (csrc/family_train.hip; amt_rmsnorm_bwd: csrc/norm_bwd.hip).  All
+ * three are fp32 and stateless, use no floating-point atomic and fix the order of every addition by the shapes alone: the same inputs give the same bits.
  *
  * amt_rope_bwd: the adjoint of amt_rope_fwd under the same index rule and the same shape checks (both cache layouts: the broadcast
  * slab 2 cache_half == hd, and the [seq][cache_half][2] cache read as [n0][seq][hd/2][2]); each pair of dy is rotated by the transpose
@@ -671,8 +672,9 @@ int32_t amt_rope_bwd(const float* dy, const float* cache, float* dx, int32_t n0,
  *   dx = r (g - xh mean(g xh))      (the gradient of x and of resid alike),   dw = sum over rows of dy xh
  * dim a multiple of 4, at most 1024; any rows > 0.  ws: AMT_RMSNORM_BWD_WS_FLOATS(dim) floats of scratch, 16-byte aligned, used by this
  * call alone until it has finished (a ticket counter, zeroed by the call, and one dw slab per workgroup).  amt_rmsnorm_bwd_blocks(rows)
- * workgroups of 4 waves (the launcher's own rule, evaluated on the host: a count, not a status; negative for rows <= 0), workgroup b
- * taking rows [b per, (b + 1) per) with per = ceil(rows / blocks), one wave per row: the two-stage sum of amt_layernorm_bwd. */
+ * workgroups of 4 waves (the launcher's own rule, min(128, ceil(rows / 16)), evaluated on the host: a count, not a status; negative for
+ * rows <= 0), workgroup b taking rows [b per, (b + 1) per) with per = ceil(rows / blocks), one wave per row: amt_layernorm_bwd's kernel
+ * without the mean and db, and its two-stage sum. */
 #define AMT_RMSNORM_BWD_WS_FLOATS(dim) (4 + 128 * (dim))
 int32_t amt_rmsnorm_bwd_blocks(int32_t rows);
 int32_t amt_rmsnorm_bwd(const float* dy, const float* x, const float* resid, const float* w, float* dx, float* dw, float* ws,

@@ -71,6 +71,15 @@ def rope_restated(x, dy, cache, dtype, conjugate=True):
     return y.detach().numpy(), xt.grad.numpy()
 
 
+def norm_bwd_plan_boundaries(limit=4096):
+    """Row counts one below / at every change of the plan kind of the norm backward launchers (csrc/norm_bwd.hip, LayerNorm and RMSNorm
+    alike): from one workgroup to several, and from 16 rows per workgroup to the even spread over all of them.  Asked from the launcher's
+    own rule."""
+    from video2music_amd import ops
+    kind = lambda r: (ops.norm_bwd_blocks(r) > 1, -(-r // ops.norm_bwd_blocks(r)) > 16)
+    return [r for edge in range(2, limit) if kind(edge) != kind(edge - 1) for r in (edge - 1, edge)]
+
+
 RMS_EPS = 1e-6
 RMS_GAIN = 0.1                      # gains and rows of this scale: mean squares of 1e-2, where eps 1e-6 vs 1e-5 shows
 

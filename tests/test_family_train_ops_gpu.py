@@ -1,4 +1,4 @@
-"""The operators the V1 / V2 chord models train through (csrc/family_train.hip) against the fp64 oracle: `autograd.RopeFn`, `RMSNormFn`,
+"""The operators the V1 / V2 chord models train through (csrc/family_train.hip, csrc/norm_bwd.hip) against the fp64 oracle: `autograd.RopeFn`, `RMSNormFn`,
 `GluFn`, and `AttentionFn` with seq-first strides.  Bound per tensor: 8 x e32 (tests/helpers_family_train.py), e32 the same restatement in
 float32 on the CPU."""
 import numpy as np
@@ -59,15 +59,8 @@ def test_rope_bwd_refuses_what_the_forward_refuses():
 
 
 # ---- RMSNormFn ----
-def plan_boundaries(limit=4096):
-    """Row counts one below / at every change of the launcher's plan kind: from one workgroup to several, and from 16 rows per workgroup
-    to the even spread over all of them.  Asked from the launcher's own rule."""
-    kind = lambda r: (ops.rmsnorm_bwd_blocks(r) > 1, -(-r // ops.rmsnorm_bwd_blocks(r)) > 16)
-    return [r for edge in range(2, limit) if kind(edge) != kind(edge - 1) for r in (edge - 1, edge)]
-
-
 def test_plan_rule_has_the_boundaries_the_cases_use():
-    assert plan_boundaries() == [16, 17, 2048, 2049]
+    assert FT.norm_bwd_plan_boundaries() == [16, 17, 2048, 2049]
     assert ops.rmsnorm_bwd_blocks(1) == 1 and ops.rmsnorm_bwd_blocks(2049) == 128
 
 
@@ -87,7 +80,7 @@ RMS_ROWS = sorted({1, 17, 16, 2048, 2049})
 @pytest.mark.parametrize("dim", [4, 100, 1024])
 @pytest.mark.parametrize("rows", RMS_ROWS)
 def test_rmsnorm_backward(rows, dim, resid):
-    assert set(plan_boundaries()) <= set(RMS_ROWS)
+    assert set(FT.norm_bwd_plan_boundaries()) <= set(RMS_ROWS)
     a = FT.rms_inputs(rows, dim, resid)
     r64, r32 = FT.rms_restated(a, torch.float64), FT.one_thread(FT.rms_restated, a, torch.float32)
     got, again = rms_device(a), rms_device(a)

@@ -1,4 +1,4 @@
-"""amt_layernorm_bwd (csrc/layernorm_bwd.hip) through `autograd.LayerNormFn` against torch's CPU autograd in fp64 on
+"""amt_layernorm_bwd (csrc/norm_bwd.hip, norm_bwd_kernel<false>) through `autograd.LayerNormFn` against torch's CPU autograd in fp64 on
 F.layer_norm(x (+ resid), w, b): the gradients of x, resid, w and b.
 
 Bound per tensor, the one tests/test_rnn_train_gpu.py established: err = max|g - g64| / max|g64| <= max(8 err_torch32, n 2^-24), with
@@ -6,12 +6,16 @@ err_torch32 torch's own fp32 CPU autograd on the same inputs and n the longest s
 and the two means of dx), `rows` terms of a column of dw / db -- n = max(rows, dim).
 
 Every third row of x (and resid) is scaled by SMALL = 3e-3, so that its variance is near eps: on rows of unit variance no epsilon shows
-(test_a_wrong_epsilon_shows_on_the_small_variance_rows_only)."""
+(test_a_wrong_epsilon_shows_on_the_small_variance_rows_only).
+
+EDGE_CASES: the row counts at which the launcher's plan changes (one workgroup to several, 16 rows per workgroup to the even spread), asked
+from its own rule, at dim 4 (one lane of a wave has a column) and dim 260 (one lane in the second float4 chunk)."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.helpers_family_train import norm_bwd_plan_boundaries
 from tests.helpers_reg_train import U, rel_err
 from video2music_amd import _lib, ops
 from video2music_amd.autograd import LayerNormFn
@@ -21,6 +25,8 @@ DEV = "cuda:0"
 EPS = 1e-5
 SMALL = 3e-3                            # rows 1, 4, 7, ... of x and resid: variance about 1e-5, the epsilon itself
 CASES = [(rows, dim, resid) for rows in (1, 37, 600) for dim in (32, 100, 512, 1024) for resid in (False, True)]
+EDGE_ROWS = (16, 17, 2048, 2049)
+EDGE_CASES = [(rows, dim, resid) for rows in EDGE_ROWS for dim in (4, 260) for resid in (False, True)]
 
 
 def inputs(rows, dim, resid):
@@ -54,7 +60,11 @@ def device(a):
     return out
 
 
-@pytest.mark.parametrize("rows,dim,resid", CASES)
+def test_edge_rows_are_the_plan_rules_boundaries():
+    assert norm_bwd_plan_boundaries() == list(EDGE_ROWS)
+
+
+@pytest.mark.parametrize("rows,dim,resid", CASES + EDGE_CASES)
 def test_gradients_against_fp64(rows, dim, resid):
     a = inputs(rows, dim, resid)
     g64, g32, got = torch_cpu(a, torch.float64), torch_cpu(a, torch.float32), device(a)
@@ -84,12 +94,17 @@ def test_a_wrong_epsilon_shows_on_the_small_variance_rows_only(rows, dim, resid)
 
 
 def test_more_rows_than_the_workgroup_cap_spreads():
-    """rows = 2049 > 128 workgroups x 16 rows: the rows are spread evenly (17 per workgroup) and the last workgroups get none."""
-    a = inputs(2049, 64, True)
+    """The first row count past the rule's cap of workgroups times 16 rows: the rows are spread evenly (17 per workgroup) and the last
+    workgroups get none."""
+    rows = norm_bwd_plan_boundaries()[-1]
+    blocks = ops.norm_bwd_blocks(rows)
+    per = -(-rows // blocks)
+    assert blocks == ops.norm_bwd_blocks(10 * rows) and per == 17 and (blocks - 1) * per >= rows
+    a = inputs(rows, 64, True)
     g64, g32, got = torch_cpu(a, torch.float64), torch_cpu(a, torch.float32), device(a)
     for k in g64:
         err, e32 = rel_err(got[k], g64[k]), rel_err(g32[k], g64[k])
-        assert err <= max(8 * e32, 2049 * U), (k, err, e32)
+        assert err <= max(8 * e32, rows * U), (k, err, e32)
 
 
 def test_bad_arguments():

@@ -4,7 +4,7 @@
     python tools/family_train_breakdown.py OUT/.../fam_results.db 7 > profiles/family_train_v22_kernels.json
 
 Reads the trace's SQLite database (view `kernels`) and prints, per step, the twenty leading kernels and the share of the kernels of
-csrc/family_train.hip; the second argument is the number of steps the traced run made (warm-up included).  The activation and
+csrc/family_train.hip and the RMSNorm backward of csrc/norm_bwd.hip; the second argument is the number of steps the traced run made (warm-up included).  The activation and
 weight-gradient kernels are shared with the mixture layers (csrc/moe_train_kernels.h) and cannot be told apart by name: they are
 reported together."""
 import json
@@ -12,7 +12,7 @@ import sqlite3
 import sys
 
 NEW = (("rope_bwd_kernel", "rotary backward (rope_bwd_kernel)"), ("rope_kernel", "rotary forward (rope_kernel)"),
-       ("rmsnorm_bwd_kernel", "RMSNorm backward (rmsnorm_bwd_kernel)"), ("norm_kernel<true>", "RMSNorm forward (norm_kernel<true>)"),
+       ("norm_bwd_kernel<true>", "RMSNorm backward (norm_bwd_kernel<true>)"), ("norm_kernel<true>", "RMSNorm forward (norm_kernel<true>)"),
        ("moe_act_fwd_kernel", "GLU activation forward, plain layers and mixtures (moe_act_fwd_kernel)"),
        ("moe_bwd_act_kernel", "GLU activation backward, plain layers and mixtures (moe_bwd_act_kernel)"),
        ("moe_wgrad", "weight-gradient product, plain layers and mixtures (moe_wgrad_kernel / _reduce)"))

@@ -16,7 +16,7 @@ KINDS = (("moe_wgrad", "mixture layer: grouped weight-gradient product (moe_wgra
          ("selective_scan_bwd", "scan backward (selective_scan_bwd_kernel)"), ("scan_bwd_reduce", "scan backward's ordered sums (scan_bwd_reduce_kernel)"),
          ("selective_scan_kernel", "scan forward (selective_scan_kernel<16, true>)"), ("dwconv_silu_bwd", "conv backward (dwconv_silu_bwd / _reduce)"),
          ("dwconv_silu_dacc", "conv backward (dwconv_silu_dacc_kernel)"), ("dwconv_silu", "conv forward (dwconv_silu_kernel)"),
-         ("layernorm_bwd", "LayerNorm backward"), ("norm_kernel", "LayerNorm forward"),
+         ("norm_bwd_kernel<false>", "LayerNorm backward"), ("norm_kernel", "LayerNorm forward"),
          ("rnn_seq_bwd", "recurrence backward (rnn_seq_bwd_kernel)"), ("rnn_seq_train", "recurrence forward (rnn_seq_train_kernel)"),
          ("reg_loss", "fused loss (reg_loss_kernel)"), ("gemm_f32_kernel", "dense GEMM (gemm_f32_kernel)"), ("decode_gemm", "skinny GEMM"),
          ("concat2", "concat2"), ("direct_copy", "torch copies (transposed / padded operands, h_prev, slices)"),

@@ -5,7 +5,7 @@
 // One wave per row, as in metrics.hip: the row's 159 logits sit in three registers per lane and are reduced by the wave trees of
 // amt_common.h.  A workgroup of 16 waves takes 64 consecutive rows of ONE clip (a clip is ceil(L / 64) workgroups), so that the
 // per-clip sums the epoch figures need come out of the same launch: the rows' two sums go to LDS, lanes 0 / 1 of wave 0 add them in
-// row order and leave the workgroup's {ce, bce, n_valid} in ws.  The workgroup that draws the last ticket of ws's counter adds
+// row order and leave the workgroup's {ce, bce, n_valid} in ws.  The last workgroup (last_workgroup.h) adds
 // the workgroups of each clip in order (clip_out), then the clips in order (loss).  The gradient's chord part is divided by the
 // batch's count of valid targets, which every workgroup counts for itself from tgt (integers: exact in any order; B L <= 10^5 ids out
 // of L2) before its rows, so that dlogits needs no second launch.  No floating-point atomic: the order of every addition is a function
@@ -13,12 +13,12 @@
 #include "../../include/amt_hip.h"
 #include "amt_common.h"
 #include "chord_rows.h"
+#include "last_workgroup.h"
 
 namespace {
 
 constexpr int WAVES = 16, THREADS = 64 * WAVES;
 constexpr int ROWS = 64;                    // rows per workgroup
-constexpr int WS_HEAD = 4;                  // ws[0]: the ticket counter (a block of 16 bytes, zeroed before every launch)
 
 __global__ __launch_bounds__(THREADS) void chord_loss_kernel(const float* __restrict__ logits, int ld, const int64_t* __restrict__ tgt,
                                                              const int32_t* __restrict__ emo_class, int B, int L, float lambda, float smoothing,
@@ -105,19 +105,8 @@ __global__ __launch_bounds__(THREADS) void chord_loss_kernel(const float* __rest
     if (wave == 0) {
         if (lane < 2) part[3 * blockIdx.x + lane] = acc;
         if (lane == 2) part[3 * blockIdx.x + 2] = (float)s_cnt[0];
-        // publish this workgroup's three values, then draw a ticket: release before, acquire after, both at agent scope
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) {
-            const unsigned ticket = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(ws), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_cnt[2] = ticket == gridDim.x - 1;
-        }
     }
-    __syncthreads();
-    if (!s_cnt[2] || tid != 0) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (!last_workgroup(ws, gridDim.x, reinterpret_cast<unsigned*>(&s_cnt[2])) || tid != 0) return;
     float ce_all = 0.0f, bce_all = 0.0f, valid_all = 0.0f;
     for (int b = 0; b < B; ++b) {
         float ce = 0.0f, bce = 0.0f, nv = 0.0f;
@@ -145,14 +134,13 @@ extern "C" int64_t amt_chord_loss_ws_floats(int32_t B, int32_t L) {
 extern "C" int32_t amt_chord_loss_fwd_bwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, int32_t B,
                                           int32_t L, float lambda, float smoothing, float* loss, float* clip_out, float* dlogits,
                                           float* ws, void* stream) {
-    AMT_CHECK_ARG(logits && tgt && emo_class && loss && clip_out && ws, "amt_chord_loss_fwd_bwd: null pointer");
+    AMT_CHECK_ARG(logits && tgt && emo_class && loss && clip_out, "amt_chord_loss_fwd_bwd: null pointer");
     AMT_CHECK_ARG(ld >= NC, "amt_chord_loss_fwd_bwd: row stride %d is below the %d classes of a row", ld, NC);
     AMT_CHECK_ARG(B > 0 && L > 0, "amt_chord_loss_fwd_bwd: B=%d, L=%d must be positive", B, L);
     AMT_CHECK_ARG((int64_t)B * L * NC <= (1 << 24), "amt_chord_loss_fwd_bwd: B=%d x L=%d rows: the divisor 159 B L is exact in fp32 up to 2^24", B, L);
     AMT_CHECK_ARG(smoothing >= 0.0f && smoothing < 1.0f, "amt_chord_loss_fwd_bwd: smoothing=%g must be in [0, 1)", (double)smoothing);
-    AMT_CHECK_ARG(((uintptr_t)ws & 15) == 0, "amt_chord_loss_fwd_bwd: ws must be 16-byte aligned");
+    if (const int32_t rc = last_workgroup_reset(ws, "amt_chord_loss_fwd_bwd", (hipStream_t)stream)) return rc;
     const int blocks = B * ((L + ROWS - 1) / ROWS);
-    AMT_HIP(hipMemsetAsync(ws, 0, WS_HEAD * sizeof(float), (hipStream_t)stream));
     hipLaunchKernelGGL(chord_loss_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, logits, ld, tgt, emo_class, B, L, lambda,
                        smoothing, loss, clip_out, dlogits, ws);
     AMT_LAUNCH_CHECK();

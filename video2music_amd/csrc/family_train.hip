@@ -1,5 +1,5 @@
-// What the training of the V1 / V2 chord models needs beside the base model's operators: the backward of the rotary embedding, the
-// plain GLU / SiLU feed-forward in training, and the backward of RMSNorm.
+// What the training of the V1 / V2 chord models needs beside the base model's operators: the backward of the rotary embedding and the
+// plain GLU / SiLU feed-forward in training (the backward of RMSNorm is norm_bwd.hip's).
 //
 // amt_rope_bwd: y = R(theta) x per interleaved pair under rope_kernel's index rule (norm.hip), so dx = R(theta)^T dy:
 //   dx0 = dy0 cos + dy1 sin,  dx1 = dy1 cos - dy0 sin.  One thread per pair reads its pair before it writes it: dx may alias dy.
@@ -12,11 +12,7 @@
 //   dH = dout W2;  dH *= mask_h;  dU = dH silu(G),  dG = dH U silu'(G);  dx = dG Wg + dU W1
 //   dW2 = dout^T H, db2;  dWg = dG^T x, dbg;  dW1 = dU^T x, db1          (moe_wgrad, one group over the n rows)
 //
-// amt_rmsnorm_bwd: with u = x (+ resid), r = rsqrt(mean(u^2) + eps), xh = u r and g = dy w over a row of `dim` values
-//   du = r (g - xh mean(g xh)),   dw = sum over rows of dy xh
-// in layernorm_bwd.hip's two-stage scheme: one wave per row, a workgroup of 4 waves takes a contiguous range of rows, the waves' column
-// sums meet in LDS in wave order and go to the workgroup's slab, the workgroup that draws the last ticket adds the slabs in workgroup
-// order.  Nothing here uses a floating-point atomic: the order of every addition is a function of the shapes alone.
+// Nothing here uses a floating-point atomic: the order of every addition is a function of the shapes alone.
 #include "../../include/amt_hip.h"
 #include "amt_common.h"
 #include "kernels.h"
@@ -40,113 +36,6 @@ __global__ __launch_bounds__(256) void rope_bwd_kernel(const float* dy, const fl
     const float c = cache[ci], sn = cache[ci + 1];
     const float2 g = *reinterpret_cast<const float2*>(dy + 2 * i);
     *reinterpret_cast<float2*>(dx + 2 * i) = make_float2(g.x * c + g.y * sn, g.y * c - g.x * sn);
-}
-
-// ---------------- RMSNorm ----------------
-constexpr int CHUNKS = 4;                   // dim <= 64 lanes * 4 floats * 4 = 1024
-constexpr int MAX_DIM = 64 * 4 * CHUNKS;
-constexpr int MAX_BLOCKS = 128;
-constexpr int ROWS_PER_BLOCK = 16;          // below MAX_BLOCKS workgroups; above, the rows are spread evenly over MAX_BLOCKS
-constexpr int WS_HEAD = 4;                  // ws[0]: the ticket counter (a block of 16 bytes, zeroed before every launch)
-
-inline int rmsnorm_bwd_blocks(int rows) { return cdiv(rows, ROWS_PER_BLOCK) < MAX_BLOCKS ? cdiv(rows, ROWS_PER_BLOCK) : MAX_BLOCKS; }
-
-__global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                          const float* __restrict__ resid, const float* __restrict__ w,
-                                                          float* __restrict__ dx, float* __restrict__ dw, float* ws, int rows, int dim, float eps) {
-    __shared__ __attribute__((aligned(16))) float s_part[4][MAX_DIM];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nb = gridDim.x, blk = blockIdx.x;
-    const int per = (rows + nb - 1) / nb, r_end = min(rows, (blk + 1) * per);
-    float4 gw[CHUNKS], aw[CHUNKS];
-#pragma unroll
-    for (int c = 0; c < CHUNKS; ++c) {
-        const int i = (c * 64 + lane) * 4;
-        gw[c] = i < dim ? ld4(w + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-        aw[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    for (int row = blk * per + wave; row < r_end; row += 4) {
-        const size_t base = (size_t)row * dim;
-        float4 v[CHUNKS], g[CHUNKS];
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < CHUNKS; ++c) {
-            const int i = (c * 64 + lane) * 4;
-            if (i < dim) {
-                v[c] = ld4(x + base + i);
-                if (resid) {
-                    const float4 r = ld4(resid + base + i);
-                    v[c].x += r.x; v[c].y += r.y; v[c].z += r.z; v[c].w += r.w;
-                }
-                g[c] = ld4(dy + base + i);
-                s += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;      // norm_kernel<true>'s expression
-            }
-        }
-        const float rstd = rsqrtf(wave_sum(s) / dim + eps);
-        float s2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < CHUNKS; ++c) {
-            const int i = (c * 64 + lane) * 4;
-            if (i < dim) {
-                const float4 d = g[c];
-                v[c].x *= rstd; v[c].y *= rstd; v[c].z *= rstd; v[c].w *= rstd;
-                aw[c].x += d.x * v[c].x; aw[c].y += d.y * v[c].y; aw[c].z += d.z * v[c].z; aw[c].w += d.w * v[c].w;
-                g[c].x = d.x * gw[c].x; g[c].y = d.y * gw[c].y; g[c].z = d.z * gw[c].z; g[c].w = d.w * gw[c].w;
-                s2 += (g[c].x * v[c].x + g[c].y * v[c].y) + (g[c].z * v[c].z + g[c].w * v[c].w);
-            }
-        }
-        const float m2 = wave_sum(s2) / dim;
-#pragma unroll
-        for (int c = 0; c < CHUNKS; ++c) {
-            const int i = (c * 64 + lane) * 4;
-            if (i < dim) {
-                float4 o;
-                o.x = rstd * (g[c].x - v[c].x * m2); o.y = rstd * (g[c].y - v[c].y * m2);
-                o.z = rstd * (g[c].z - v[c].z * m2); o.w = rstd * (g[c].w - v[c].w * m2);
-                st4(dx + base + i, o);
-            }
-        }
-    }
-    // the 4 waves' column sums, added in wave order, are this workgroup's slab
-#pragma unroll
-    for (int c = 0; c < CHUNKS; ++c) {
-        const int i = (c * 64 + lane) * 4;
-        if (i < dim) st4(&s_part[wave][i], aw[c]);
-    }
-    __syncthreads();
-    float* slab = ws + WS_HEAD + (size_t)blk * dim;
-    for (int f = tid * 4; f < dim; f += 1024) {
-        float4 a = ld4(&s_part[0][f]);
-#pragma unroll
-        for (int wv = 1; wv < 4; ++wv) {
-            const float4 t = ld4(&s_part[wv][f]);
-            a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
-        }
-        st4(slab + f, a);
-    }
-    // publish the slab, then draw a ticket: every wave's stores have landed before lane 0's agent-scope release
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned ticket = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(ws), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = ticket == (unsigned)nb - 1;
-        s_part[0][0] = last ? 1.0f : 0.0f;                 // "I am last" goes through the one LDS array: its sums were read before the barrier above
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (s_part[0][0] == 0.0f) return;
-    for (int f = tid * 4; f < dim; f += 1024) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int k = 0; k < nb; ++k) {
-            const float4 t = ld4(ws + WS_HEAD + (size_t)k * dim + f);
-            a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
-        }
-        st4(dw + f, a);
-    }
 }
 
 // ---------------- the plain GLU / SiLU expert ----------------
@@ -197,22 +86,6 @@ extern "C" int32_t amt_rope_bwd(const float* dy, const float* cache, float* dx, 
     const long total = (long)n0 * seq * n2 * (hd / 2);
     hipLaunchKernelGGL(rope_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, cache, dx, seq, n2, hd,
                        total, bcast);
-    AMT_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int32_t amt_rmsnorm_bwd_blocks(int32_t rows) { return rows > 0 ? rmsnorm_bwd_blocks(rows) : -1; }
-
-extern "C" int32_t amt_rmsnorm_bwd(const float* dy, const float* x, const float* resid, const float* w, float* dx, float* dw, float* ws,
-                                   int32_t rows, int32_t dim, float eps, void* stream) {
-    AMT_CHECK_ARG(dy && x && w && dx && dw && ws, "amt_rmsnorm_bwd: null pointer");
-    AMT_CHECK_ARG(rows > 0, "amt_rmsnorm_bwd: rows=%d must be positive", rows);
-    AMT_CHECK_ARG(dim > 0 && dim % 4 == 0 && dim <= MAX_DIM, "amt_rmsnorm_bwd: dim=%d must be a multiple of 4 in [4, %d]", dim, MAX_DIM);
-    AMT_CHECK_ARG(((uintptr_t)ws & 15) == 0, "amt_rmsnorm_bwd: ws must be 16-byte aligned");
-    static_assert(WS_HEAD + MAX_BLOCKS * MAX_DIM == AMT_RMSNORM_BWD_WS_FLOATS(MAX_DIM), "amt_hip.h states the workspace size");
-    AMT_HIP(hipMemsetAsync(ws, 0, WS_HEAD * sizeof(float), (hipStream_t)stream));
-    hipLaunchKernelGGL(rmsnorm_bwd_kernel, dim3(rmsnorm_bwd_blocks(rows)), dim3(256), 0, (hipStream_t)stream, dy, x, resid, w, dx, dw, ws, rows, dim,
-                       eps);
     AMT_LAUNCH_CHECK();
     return 0;
 }

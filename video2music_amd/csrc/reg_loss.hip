@@ -10,11 +10,11 @@
 // one per 4096 instrument values: two logs and two divisions per value keep one CU busy for 200 us at that batch, all CUs for a few.
 // Workgroup b takes a contiguous range of the values, thread i of it the range's values i, i + 1024, ... in that order; the 64 lanes
 // of a wave meet in the fixed DPP tree of wave_sum, thread 0 adds the 16 wave sums in wave order and leaves the workgroup's two sums in
-// ws.  The workgroup that takes the last ticket of ws's counter (an agent-scope acquire-release add by the thread that wrote, and that
-// will read, the sums; nobody waits for anybody) adds the workgroups' sums in workgroup order.  No floating-point atomic: the order of
-// every addition is a function of the row count alone, so the same inputs give the same bits.
+// ws.  Thread 0 of the last workgroup (last_workgroup.h; nobody waits for anybody) adds the workgroups' sums in workgroup order.  No
+// floating-point atomic: the order of every addition is a function of the row count alone, so the same inputs give the same bits.
 #include "../../include/amt_hip.h"
 #include "amt_common.h"
+#include "last_workgroup.h"
 
 namespace {
 
@@ -22,7 +22,6 @@ constexpr int N_INST = 40;
 constexpr int THREADS = 1024;
 constexpr int MAX_BLOCKS = 256;
 constexpr int VALUES_PER_BLOCK = 4 * THREADS;
-constexpr int WS_HEAD = 4;                  // ws[0]: the ticket counter (a block of 16 bytes, zeroed before every launch)
 
 __global__ __launch_bounds__(THREADS) void reg_loss_kernel(const float* __restrict__ ln_nd, const float* __restrict__ inst,
                                                            const float* __restrict__ note_density, const float* __restrict__ loudness,
@@ -55,23 +54,20 @@ __global__ __launch_bounds__(THREADS) void reg_loss_kernel(const float* __restri
     bce = wave_sum(bce);
     if ((tid & 63) == 0) { s_part[0][tid >> 6] = sl1; s_part[1][tid >> 6] = bce; }
     __syncthreads();
+    float* part = ws + WS_HEAD;
     if (tid == 0) {
         float a = 0.0f, c = 0.0f;
 #pragma unroll
         for (int w = 0; w < THREADS / 64; ++w) { a += s_part[0][w]; c += s_part[1][w]; }
-        float* part = ws + WS_HEAD;
         part[2 * b] = a;
         part[2 * b + 1] = c;
-        // release this workgroup's two sums, acquire the others': the last ticket's holder sees them all
-        const unsigned ticket = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(ws), 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (ticket == (unsigned)nb - 1) {
-            a = 0.0f; c = 0.0f;
-            for (int k = 0; k < nb; ++k) { a += part[2 * k]; c += part[2 * k + 1]; }
-            loss[0] = a / n_reg + c / n_bce;
-            loss[1] = a / n_reg;
-            loss[2] = c / n_bce;
-        }
     }
+    if (!last_workgroup(ws, nb, reinterpret_cast<unsigned*>(&s_part[0][0])) || tid != 0) return;
+    float a = 0.0f, c = 0.0f;
+    for (int k = 0; k < nb; ++k) { a += part[2 * k]; c += part[2 * k + 1]; }
+    loss[0] = a / n_reg + c / n_bce;
+    loss[1] = a / n_reg;
+    loss[2] = c / n_bce;
 }
 
 }  // namespace
@@ -79,13 +75,12 @@ __global__ __launch_bounds__(THREADS) void reg_loss_kernel(const float* __restri
 extern "C" int32_t amt_reg_loss_fwd_bwd(const float* ln_nd, const float* inst, const float* note_density, const float* loudness,
                                         const float* instrument, int32_t rows, float* loss, float* d_ln_nd, float* d_logit,
                                         float* ws, void* stream) {
-    AMT_CHECK_ARG(ln_nd && inst && note_density && loudness && instrument && loss && d_ln_nd && d_logit && ws, "amt_reg_loss_fwd_bwd: null pointer");
+    AMT_CHECK_ARG(ln_nd && inst && note_density && loudness && instrument && loss && d_ln_nd && d_logit, "amt_reg_loss_fwd_bwd: null pointer");
     AMT_CHECK_ARG(rows > 0 && rows <= (1 << 24), "amt_reg_loss_fwd_bwd: rows=%d must be in [1, 2^24] (the divisors 2 rows and 40 rows are exact in fp32)", rows);
-    AMT_CHECK_ARG(((uintptr_t)ws & 15) == 0, "amt_reg_loss_fwd_bwd: ws must be 16-byte aligned");
+    if (const int32_t rc = last_workgroup_reset(ws, "amt_reg_loss_fwd_bwd", (hipStream_t)stream)) return rc;
     static_assert(WS_HEAD + 2 * MAX_BLOCKS == AMT_REG_LOSS_WS_FLOATS, "amt_hip.h states the workspace size");
     const int64_t values = (int64_t)N_INST * rows;
     const int blocks = (int)((values + VALUES_PER_BLOCK - 1) / VALUES_PER_BLOCK < MAX_BLOCKS ? (values + VALUES_PER_BLOCK - 1) / VALUES_PER_BLOCK : MAX_BLOCKS);
-    AMT_HIP(hipMemsetAsync(ws, 0, WS_HEAD * sizeof(float), (hipStream_t)stream));
     hipLaunchKernelGGL(reg_loss_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, ln_nd, inst, note_density, loudness, instrument,
                        rows, loss, d_ln_nd, d_logit, ws);
     AMT_LAUNCH_CHECK();

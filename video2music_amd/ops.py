@@ -231,13 +231,28 @@ def reg_loss(ln_nd, inst, note_density, loudness, instrument):
     return loss, d_ln_nd, d_logit
 
 
-def layernorm_bwd(dy, x, w, resid=None, eps=1e-5):
-    """amt_layernorm_bwd: the backward of `layernorm(x, w, b, resid, eps)` from dy and the forward's own inputs.  Returns dx (the
-    gradient of x and of resid alike), dw, db."""
+def norm_bwd_blocks(rows):
+    """The workgroups `layernorm_bwd` and `rmsnorm_bwd` launch for this many rows (amt_rmsnorm_bwd_blocks, the rule of csrc/norm_bwd.hip;
+    needs no GPU): workgroup b takes the rows [b per, (b + 1) per), per = ceil(rows / blocks), and the gradients of the gain and the
+    bias are the sums of the workgroups' slabs in that order."""
+    n = _lib.call("amt_rmsnorm_bwd_blocks", rows)
+    if n < 1:
+        raise _lib.AmtError(f"amt_rmsnorm_bwd_blocks: amt_layernorm_bwd / amt_rmsnorm_bwd refuse rows={rows}")
+    return n
+
+
+def _norm_bwd_shape(dy, x, w, resid):
     rows, dim = x.shape
     assert dy.shape == x.shape and (resid is None or resid.shape == x.shape) and w.shape == (dim,)
     for t in (dy, x, w) + (() if resid is None else (resid,)):
         assert t.dtype == torch.float32
+    return rows, dim
+
+
+def layernorm_bwd(dy, x, w, resid=None, eps=1e-5):
+    """amt_layernorm_bwd: the backward of `layernorm(x, w, b, resid, eps)` from dy and the forward's own inputs.  Returns dx (the
+    gradient of x and of resid alike), dw, db."""
+    rows, dim = _norm_bwd_shape(dy, x, w, resid)
     dx = torch.empty_like(x)
     dw, db = torch.empty_like(w), torch.empty_like(w)
     ws = torch.empty(4 + 256 * dim, device=x.device, dtype=torch.float32)       # AMT_LAYERNORM_BWD_WS_FLOATS(dim); a call's own scratch
@@ -452,22 +467,13 @@ def rope_bwd(dy, cache, pos=0, out=None):
     return dx
 
 
-def rmsnorm_bwd_blocks(rows):
-    """The workgroups `rmsnorm_bwd` launches for this many rows (amt_rmsnorm_bwd_blocks; needs no GPU): workgroup b takes the rows
-    [b per, (b + 1) per), per = ceil(rows / blocks), and the gain's gradient is the sum of the workgroups' slabs in that order."""
-    n = _lib.call("amt_rmsnorm_bwd_blocks", rows)
-    if n < 1:
-        raise _lib.AmtError(f"amt_rmsnorm_bwd_blocks: amt_rmsnorm_bwd refuses rows={rows}")
-    return n
+rmsnorm_bwd_blocks = norm_bwd_blocks
 
 
 def rmsnorm_bwd(dy, x, w, resid=None, eps=1e-6):
     """amt_rmsnorm_bwd: the backward of `rmsnorm(x, w, resid, eps)` from dy and the forward's own inputs.  Returns dx (the gradient of
     x and of resid alike) and dw."""
-    rows, dim = x.shape
-    assert dy.shape == x.shape and (resid is None or resid.shape == x.shape) and w.shape == (dim,)
-    for t in (dy, x, w) + (() if resid is None else (resid,)):
-        assert t.dtype == torch.float32
+    rows, dim = _norm_bwd_shape(dy, x, w, resid)
     dx, dw = torch.empty_like(x), torch.empty_like(w)
     ws = torch.empty(4 + 128 * dim, device=x.device, dtype=torch.float32)       # AMT_RMSNORM_BWD_WS_FLOATS(dim); a call's own scratch
     _lib.call("amt_rmsnorm_bwd", p(dy), p(x), p(resid), p(w), p(dx), p(dw), p(ws), rows, dim, float(eps), _st())

@@ -3,8 +3,8 @@
 ``-scene_embed``, ``-chord_embed`` and ``-droptoken``.  The bare command trains the reference's default, '1.2.3' with the chord table.
 
 Flags, loop, output files, CSV header, schedule and optimisers are ``train``'s.  A step runs ``VideoMusicTransformer_V2._forward_train``:
-``autograd.RopeFn``, ``GluFn`` and ``RMSNormFn`` (``csrc/family_train.hip``) beside ``AttentionFn``, ``LayerNormFn``, ``LinearFn``,
-``EmbeddingFn`` and the mixture layers' ``MoEFn``.
+``autograd.RopeFn``, ``GluFn`` (``csrc/family_train.hip``) and ``RMSNormFn`` (``csrc/norm_bwd.hip``) beside ``AttentionFn``,
+``LayerNormFn``, ``LinearFn``, ``EmbeddingFn`` and the mixture layers' ``MoEFn``.
 
 The frozen table of ``-chord_embed`` (the reference fills it from a gensim Word2Vec file) comes from ``--chord_embed_table PATH`` (a
 ``.npy`` of shape (n_chords, d_model), float32), from ``--synthetic_weights`` (the procedural fill), or with ``-continue_weights`` in the
