@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers_numeric_range import attn_train_torch_cpu
 from tests.helpers_reg_train import U, rel_err
 from video2music_amd import _lib, ops
 from video2music_amd.autograd import AttentionFn, blh_strides
@@ -49,30 +50,7 @@ def make(B, H, Lq, Lk, hd, causal, rpr, er_len, g, mask):
 
 
 def torch_cpu(a, keep, H, causal, g, dtype):
-    t = {k: torch.from_numpy(v).to(dtype).requires_grad_(k != "dO") for k, v in a.items()}
-    B, Lq, E = t["q"].shape
-    Lk, hd = t["k"].shape[1], E // H
-    qh = (t["q"] * hd ** -0.5).view(B, Lq, H, hd).transpose(1, 2)
-    kh = t["k"].view(B, Lk, H // g, hd).transpose(1, 2).repeat_interleave(g, dim=1)
-    vh = t["v"].view(B, Lk, H // g, hd).transpose(1, 2).repeat_interleave(g, dim=1)
-    S = qh @ kh.transpose(2, 3)
-    i, j = torch.arange(Lq)[:, None], torch.arange(Lk)[None, :]
-    if "Er" in t:
-        er_len = t["Er"].shape[0]
-        rel = qh @ t["Er"].t()                                                   # (B, H, L, er_len)
-        idx = (er_len - 1 - (i - j)).clamp(0, er_len - 1)
-        S = S + torch.where(j <= i, torch.gather(rel, 3, idx.expand(B, H, Lq, Lk)), torch.zeros((), dtype=dtype))
-    if causal:
-        S = S.masked_fill(j > i, float("-inf"))
-    lse = torch.logsumexp(S, dim=-1)
-    Pd = torch.softmax(S, dim=-1)
-    if keep is not None:
-        Pd = Pd * torch.from_numpy(keep).to(dtype) / (1.0 - P_DROP)
-    O = (Pd @ vh).transpose(1, 2).reshape(B, Lq, E)
-    O.backward(t["dO"])
-    out = {"O": O.detach().numpy(), "lse": lse.detach().numpy()}
-    out.update({k: t[k].grad.numpy() for k in t if k != "dO"})
-    return out
+    return attn_train_torch_cpu(a, keep, H, causal, g, dtype, P_DROP)          # the written-out formula, shared with the range tests
 
 
 def device(a, keep, H, causal, g):

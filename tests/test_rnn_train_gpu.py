@@ -9,8 +9,8 @@ own error happens to be near zero."""
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
+from tests.helpers_numeric_range import rnn_torch_cpu as torch_cpu      # nn.LSTM / nn.GRU on the CPU, shared with the range tests
 from tests.helpers_reg_train import U, rel_err
 from video2music_amd import _lib, ops
 from video2music_amd.autograd import RnnLayerFn
@@ -31,19 +31,6 @@ def inputs(G, n_dirs, d, B, L, seed=None):
             shape = (G * d, d) if nm.startswith("weight") else (G * d,)
             par[nm + "_l0" + sfx] = rng.uniform(-k, k, shape).astype(np.float32)
     return par, rng.standard_normal((B, L, d)).astype(np.float32), rng.standard_normal((B, L, n_dirs * d)).astype(np.float32)
-
-
-def torch_cpu(G, n_dirs, d, par, x, dy, dtype, reverse=False):
-    """torch's CPU autograd on nn.LSTM / nn.GRU; a single reversed direction is the forward module on the time-flipped sequence."""
-    m = (nn.LSTM if G == 4 else nn.GRU)(d, d, 1, bidirectional=n_dirs == 2, batch_first=True).to(dtype)
-    m.load_state_dict({k: torch.from_numpy(v).to(dtype) for k, v in par.items()})
-    xt = torch.from_numpy(x).to(dtype).requires_grad_(True)
-    y = m(xt.flip(1) if reverse else xt)[0]
-    y = y.flip(1) if reverse else y
-    y.backward(torch.from_numpy(dy).to(dtype))
-    out = {"y": y.detach().numpy(), "x": xt.grad.numpy()}
-    out.update({k: getattr(m, k).grad.numpy() for k in par})
-    return out
 
 
 def device(G, n_dirs, d, par, x, dy, reverse=False):
