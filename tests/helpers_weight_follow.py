@@ -1,0 +1,639 @@
+"""Do the derived weight tables follow the parameters?  Cases, mutations and the `follows` check of tests/test_weight_follow_gpu.py (on the
+GPU) and tests/test_weight_follow_host.py (the harness on a toy module, torch's version-counter facts, the conditioning of every case on
+the fp64 oracles).
+
+Every inference path reads copies of the weights (the native handle's tables, `_derived()`, the packed / stacked / folded tables of the
+cached V1 / V2 step, the mixture layers' expert stacks, V3's lambda scalars, the regression head's padded, packed and stacked tensors),
+each rebuilt when a signature of (storage pointer, version) over a hand-written list of source tensors changes.  `follows` changes the
+weights of a warm model and asks that the path then computes, bit for bit, what a FRESH model of the same class loaded with the same
+state dict computes, that the change moved the output by at least the case's sensitivity threshold, and that undoing it brings the first
+output back bit for bit.
+
+Shapes: B = 2 clips, T = 6 decode positions, S = 8 frames, the smallest at which every table is read.  Thresholds: the bound the
+parity tests give the same path (8 x e32 of `helpers_family_parity` / `helpers_reg_parity`, 4 x e32 of `helpers_decode_parity`, `TOL` of
+test_lockstep_parity_gpu, `TOL` of test_modules_gpu) times that helper's SENSITIVITY factor (10 / 100 / 10); e32 is the error of the
+fp32 oracle against the fp64 one on the case's own inputs.  The standard perturbation of a tensor is w * 1.5 + 0.25 (PERTURB overrides it
+per key pattern where that is too little; the host file measures every movement on the fp64 oracle, never on the code under test)."""
+import fnmatch
+import functools
+import re
+import types
+from unittest import mock
+
+import numpy as np
+import torch
+
+from oracle import amt_oracle as O
+from oracle import reg_oracle as RO
+from tests import helpers_decode_parity as D
+from tests import helpers_family_parity as FP
+from tests.helpers import feats_t
+from video2music_amd import synthetic
+from video2music_amd.utilities import constants as K
+
+B, T, S = 2, 6, 8
+ROUTE_GAP = FP.ROUTE_GAP
+LOCKSTEP_TOL = dict(a=5e-6, b=4e-6, i=3e-6, j=4e-6)        # test_lockstep_parity_gpu.TOL (that module is GPU-marked: the host file
+MODULES_TOL = 1e-3                                         # cannot import it); test_modules_gpu.TOL.  The GPU file checks both copies.
+OPTIM_LR = 0.05       # a constant -lr as the CLIs pass it through: one Adam step then moves every element by about the standard shift / 5
+ANCHOR_KEY = {"base": "transformer.decoder.layers.0.norm1.bias", "family": "transformer.decoder.layers.0.norm1.*",
+              "reg": "in_proj.0.bias", "moe": "experts.0.linear2.bias"}          # the tensor mutated for the oracle anchor
+
+rel_err = FP.rel_err
+
+
+# ---- the standard perturbation -------------------------------------------------------------------------------------------------------
+# (key pattern, scale, shift, reason): first match wins; the default moves zero biases too
+PERTURB = [
+    ("*.lambda_??", 1.5, 40.0, "V3's lambda vectors enter through exp(lq . lk) with |sum lk| of 0.03 .. 0.14: the standard perturbation moves "
+                               "the logits by 0.07 .. 2 thresholds, a shift of 40 by 3.3 .. (fp64 oracle, test_weight_follow_host.py)"),
+    ("gate.bias", 3.0, 0.25, "the stand-alone mixture layers' router bias: a shift common to all experts changes neither the top-2 nor their "
+                             "softmax, and the scale of 1.5 alone moves the output by 0.998 of test_modules_gpu's coarse bound x 10"),
+    ("*", 1.5, 0.25, "the standard perturbation"),
+]
+
+
+def perturbation(key):
+    for pat, scale, shift, _ in PERTURB:
+        if fnmatch.fnmatchcase(key, pat):
+            return scale, shift
+    raise KeyError(key)
+
+
+def perturb_(t, key, alone=True):
+    """`alone`: the tensor is the only one perturbed (the sweeps); with every tensor perturbed at once the standard one is enough for
+    all (and a shifted lambda_q times a shifted lambda_k would overflow exp)."""
+    scale, shift = perturbation(key) if alone else perturbation("")
+    return t.mul_(scale).add_(shift)
+
+
+# ---- tensors of the state dict that a path does not read ---------------------------------------------------------------------------
+# (case pattern, path pattern, key pattern, reason).  For these `follows` asks bit equality with the first output instead.
+UNUSED = [
+    ("*", "*", "embedding.weight", "the reference embeds root + attr (or the frozen chord table); `embedding` takes no part in forward"),
+    ("*", "*", "condition_linear.*", "constructed by the reference, never called"),
+    ("base*", "*", "Wout_root.*", "read with IS_SEPERATED only"),
+    ("base*", "*", "Wout_attr.*", "read with IS_SEPERATED only"),
+    ("*_ce", "*", "embedding_root.weight", "chord_embed: the chord ids index the frozen table"),
+    ("*_ce", "*", "embedding_attr.weight", "chord_embed: the attr slot adds a zero row"),
+    ("v3*", "*", "*.ff.bias", "the balancing buffer enters the routing in training mode only"),
+    # experts no token of the path's 6 .. 16 tokens per mixture layer routes to (the fp64 oracle's routing; ROUTE_GAP keeps fp32's the same)
+    ("v11_128_rms", "one_clip", "transformer.decoder.layers.0.ff.experts.[13].*", "no token of clip 0 routes to it"),
+    ("v11_128_rms", "one_clip", "transformer.decoder.layers.1.ff.experts.0.*", "no token of clip 0 routes to it"),
+    ("v11_128_rms", "one_clip", "transformer.encoder.layers.1.ff.experts.5.*", "no frame of clip 0 routes to it"),
+    ("v10_128", "one_clip", "transformer.decoder.layers.1.ff.experts.5.*", "no token of clip 0 routes to it"),
+    ("v123_128", "forward", "transformer.encoder.layers.1.ff.experts.[34].*", "no frame of the batch routes to it"),
+    ("v123_128", "lockstep", "transformer.encoder.layers.1.ff.experts.3.*", "no frame of either clip routes to it"),
+    ("v123_128", "one_clip", "transformer.encoder.layers.1.ff.experts.3.*", "no frame of clip 0 routes to it"),
+    ("v123_128", "one_clip", "transformer.decoder.layers.0.ff.experts.0.*", "no token of clip 0 routes to it"),
+    ("v133_128", "forward", "transformer.encoder.layers.3.ff.experts.[01].*", "no frame of the batch routes to it"),
+    ("v133_128", "forward", "transformer.decoder.layers.3.ff.experts.0.*", "no token of the batch routes to it"),
+    ("v133_128", "ops_step", "transformer.encoder.layers.3.ff.experts.[013].*", "no frame of clip 0 routes to it"),
+    ("v133_128", "ops_step", "transformer.decoder.layers.3.ff.experts.[014].*", "no token of clip 0 routes to it"),
+    ("reg_*", "feature", "regressor.*", "get_feature stops before the heads"),
+    ("reg_*", "feature", "classifier.*", "get_feature stops before the heads"),
+    ("reg_*", "*lnnd", "classifier.*", "the other head"),
+    ("reg_*", "*inst", "regressor.*", "the other head"),
+]
+
+
+def unused_reason(case, path, key):
+    for cp, pp, kp, why in UNUSED:
+        if fnmatch.fnmatchcase(case, cp) and fnmatch.fnmatchcase(path, pp) and fnmatch.fnmatchcase(key, kp):
+            return why
+    return None
+
+
+# ---- mutations -------------------------------------------------------------------------------------------------------------------------
+def tensors_of(m, keys=None):
+    """{key: the module's own Parameter / buffer} for the floating-point entries of its state dict."""
+    own = {k: v for k, v in m.state_dict(keep_vars=True).items() if v.is_floating_point()}
+    return own if keys is None else {k: own[k] for k in keys}
+
+
+def v_inplace(m, keys, run):
+    with torch.no_grad():
+        for k, p in tensors_of(m, keys).items():
+            perturb_(p, k, keys is not None)
+
+
+def v_detach(m, keys, run):
+    for k, p in tensors_of(m, keys).items():
+        perturb_(p.detach(), k, keys is not None)
+
+
+def _optim(cls_name):
+    def v_optim(m, keys, run):
+        """One step of the optimiser as train.py / train_regression.py construct it (`train_regression.make_optimizer`; neither CLI
+        clips gradients), on seeded gradients: no backward needed, so it also covers models that do not train here."""
+        from video2music_amd.train_regression import make_optimizer
+        ps = [p for p in m.parameters() if p.requires_grad]
+        g = torch.Generator().manual_seed(7)
+        for p in ps:
+            p.grad = torch.randn(p.shape, generator=g).to(p.device)
+        make_optimizer(types.SimpleNamespace(optimizer=cls_name), ps, OPTIM_LR).step()
+        for p in ps:
+            p.grad = None
+    v_optim.__name__ = f"v_optim_{cls_name}"
+    return v_optim
+
+
+def _moved_sd(m, keys):
+    own = tensors_of(m, keys)
+    return {k: (perturb_(v.detach().clone(), k, keys is not None) if k in own else v.detach().clone()) for k, v in m.state_dict().items()}
+
+
+def v_load(m, keys, run):
+    m.load_state_dict(_moved_sd(m, keys))
+
+
+def v_load_assign(m, keys, run):
+    m.load_state_dict(_moved_sd(m, keys), assign=True)
+
+
+def v_setdata(m, keys, run):
+    for k, p in tensors_of(m, keys).items():
+        p.data = perturb_(p.detach().clone(), k, keys is not None)
+
+
+def v_cpu_roundtrip(m, keys, run):
+    dev = next(m.parameters()).device
+    m.cpu()
+    v_inplace(m, keys, run)
+    m.to(dev)
+
+
+def i_data_inplace(m, keys, run):
+    for k, p in tensors_of(m, keys).items():
+        perturb_(p.data, k, keys is not None)
+    m.drop_derived()
+
+
+def i_alias(m, keys, run):
+    own = tensors_of(m, keys)
+    xs = {k: p.detach().clone() for k, p in own.items()}
+    for k, p in own.items():
+        p.data = xs[k]
+    run()
+    for k, x in xs.items():
+        perturb_(x, k, keys is not None)
+    m.drop_derived()
+    return xs
+
+
+def i_swap(m, keys, run):
+    """The EMA idiom; every step is an ordinary assignment and the caches must follow without help."""
+    own = tensors_of(m, keys)
+    xs = {k: p.detach().clone() for k, p in own.items()}
+    ys = {k: p.detach().clone().mul_(0.5) for k, p in own.items()}
+    for k, p in own.items():
+        p.data = xs[k]
+    run()
+    for k, p in own.items():
+        p.data = ys[k]
+    run()
+    for k, x in xs.items():
+        perturb_(x, k, keys is not None)                 # detached from p: no counter of p moves
+    for k, p in own.items():
+        p.data = xs[k]
+    return xs, ys
+
+
+VISIBLE = [v_inplace, v_detach, _optim("Adam"), _optim("AdamW"), v_load, v_load_assign, v_setdata, v_cpu_roundtrip, i_swap]
+NEEDS_CALL = [i_data_inplace, i_alias]
+KINDS = {f.__name__: f for f in VISIBLE + NEEDS_CALL}
+
+
+# ---- the check -------------------------------------------------------------------------------------------------------------------------
+def twin_of(case, a, device):
+    """A new object of the same class and constructor arguments, loaded with clones of `a`'s current state dict, never run before."""
+    b = case.make()
+    b.load_state_dict({k: v.detach().clone().cpu() for k, v in a.state_dict().items()})
+    return b.to(device)
+
+
+def follows(case, a, path, mutate, keys=None, threshold=None, unused=False, device="cuda", y0=None, anchor=None, ids=False):
+    """Steps 1-7 of the module docstring on model `a` (left as it was found).  `path(model)` returns a CPU tensor; `mutate(model, keys,
+    run)`; keys None: every floating-point tensor of the state dict.  `ids`: the path returns arg-max ids and one tensor is changed: no
+    sensitivity assert (step 6), everything else.  `anchor(y1, state dict)`: called once after the mutation."""
+    run = lambda: path(a)
+    if y0 is None:
+        y0 = run()
+    orig = {k: v.detach().clone() for k, v in tensors_of(a).items()}
+    keep = mutate(a, keys, run)
+    y1 = run()
+    assert torch.isfinite(y1.double()).all(), "the mutated model's output is not finite"
+    y_ref = path(twin_of(case, a, device))
+    stale = "" if torch.equal(y1, y_ref) else f"rel_err {rel_err(y1, y_ref):.3e} (against the old output: {rel_err(y1, y0):.3e})"
+    assert torch.equal(y1, y_ref), f"STALE: after {mutate.__name__} of {keys or 'every tensor'} the path does not compute what a fresh model does: {stale}"
+    if unused:
+        assert torch.equal(y1, y0), f"UNUSED is wrong: {keys} moved the output by {rel_err(y1, y0):.3e}"
+    elif not ids:                                         # (ids of a sweep: see test_every_tensor_alone_moves_every_path)
+        moved = rel_err(y1, y0)
+        assert moved >= threshold, f"INSENSITIVE: {mutate.__name__} of {keys or 'every tensor'} moved the output by {moved:.3e} < {threshold:.3e}"
+    if anchor is not None:
+        anchor(y1, {k: v.detach().cpu().clone() for k, v in a.state_dict().items()})
+    with torch.no_grad():                                 # undo, visibly
+        for k, p in tensors_of(a).items():             # (only what the mutation touched: the rest keeps its version)
+            if not torch.equal(p.detach(), orig[k].to(p.device)):
+                p.copy_(orig[k].to(p.device))
+    y2 = run()
+    assert torch.equal(y2, y0), f"STALE after the undo of {mutate.__name__} of {keys or 'every tensor'}: rel_err {rel_err(y2, y0):.3e}"
+    del keep
+    return y0
+
+
+# ---- cases -----------------------------------------------------------------------------------------------------------------------------
+class Case:
+    """name; kind; make() -> fresh CPU model in eval mode; paths {name: f(model) -> CPU tensor}; oracle(sd, path, dtype) -> tensor in
+    the path's layout (None: the path has no oracle), with `gates` filled; bound(path, sd); factor: the SENSITIVITY of its helper."""
+
+    def __init__(self, name, kind, make, seed, recipe="default", env=()):
+        self.name, self.kind, self.make, self.seed, self.recipe, self.env = name, kind, make, seed, recipe, dict(env)
+        self.paths = {}
+        self.factor = D.SENSITIVITY if kind == "base" else FP.SENSITIVITY
+
+    @functools.cached_property
+    def sd(self):
+        """Seeded fp32 state dict by the model's own key list (the sinusoidal `pe` buffers keep their values)."""
+        own = self.make().state_dict()
+        shapes = [(k, tuple(v.shape)) for k, v in own.items() if not k.endswith(".pe")]
+        sd = {k: torch.from_numpy(v) for k, v in synthetic.synthetic_state_dict(shapes, seed=self.seed, recipe=self.recipe).items()}
+        sd.update({k: v.clone() for k, v in own.items() if k.endswith(".pe")})
+        return sd
+
+    def model(self, device="cuda"):
+        m = self.make()
+        m.load_state_dict({k: v.clone() for k, v in self.sd.items()})
+        return m.to(device)
+
+    def keys(self):
+        return [k for k, v in self.sd.items() if v.is_floating_point()]
+
+    def e32(self, path, sd):
+        y64 = self.oracle(sd, path, torch.float64)
+        n = torch.get_num_threads()
+        torch.set_num_threads(1)                          # helpers_reg_parity.ref32: a threaded BLAS moves e32 from machine to machine
+        try:
+            return self.err(path)(self.oracle(sd, path, torch.float32), y64)
+        finally:
+            torch.set_num_threads(n)
+
+    def err(self, path):
+        return D.prob_err if path == "host_step" else rel_err
+
+    def bound(self, path, sd=None):
+        """The bound the parity tests give this path, on state dict `sd` (default: the case's own)."""
+        fixed = self.fixed_bound(path)
+        if fixed is not None:
+            return fixed
+        return self._bound0(path) if sd is None else self.bound_factor * self.e32(path, sd)
+
+    @functools.lru_cache(maxsize=None)
+    def _bound0(self, path):
+        return self.bound_factor * self.e32(path, self.sd)
+
+    def threshold(self, path):
+        return self.factor * self.bound(path)
+
+    def fixed_bound(self, path):
+        return None
+
+    def oracle_all(self, sd, dtype):
+        """{path: oracle output} for every path that has one, sharing the oracle runs the paths have in common."""
+        return {p: y for p in self.paths for y in [self.oracle(sd, p, dtype)] if y is not None}
+
+    def groups(self):
+        """{group: keys}: the sweep's pytest ids, one per layer and stack plus the rest."""
+        out = {}
+        for k in self.keys():
+            g = re.match(r"(?:transformer\.(encoder|decoder)|model)\.layers\.(\d+)\.", k)
+            out.setdefault("rest" if g is None else f"{(g.group(1) or 'layer')[:3]}{g.group(2)}", []).append(k)
+        return out
+
+
+def _cast(sd, dtype):
+    return {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
+
+
+def _dev(m):
+    return next(m.parameters()).device
+
+
+# .... base model ....
+class BaseCase(Case):
+    bound_factor = D.FACTOR
+
+    def __init__(self, name, seed, dff=256, rpr=True, **ctor):
+        self.cfg = dict(n_layers=2, num_heads=4, d_model=128, dim_feedforward=dff, max_sequence_chord=300,
+                        total_vf_dim=synthetic.total_vf_dim(1) - int(bool(ctor.get("scene_embed"))), rpr=rpr, **ctor)
+        self.folded = D.takes_folded_chain(128, dff)
+        super().__init__(name, "base", self._make, seed)
+        self.ce = bool(ctor.get("chord_embed"))
+        feats = synthetic.synthetic_features(B, seed=100 + seed, n_frames=S)
+        self.f = feats_t(feats, key=D.clip_keys(B, seed))
+        self.toks, self.roots, self.attrs = D.chord_ids(B, T, seed)
+        if self.ce:
+            self.roots, self.attrs = self.toks, torch.zeros_like(self.toks)
+        self.paths = {"forward": self.p_forward, "graph_step": self.p_graph, "host_step": self.p_host}
+
+    def _make(self):
+        from video2music_amd.model.video_music_transformer import VideoMusicTransformer
+        return VideoMusicTransformer(**self.cfg).eval()
+
+    def fdev(self, m):
+        return {k: v.to(_dev(m)) for k, v in self.f.items()}
+
+    def p_forward(self, m):
+        with torch.no_grad():
+            return m(self.toks, self.roots, self.attrs, *D.feature_args(self.fdev(m))).cpu()
+
+    def p_graph(self, m):
+        return D.teacher_forced_logits(m, self.fdev(m), self.toks, self.roots, self.attrs)
+
+    def p_host(self, m):
+        return D.host_step_probs(m, self.fdev(m), self.toks, self.roots, self.attrs, 0, 2)
+
+    def oracle(self, sd, path, dtype):
+        sd = _cast(sd, dtype)
+        f = {k: v.to(dtype) for k, v in self.f.items()}
+        L = T if path == "forward" else T - 1
+        # the oracle computes the sinusoidal tables itself; the model reads them from its state dict: hand it the state dict's
+        pe = [sd["positional_encoding_video.pe"][:S, 0], sd["positional_encoding.pe"][:L, 0]]        # encode first, then the chord stream
+        with torch.no_grad(), mock.patch.object(O, "positional_encoding", side_effect=pe):
+            y = O.forward(sd, self.cfg["num_heads"], self.roots[:, :L], self.attrs[:, :L], f["semantic"], f["key"], f["scene_offset"],
+                          f["motion"], f["emotion"])
+        self.gates = []
+        return D.decision_rows(y, self.toks, 0, 2) if path == "host_step" else y
+
+
+# .... V1 / V2 / V3 ....
+class FamilyCase(Case):
+    bound_factor = FP.BOUND_FACTOR
+
+    def __init__(self, name, cls, version, E, dff, seed, n_layers=2, paths=("forward", "lockstep", "one_clip"), env=(), **kw):
+        self.cls, self.version, self.E, self.H, self.kw = cls, version, E, 4, kw
+        self.ctor = dict(version_name=version, n_layers=n_layers, num_heads=4, d_model=E, dim_feedforward=dff,
+                         total_vf_dim=synthetic.total_vf_dim(1) - int(bool(kw.get("scene_embed"))), **kw)
+        super().__init__(name, "family", self._make, seed, env=env)
+        self.ce = bool(kw.get("chord_embed"))
+        self.f = feats_t(synthetic.synthetic_features(B, seed=seed + 1000, n_frames=S))
+        rs = np.random.RandomState(seed + 2000)
+        if self.ce:
+            self.roots, self.attrs = torch.from_numpy(rs.randint(0, K.CHORD_SIZE, size=(B, T))), torch.zeros(B, T, dtype=torch.long)
+        else:
+            self.roots = torch.from_numpy(rs.randint(0, K.CHORD_ROOT_SIZE, size=(B, T)))
+            self.attrs = torch.from_numpy(rs.randint(0, K.CHORD_ATTR_SIZE, size=(B, T)))
+        every = {"forward": self.p_forward, "lockstep": self.p_lockstep, "one_clip": self.p_one_clip, "ops_step": self.p_ops_step,
+                 "generate": self.p_generate}
+        self.paths = {k: every[k] for k in paths}
+
+    def _make(self):
+        from video2music_amd.model import video_music_transformer as V
+        return getattr(V, self.cls)(**self.ctor).eval()
+
+    def fdev(self, m):
+        return {k: v.to(_dev(m)) for k, v in self.f.items()}
+
+    def p_forward(self, m):
+        f = self.fdev(m)
+        with torch.no_grad():
+            return m(self.roots, self.roots, self.attrs, f["semantic"], f["key"], f["scene_offset"], f["motion"], f["emotion"]).cpu()
+
+    def p_lockstep(self, m):
+        from tests.helpers import lockstep_step_logits
+        return lockstep_step_logits(m, self.fdev(m), self.roots, self.attrs)
+
+    def p_one_clip(self, m):
+        from tests.helpers import one_clip_step_logits
+        return one_clip_step_logits(m, self.fdev(m), self.roots[0], self.attrs[0])
+
+    def p_ops_step(self, m):
+        """The cached step issued operator by operator (layers of unequal width: st["native"] is false), clip 0, teacher-forced."""
+        f = self.fdev(m)
+        with torch.no_grad():
+            memory, _, S_ = m._encode_memory(f["semantic"][:1], f["scene_offset"][:1], f["motion"][:1], f["emotion"][:1])
+            st = m._cache_init(memory, S_)
+            assert not st["native"], "the case is meant for the operator path"
+            key = float(f["key"].reshape(-1)[0])
+            return torch.stack([m._decode_step_ops(int(self.roots[0, t]), int(self.attrs[0, t]), key, t, st).clone() for t in range(T)]).cpu()
+
+    def p_generate(self, m):
+        f = self.fdev(m)
+        pr, prr, pra = (torch.tensor(v) for v in zip(K.primer_from_name("C")))
+        if self.ce:
+            prr, pra = pr, torch.zeros_like(pr)
+        with torch.no_grad():
+            return m.generate(f["semantic"][:1], f["key"][:1], f["scene_offset"][:1], f["motion"][:1], f["emotion"][:1], pr, prr, pra,
+                              target_seq_length=T, beam=0, sampler="argmax", use_graph=True).cpu()
+
+    def fixed_bound(self, path):
+        if path == "forward":
+            return None
+        if path in ("one_clip", "ops_step"):
+            return LOCKSTEP_TOL["j"]
+        if path == "generate":
+            return LOCKSTEP_TOL["i"]          # ids: one moved id is a rel_err of >= 1 / 158
+        return LOCKSTEP_TOL[{128: "a", 256: "b"}[self.E] if self.version == "2.2" and not self.ce else "i"]
+
+    def oracle(self, sd, path, dtype):
+        if path == "generate":
+            return None
+        sd = _cast(sd, dtype)
+        f = {k: v.to(dtype) for k, v in self.f.items()}
+        self.gates = []
+
+        def run(sl):
+            with torch.no_grad():
+                return O.forward_family(sd, self.version, self.H, self.roots[sl], self.attrs[sl], f["semantic"][sl], f["key"][sl],
+                                        f["scene_offset"][sl], f["motion"][sl], f["emotion"][sl], max_seq_video=300, collect=self.gates)
+        if path == "forward":
+            return run(slice(None))
+        if path == "lockstep":                                      # each clip a batch of one; (T, B, 159)
+            return torch.stack([run(slice(c, c + 1))[0] for c in range(B)], dim=1)
+        return run(slice(0, 1))[0]
+
+
+    def oracle_all(self, sd, dtype):
+        out = {}
+        if "forward" in self.paths:
+            out["forward"] = self.oracle(sd, "forward", dtype)
+        steps = [p for p in self.paths if p in ("lockstep", "one_clip", "ops_step")]
+        if steps:
+            gates = self.gates if out else []
+            y = self.oracle(sd, "lockstep", dtype)
+            self.gates = gates + self.gates
+            out.update({p: (y if p == "lockstep" else y[:, 0]) for p in steps})
+        return out
+
+
+# .... regression heads ....
+class RegCase(Case):
+    bound_factor = FP.BOUND_FACTOR
+
+    def __init__(self, name, rm, d, seed, n_layers=2, vf=37):
+        self.rm, self.ctor = rm, dict(n_layers=n_layers, d_model=d, d_hidden=64, total_vf_dim=vf, regModel=rm)
+        super().__init__(name, "reg", self._make, seed)
+        rs = np.random.RandomState(seed + 1000)
+        z = rs.standard_normal((B, S, 6))
+        e = np.exp(z - z.max(-1, keepdims=True))
+        self.f = dict(semantic=torch.from_numpy(rs.standard_normal((B, S, vf - 6)).astype(np.float32)),
+                      emotion=torch.from_numpy((e / e.sum(-1, keepdims=True)).astype(np.float32)))
+        self.targets = (torch.from_numpy(rs.uniform(0, 10, (B, S)).astype(np.float32)), torch.from_numpy(rs.uniform(0, 1, (B, S)).astype(np.float32)),
+                        torch.from_numpy((rs.uniform(size=(B, S, 40)) < 0.3).astype(np.float32)))
+        self.paths = {"feature": self.p_feature, "lnnd": lambda m: self.p_forward(m)[0], "inst": lambda m: self.p_forward(m)[1],
+                      "metrics_lnnd": lambda m: self.p_metrics(m)["ln_nd"].cpu(), "metrics_inst": lambda m: self.p_metrics(m)["inst"].cpu()}
+
+    def _make(self):
+        from video2music_amd.model.video_regression import VideoRegression
+        return VideoRegression(**self.ctor).eval()
+
+    def p_feature(self, m):
+        dev = _dev(m)
+        with torch.no_grad():
+            return m.get_feature(self.f["semantic"].to(dev), None, None, self.f["emotion"].to(dev)).cpu()
+
+    def p_forward(self, m):
+        dev = _dev(m)
+        with torch.no_grad():
+            return tuple(t.cpu() for t in m(self.f["semantic"].to(dev), None, None, self.f["emotion"].to(dev)))
+
+    def p_metrics(self, m):
+        from video2music_amd.metrics import regression_metrics
+        dev = _dev(m)
+        with torch.no_grad():
+            feat = m.get_feature(self.f["semantic"].to(dev), None, None, self.f["emotion"].to(dev))
+            return regression_metrics(m, feat, *self.targets, return_rows=True)
+
+    def oracle(self, sd, path, dtype):
+        col = {}
+        with torch.no_grad():
+            ln_nd, inst = RO.forward(sd, self.f["semantic"], self.f["emotion"], collect=col, reg_model=self.rm, dtype=dtype)
+        self.gates = col["gates"]
+        return col["feature"] if path == "feature" else ln_nd if path.endswith("lnnd") else inst
+
+
+    def oracle_all(self, sd, dtype):
+        col = {}
+        with torch.no_grad():
+            ln_nd, inst = RO.forward(sd, self.f["semantic"], self.f["emotion"], collect=col, reg_model=self.rm, dtype=dtype)
+        self.gates = col["gates"]
+        return {p: (col["feature"] if p == "feature" else ln_nd if p.endswith("lnnd") else inst) for p in self.paths}
+
+
+# .... stand-alone mixture layers ....
+class MoECase(Case):
+    def __init__(self, name, shared, seed):
+        self.shared = shared
+        super().__init__(name, "moe", self._make, seed)
+        self.x = torch.from_numpy(np.random.RandomState(seed + 1000).standard_normal((32, B, 128)).astype(np.float32))
+        self.paths = {"forward": self.p_forward}
+
+    def _make(self):
+        from video2music_amd.model.moe import GLUExpert, MoELayer, SharedMoELayer
+        e = GLUExpert(128, 192)
+        return (SharedMoELayer(e, 128, n_experts=6, n_experts_per_token=2) if self.shared else MoELayer(e, 128, 6, 2)).eval()
+
+    def p_forward(self, m):
+        with torch.no_grad():
+            return m(self.x.to(_dev(m))).cpu()
+
+    def fixed_bound(self, path):
+        return MODULES_TOL
+
+    def err(self, path):
+        return lambda got, ref: float((got.double() - ref.double()).abs().max())          # test_modules_gpu's measure
+
+    def oracle(self, sd, path, dtype):
+        sd = _cast(sd, dtype)
+        with torch.no_grad():
+            self.gates = [O.linear(self.x.to(dtype), sd["gate.weight"], sd["gate.bias"])]
+            return O.moe_forward(self.x.to(dtype), sd, 6, k=2, shared=self.shared)
+
+
+V1, V2, V3 = "VideoMusicTransformer_V1", "VideoMusicTransformer_V2", "VideoMusicTransformer_V3"
+STEPS = ("forward", "lockstep", "one_clip", "generate")
+CASES = [
+    BaseCase("base_fold", 11),                                                     # the folded decode chain, Er tables
+    BaseCase("base_plain_norpr", 12, dff=160, rpr=False),                          # d + dff = 288: the plain chain; the zero Er
+    BaseCase("base_se", 13, scene_embed=True),
+    BaseCase("base_ce", 14, chord_embed=True),
+    # V2 builds three GLU layers whatever n_layers says: g1fold in every layer, ffnfold in layers 0 and 1 (the last has no next layer)
+    FamilyCase("v22_256", V2, "2.2", 256, 256, 21, paths=STEPS),
+    FamilyCase("v22_256_ffn0", V2, "2.2", 256, 256, 21, paths=("lockstep",), env={"AMT_V2_FOLD_FFN": "0"}),
+    FamilyCase("v22_256_ffn2", V2, "2.2", 256, 256, 21, paths=("lockstep",), env={"AMT_V2_FOLD_FFN": "2"}),
+    FamilyCase("v22_256_g10", V2, "2.2", 256, 256, 21, paths=("lockstep",), env={"AMT_V2_FOLD_G1": "0"}),
+    FamilyCase("v22_128", V2, "2.2", 128, 256, 22, paths=STEPS),                   # ffnfold off by width, g1fold on
+    FamilyCase("v22_128_ce", V2, "2.2", 128, 256, 23, paths=STEPS, chord_embed=True),
+    FamilyCase("v20_128", V2, "2.0", 128, 256, 24, paths=STEPS),                   # learned positional tables: `_pe_chord`
+    # RMSNorm (no norm bias, every fold off) is a V1 case: VideoMusicTransformer_V2 accepts rms_norm and ignores it, as the reference does
+    FamilyCase("v11_128_rms", V1, "1.1", 128, 256, 25, paths=STEPS, rms_norm=True),   # GLU mixtures without a shared expert
+    FamilyCase("v10_128", V1, "1.0", 128, 256, 26, paths=STEPS),                   # SiLU mixtures without a shared expert
+    FamilyCase("v123_128", V1, "1.2.3", 128, 256, 27, paths=STEPS),                # rotary, shared SiLU mixtures
+    FamilyCase("v133_128", V1, "1.3.3", 128, 192, 28, n_layers=4, paths=("forward", "ops_step", "generate")),   # widths 192 and 256
+    FamilyCase("v31_128", V3, "3.1", 128, 256, 29, n_layers=3, paths=("forward",)),  # lambda scalars, subln, the 2 d_model RoPE cache
+    RegCase("reg_bilstm", "bilstm", 64, 31),
+    RegCase("reg_gru", "gru", 64, 32),
+    RegCase("reg_bimambap", "bimamba+", 64, 33),
+    RegCase("reg_mamba", "mamba", 64, 34),
+    RegCase("reg_sharedmoe_bimambap", "sharedmoe_bimamba+", 64, 35, n_layers=1),
+    RegCase("reg_cnnbigru", "cnnbigru", 64, 36),
+    MoECase("moe_plain", False, 41),
+    MoECase("moe_shared", True, 42),
+]
+BY_NAME = {c.name: c for c in CASES}
+assert len(BY_NAME) == len(CASES)
+
+
+# What each case exists to reach, pinned by test_cases_reach_their_tables: the base handle's chain (launches per eagerly issued step) and the
+# roles of the cached step's folded tables after one lockstep step: layers with a g1fold entry, (layer, mode) of the ffnfold entries
+BASE_FOLDED = {"base_fold": True, "base_plain_norpr": False, "base_se": True, "base_ce": True}
+STEP_FOLDS = {
+    "v22_256": ({0, 1, 2}, {(0, 1), (1, 1)}),             # the last layer has no next layer to fold norm3 into
+    "v22_256_ffn0": ({0, 1, 2}, set()),
+    "v22_256_ffn2": ({0, 1, 2}, {(0, 2), (1, 2), (2, 2)}),
+    "v22_256_g10": (set(), {(0, 1), (1, 1)}),
+    "v22_128": ({0, 1, 2}, set()),                        # ffnfold off by width
+    "v22_128_ce": ({0, 1, 2}, set()),
+    "v20_128": ({0, 1, 2}, set()),
+    "v11_128_rms": (set(), set()),                        # RMSNorm: nothing to fold
+    "v10_128": ({0, 1}, set()),                           # mixture layers: norm1 folds, the feed-forward does not
+    "v123_128": ({0, 1}, set()),
+}
+
+
+def step_folds(m):
+    """(layers with a g1fold entry, (layer, mode) of the ffnfold entries) in the model's step-table cache."""
+    roles = list(m.__dict__.get("_pack_cache", {}))
+    return ({r[1] for r in roles if r[0] == "g1fold"}, {(r[1], r[2]) for r in roles if r[0] == "ffnfold"})
+
+
+def route_gap(case):
+    """Smallest relative 2nd-vs-3rd gate-logit gap of the oracle run last made on `case` (inf without a mixture layer)."""
+    return FP.route_gap(case.gates)
+
+
+def set_env(monkeypatch, case):
+    for k in ("AMT_V2_FOLD_FFN", "AMT_V2_FOLD_G1"):
+        if k in case.env:
+            monkeypatch.setenv(k, case.env[k])
+        else:
+            monkeypatch.delenv(k, raising=False)
+
+
+def anchor_keys(case):
+    return [k for k in case.keys() if fnmatch.fnmatchcase(k, ANCHOR_KEY[case.kind])][:1]
+
+
+def make_anchor(case, path):
+    """After the designated mutation the output must also be within the path's existing bound of the fp64 oracle on the mutated state
+    dict: a cache shared by the whole process would make the model and its twin wrong together."""
+    def anchor(y1, sd):
+        ref = case.oracle(sd, path, torch.float64)
+        if ref is None:
+            return
+        assert route_gap(case) > ROUTE_GAP, f"{case.name}: the mutated oracle has a routing near-tie ({route_gap(case):.2e}); pick another seed"
+        bound, err = case.bound(path, sd), case.err(path)(y1, ref)
+        print(f"\nWEIGHT_FOLLOW anchor {case.name}/{path}: err {err:.2e}  bound {bound:.2e}")
+        assert err <= bound, (case.name, path, err, bound)
+    return anchor

@@ -262,6 +262,13 @@ class TemperatureScheduler(nn.Module):
         return self.t
 
 
+def drop_derived_below(module):
+    """`drop_derived()` of every submodule of `module` that has one (mixture layers, differential attentions)."""
+    for sub in module.modules():
+        if sub is not module and hasattr(sub, "drop_derived"):
+            sub.drop_derived()
+
+
 class _MoEBase(nn.Module):
     shared = False
     ep_group = None
@@ -306,6 +313,13 @@ class _MoEBase(nn.Module):
                            _stack(self.experts, "linear2", "weight"), _stack(self.experts, "linear2", "bias"))
             self._stack_sig = sig
         return self._stack
+
+    def drop_derived(self):
+        """Forgets every copy derived from the parameters (the stacked expert tensors): the next forward rebuilds them.  To be called
+        after a write torch's version counters do not see (`p.data.mul_(..)`, a write through a tensor that `p.data` aliases);
+        INTEGRATION.md, "When weights change"."""
+        self._stack_sig = None
+        self._stack = None
 
     def _train_refusal(self):
         """Why this layer does not train here, or None: the reference's callers train with fixed k and temperature 1."""

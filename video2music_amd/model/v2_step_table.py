@@ -53,12 +53,18 @@ def build_step_table(self, memory, S):
 
     cache = self.__dict__.setdefault("_pack_cache", {})
 
-    def cached(ident, version, build):
-        """One entry per identity (storage pointers + role); a new parameter version (load_state_dict, an optimiser step
-        followed by eval) REPLACES the entry, so stale packed copies do not stay resident."""
-        hit = cache.get(ident)
-        if hit is None or hit[0] != version:
-            cache[ident] = hit = (version, build())
+    def cached(role, srcs, build):
+        """One entry per ROLE (which table of which layer), whatever tensors currently fill it.  The entry keeps the (storage pointer,
+        version) pairs of its sources; any difference -- a new parameter version (load_state_dict, an optimiser step followed by
+        eval) or other storage in that place (`p.data = t`, `load_state_dict(assign=True)`, `.to()`) -- REPLACES it, so stale packed
+        copies do not stay resident and storage that comes back later (an EMA swap: `p.data = shadow` ... `p.data = backup` ...
+        `p.data = shadow` with the shadow updated in between, which no version counter of `p` sees) is packed again -- provided this
+        table was built at least once while the other storage was attached, or a version moved in between: a swap the step never
+        ran under looks like no change at all."""
+        sig = tuple((t.data_ptr(), t._version) for t in srcs)
+        hit = cache.get(role)
+        if hit is None or hit[0] != sig:
+            cache[role] = hit = (sig, build())
         return hit[1]
 
     def pack_now(w, rows=None):
@@ -68,32 +74,31 @@ def build_step_table(self, memory, S):
         _lib.call("amt_pack_weight_fwd", _lib.ptr(src), _lib.ptr(out), N, K, _lib.stream_ptr())
         return out
 
-    def packed(w, rows=None):
+    def packed(role, w, rows=None):
         """Weight (N, K) [or its first `rows` rows] in the skinny GEMM's tile order; packed once per parameter version."""
         w = w.detach()
-        return cached((w.data_ptr(), rows), w._version, lambda: pack_now(w, rows))
+        return cached(("packed", role, rows), (w,), lambda: pack_now(w, rows))
 
-    def packed_experts(experts, name):
+    def packed_experts(role, experts, name):
         # (the per-expert packed pieces are temporaries: only the concatenation stays resident)
         lins = [expert_parts(e)[name] for e in experts]
-        return cached(tuple(l.weight.data_ptr() for l in lins) + (name,), tuple(l.weight._version for l in lins),
-                      lambda: torch.cat([pack_now(l.weight) for l in lins]))
+        return cached(("experts", role, name), [l.weight for l in lins], lambda: torch.cat([pack_now(l.weight) for l in lins]))
 
     def nbias(n):       # a norm's bias; None (RMSNorm) selects the RMS form inside the step
         return getattr(n, "bias", None)
 
     for t in (self._PR, self._PA, self._wkey, self.Linear_chord.bias, self._rope_cache, self.transformer.decoder.norm.weight,
-              nbias(self.transformer.decoder.norm), packed(self.Wout.weight), self.Wout.bias,
+              nbias(self.transformer.decoder.norm), packed("Wout", self.Wout.weight), self.Wout.bias,
               torch.tensor([0, 1], device=dev, dtype=torch.int32), self._pe_chord if self._learned_pos else None):
         add(t)
     from .moe import GLUExpert, SiLUExpert, _stack, expert_dff, expert_parts
     dff, widths = None, set()
 
-    def add_expert(e):
+    def add_expert(role, e):
         """linear1 w, b (None for a SiLUExpert), gate w, b, linear2 w, b -- packed weights."""
         q = expert_parts(e)
         for name in ("linear1", "gate", "linear2"):
-            add(None if q[name] is None else packed(q[name].weight))
+            add(None if q[name] is None else packed((role, name), q[name].weight))
             add(None if q[name] is None else q[name].bias)
 
     # the one-call step streams K/V with the decode-attention kernel: head-major caches (H, rows, hd)
@@ -104,8 +109,9 @@ def build_step_table(self, memory, S):
     layers = list(self.transformer.decoder.layers)
     for li, (lyr, (kc, vc), (kx, vx)) in enumerate(zip(layers, st["self_hm"], st["cross_hm"])):
         sa, ca = lyr.self_attn, lyr.cross_attn
-        for t in (packed(sa.in_proj_weight), sa.in_proj_bias, packed(sa.out_proj.weight), sa.out_proj.bias, lyr.norm1.weight, nbias(lyr.norm1),
-                  packed(ca.in_proj_weight, rows=E), ca.in_proj_bias, packed(ca.out_proj.weight), ca.out_proj.bias, lyr.norm2.weight,
+        for t in (packed((li, "sa_in"), sa.in_proj_weight), sa.in_proj_bias, packed((li, "sa_out"), sa.out_proj.weight), sa.out_proj.bias,
+                  lyr.norm1.weight, nbias(lyr.norm1), packed((li, "ca_in"), ca.in_proj_weight, rows=E), ca.in_proj_bias,
+                  packed((li, "ca_out"), ca.out_proj.weight), ca.out_proj.bias, lyr.norm2.weight,
                   nbias(lyr.norm2), lyr.norm3.weight, nbias(lyr.norm3), kc, vc, kx, vx):
             add(t)
         ff = lyr.ff
@@ -137,13 +143,12 @@ def build_step_table(self, memory, S):
                     out += [None, None]
                 return out
 
-            return cached(tuple((l.weight.data_ptr(), l.bias.data_ptr()) for l in srcs) + ("stacked", with_down),
-                          tuple((l.weight._version, l.bias._version) for l in srcs), build)
+            return cached(("stacked", li, with_down), [t for l in srcs for t in (l.weight, l.bias)], build)
 
         if isinstance(ff, (GLUExpert, SiLUExpert)):
             layer_dff = expert_dff(ff)
             add(None), add(None)
-            add_expert(ff)
+            add_expert((li, "ff"), ff)
             for _ in range(6):
                 add(None)
             for t in stacked([ff], False):
@@ -161,10 +166,10 @@ def build_step_table(self, memory, S):
                 if expert_parts(ff.experts[0])[name] is None:
                     add(None), add(None)
                 else:
-                    add(packed_experts(ff.experts, name))
+                    add(packed_experts(li, ff.experts, name))
                     add(_stack(ff.experts, name, "bias"))
             if ff.shared:
-                add_expert(ff.shared_expert)
+                add_expert((li, "shared"), ff.shared_expert)
             else:
                 for _ in range(6):
                     add(None)
@@ -187,7 +192,7 @@ def build_step_table(self, memory, S):
                 return [pack_now(P2), ops.linear(bo.view(1, E).contiguous(), Wqg).view(E).contiguous(),
                         Wqg.sum(dim=1).contiguous(), (ops.linear(beta.view(1, E).contiguous(), Wq.contiguous()).view(E) + bq).contiguous()]
 
-            for t in cached(tuple(t.data_ptr() for t in srcs) + ("g1fold",), tuple(t._version for t in srcs), build_fold):
+            for t in cached(("g1fold", li), srcs, build_fold):
                 add(t)
         else:
             for _ in range(4):
@@ -233,7 +238,7 @@ def build_step_table(self, memory, S):
                 return out + [pack_now(P3), ops.linear(row(b2), Wq).view(-1).contiguous(), Wq.sum(dim=1).contiguous(),
                               (ops.linear(row(lyr.norm3.bias), Wn.contiguous()).view(-1) + bn).contiguous()]
 
-            for t in cached(tuple(t.data_ptr() for t in srcs) + ("ffnfold", fold_mode), tuple(t._version for t in srcs), build_ffn_fold):
+            for t in cached(("ffnfold", li, fold_mode), srcs, build_ffn_fold):
                 add(t)
         else:
             for _ in range(8):

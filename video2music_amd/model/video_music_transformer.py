@@ -236,6 +236,14 @@ class VideoMusicTransformer(nn.Module):
             self._weights_sig = sig
         return self._handle
 
+    def drop_derived(self):
+        """Forgets the weight signature of the library handle: the next forward / generate uploads every tensor of the state dict
+        again and `amt_finalize` rebuilds every packed, folded and table copy from them (in place: the captured decode graphs keep
+        pointing at the rebuilt tables).  Changes torch can see (in-place operations on the parameter, optimiser steps,
+        `load_state_dict`, `p.data = t`, `.to()`) are followed without it; a write through `p.data` or through a tensor that
+        `p.data` aliases bumps no version counter and needs this call ("When weights change")."""
+        self._weights_sig = None
+
     def __del__(self):
         h = getattr(self, "_handle", None)
         if h is not None:

@@ -217,6 +217,17 @@ class VideoRegression(nn.Module):
                 self._Wx.append(t)
             self._derived_sig = sig
 
+    def drop_derived(self):
+        """Forgets every copy derived from the parameters (the padded `_Win` / `_Wdt` / `_Wx`, the packed heads, the stacked
+        recurrent weights, the mixture layers' expert stacks): the next call rebuilds them.  Needed only after a write torch's
+        version counters do not see (`p.data.mul_(..)`, a write through a tensor that `p.data` aliases); INTEGRATION.md, "When
+        weights change"."""
+        from .moe import drop_derived_below
+        self._derived_sig = None
+        self.__dict__.pop("_heads_cache", None)
+        self.__dict__.pop("_rnn_cache", None)
+        drop_derived_below(self)
+
     def packed_heads(self):
         """Both heads as the one packed, transposed tensor `ops.reg_metrics` reads (`ops.pack_reg_heads`); rebuilt when a head
         parameter changes."""

@@ -156,6 +156,19 @@ class VideoMusicTransformer_V2(nn.Module):
                               else torch.zeros(self._max_dec, d, device=dev))
             self._derived_sig = sig
 
+    def drop_derived(self):
+        """Forgets every copy derived from the parameters -- the Linear_chord / Linear_vis / positional tables of `_derived`, the
+        packed, stacked and folded weights of the cached decode step, the mixture layers' expert stacks, V3's lambda scalars --
+        so that the next call rebuilds them from the parameters as they are.  Changes torch can see (in-place operations on the
+        parameter, optimiser steps, `load_state_dict`, `p.data = t`, `.to()`) are followed without it; a write through `p.data` or
+        through a tensor that `p.data` aliases bumps no version counter and needs this call ("When weights change").
+        Step graphs are captured per `generate` call and hold no table across calls."""
+        from .moe import drop_derived_below
+        self._derived_sig = None
+        self._wvis_cache = {}
+        self.__dict__.pop("_pack_cache", None)
+        drop_derived_below(self)
+
     def _wvis(self, sem_dim):
         """Linear_vis.weight laid out for the rows of `concat_features` ([semantic | scene | motion | emotion], zero-padded
         to a multiple of 32 columns).  With scene_embed the reference leaves the scene column out of the features (:463-465):

@@ -38,6 +38,10 @@ class _DiffAttnParams(nn.Module):
             self._lam_sig = sig
         return self._lam
 
+    def drop_derived(self):
+        """Forgets the cached lambda scalar (see `VideoMusicTransformer_V2.drop_derived`)."""
+        self._lam_sig = None
+
 
 class VideoMusicTransformer_V3(VideoMusicTransformer_V2):
     """Reference ``VideoMusicTransformer_V3`` (model/video_music_transformer.py:611-909), versions '3.0', '3.1', '3.2', eval
