@@ -303,23 +303,32 @@ class _MoEBase(nn.Module):
         """Routing temperature of this forward: 1 unless the layer steps a temperature scheduler in eval mode (SharedMoELayer)."""
         return 1.0
 
-    def _stacked_expert_weights(self):
+    def _stacked_expert_weights(self, publish=True):
         """(n_exp, ...) contiguous copies of the experts' tensors for the grouped GEMMs, rebuilt only when a
-        parameter changed (the library takes one base pointer + a per-expert stride)."""
+        parameter changed (the library takes one base pointer + a per-expert stride).  publish=False (the training step, whose
+        parameters change with every step and which consumes the stacks on the stream that built them): a stack that is not cached is
+        built for this call alone, without the wait that publishing one costs."""
         sig = tuple((p.data_ptr(), p._version) for e in self.experts for p in e.parameters())
-        if getattr(self, "_stack_sig", None) != sig:
-            self._stack = (_stack(self.experts, "linear1", "weight"), _stack(self.experts, "linear1", "bias"),
-                           _stack(self.experts, "gate", "weight"), _stack(self.experts, "gate", "bias"),
-                           _stack(self.experts, "linear2", "weight"), _stack(self.experts, "linear2", "bias"))
-            self._stack_sig = sig
-        return self._stack
+        build = lambda: (_stack(self.experts, "linear1", "weight"), _stack(self.experts, "linear1", "bias"),
+                         _stack(self.experts, "gate", "weight"), _stack(self.experts, "gate", "bias"),
+                         _stack(self.experts, "linear2", "weight"), _stack(self.experts, "linear2", "bias"))
+        hit = getattr(self, "_stack_hit", None)
+        if hit is None or hit[0] != sig:
+            if not publish:
+                return build()
+            with _lib.DERIVED_LOCK:
+                hit = getattr(self, "_stack_hit", None)
+                if hit is None or hit[0] != sig:
+                    stack = build()
+                    _lib.derived_ready()            # stacked on this stream, read from any: finished before it is published
+                    self._stack_hit = hit = (sig, stack)
+        return hit[1]
 
     def drop_derived(self):
         """Forgets every copy derived from the parameters (the stacked expert tensors): the next forward rebuilds them.  To be called
         after a write torch's version counters do not see (`p.data.mul_(..)`, a write through a tensor that `p.data` aliases);
         INTEGRATION.md, "When weights change"."""
-        self._stack_sig = None
-        self._stack = None
+        self._stack_hit = None
 
     def _train_refusal(self):
         """Why this layer does not train here, or None: the reference's callers train with fixed k and temperature 1."""
@@ -371,7 +380,7 @@ class _MoEBase(nn.Module):
 
         masks = [mask((n_tok * k, raw), p_in), mask((n_tok * k, d), p_out), mask((n_tok, raw), p_shared)]
         shared = expert_tensors(self.shared_expert) if self.shared else None
-        plan = {"k": k, "n_exp": self.n_experts, "dff_raw": raw, "masks": tuple(masks), "stacked": self._stacked_expert_weights(),
+        plan = {"k": k, "n_exp": self.n_experts, "dff_raw": raw, "masks": tuple(masks), "stacked": self._stacked_expert_weights(publish=False),
                 "shared": shared}
         own = lambda e: [q for name in ("linear1", "gate", "linear2") for lin in [expert_parts(e)[name]] if lin is not None
                          for q in (lin.weight, lin.bias)]

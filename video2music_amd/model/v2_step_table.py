@@ -52,6 +52,7 @@ def build_step_table(self, memory, S):
             ptrs.append(t.data_ptr())
 
     cache = self.__dict__.setdefault("_pack_cache", {})
+    built = {}
 
     def cached(role, srcs, build):
         """One entry per ROLE (which table of which layer), whatever tensors currently fill it.  The entry keeps the (storage pointer,
@@ -62,9 +63,9 @@ def build_step_table(self, memory, S):
         table was built at least once while the other storage was attached, or a version moved in between: a swap the step never
         ran under looks like no change at all."""
         sig = tuple((t.data_ptr(), t._version) for t in srcs)
-        hit = cache.get(role)
+        hit = built.get(role) or cache.get(role)
         if hit is None or hit[0] != sig:
-            cache[role] = hit = (sig, build())
+            built[role] = hit = (sig, build())          # this table points into it now; other callers see it once it is finished (below)
         return hit[1]
 
     def pack_now(w, rows=None):
@@ -245,6 +246,11 @@ def build_step_table(self, memory, S):
                 add(None)
         widths.add(layer_dff)
         dff = layer_dff
+    if built:
+        # the new entries were packed on this thread's current stream; the next table that takes them from the cache may be built
+        # by another host thread on its own stream (`generate` of several clips at once), which nothing orders behind this one
+        _lib.derived_ready()
+        cache.update(built)
     st["tab"] = (C.c_void_p * len(ptrs))(*ptrs)
     st["keep"] = keep
     st["dff"] = dff

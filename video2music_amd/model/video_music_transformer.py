@@ -207,6 +207,10 @@ class VideoMusicTransformer(nn.Module):
         sig = tuple((k, v.data_ptr(), v._version) for k, v in self.state_dict().items()) + (bool(IS_SEPERATED),)
         if sig != self._weights_sig:
             torch.cuda.synchronize(dev)
+            # amt_load_weight is a blocking copy on the null stream, which torch's side streams do not wait for and which does not wait
+            # for them: every temporary below is produced first, on the current stream, and that stream is synchronised once before the
+            # first copy reads one
+            upload = []
             for name, t in self.state_dict().items():
                 t = t.detach().to(torch.float32).contiguous()
                 if name == "Linear_vis.weight" and self.scene_embed:
@@ -224,14 +228,16 @@ class VideoMusicTransformer(nn.Module):
                         t = self.chord_embedding_model.weight.detach().to(torch.float32).contiguous()
                     elif name == "embedding_attr.weight":
                         t = torch.zeros_like(t)
-                shape = (C.c_int64 * t.dim())(*t.shape)
-                _lib.call("amt_load_weight", self._handle, name.encode(), _lib.ptr(t), t.dim(), shape)
+                upload.append((name, t))
             if not self.rpr:
                 zero = torch.zeros(self.max_seq_chord, self.d_model // self.nhead, device=dev)
-                shape = (C.c_int64 * 2)(*zero.shape)
-                for i in range(self.nlayers):
-                    _lib.call("amt_load_weight", self._handle, f"transformer.decoder.layers.{i}.self_attn.Er".encode(), _lib.ptr(zero), 2, shape)
+                upload += [(f"transformer.decoder.layers.{i}.self_attn.Er", zero) for i in range(self.nlayers)]
                 self._zero_er = zero
+            torch.cuda.current_stream().synchronize()
+            for name, t in upload:
+                shape = (C.c_int64 * t.dim())(*t.shape)
+                _lib.call("amt_load_weight", self._handle, name.encode(), _lib.ptr(t), t.dim(), shape)
+            del upload
             _lib.call("amt_finalize", self._handle)
             self._weights_sig = sig
         return self._handle
@@ -510,7 +516,7 @@ class VideoMusicTransformer(nn.Module):
             else:                              # Categorical(probs).sample(), :1104-1105
                 gen[:, cur] = torch.multinomial(probs, 1).reshape(())
             _lib.call("amt_generate_commit", h, _lib.ptr(gen[0, cur:cur + 1].contiguous()), st)
-        torch.cuda.synchronize(dev)
+        torch.cuda.current_stream().synchronize()
         return gen
 
     def _debug_set_skip(self, mask):

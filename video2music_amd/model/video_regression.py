@@ -30,7 +30,7 @@ import math
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import _lib, ops
 
 INSTRUMENT_SIZE = 40            # utilities/constants.py:84
 
@@ -186,35 +186,34 @@ class VideoRegression(nn.Module):
     # zero-padded copies of the weights whose K (or row count) does not fit the GEMM's steps (rebuilt when they change)
     def _derived(self):
         if self._rnn:                                   # only the in-projection needs a padded copy
-            w = self.in_proj[0].weight
-            sig = (w.data_ptr(), w._version)
-            if sig != self._derived_sig:
-                self._Fpad = (self.total_vf_dim + 31) // 32 * 32
-                self._Win = torch.zeros(self.d_model, self._Fpad, device=w.device)
-                self._Win[:, :self.total_vf_dim] = w.detach()
-                self._derived_sig = sig
-            return
-        blocks = ([m for l in self.model.layers for m in (l.mamba_forward, l.mamba_backward)] if self._bidirectional
-                  else [(l[0] if isinstance(l, nn.Sequential) else l).mixer for l in self.model.layers])
-        ws = [self.in_proj[0].weight] + [m.dt_proj.weight for m in blocks]
-        xs = [m.x_proj.weight for m in blocks]
+            ws, xs = [self.in_proj[0].weight], []
+        else:
+            blocks = ([m for l in self.model.layers for m in (l.mamba_forward, l.mamba_backward)] if self._bidirectional
+                      else [(l[0] if isinstance(l, nn.Sequential) else l).mixer for l in self.model.layers])
+            ws = [self.in_proj[0].weight] + [m.dt_proj.weight for m in blocks]
+            xs = [m.x_proj.weight for m in blocks]
         sig = tuple((w.data_ptr(), w._version) for w in ws + xs)
-        if sig != self._derived_sig:
+        if sig == self._derived_sig:
+            return
+        with _lib.DERIVED_LOCK:
+            if sig == self._derived_sig:
+                return
             dev = ws[0].device
             F = self.total_vf_dim
-            self._Fpad = (F + 31) // 32 * 32
-            self._Win = torch.zeros(self.d_model, self._Fpad, device=dev)
-            self._Win[:, :F] = ws[0].detach()
-            self._Wdt = []
+            Fpad = (F + 31) // 32 * 32
+            Win = torch.zeros(self.d_model, Fpad, device=dev)
+            Win[:, :F] = ws[0].detach()
+            Wdt, Wx = [], []
             for w in ws[1:]:                       # (d_inner, dt_rank) -> (d_inner, 32): the GEMM reads dt | B | C[:..] x zeros
                 t = torch.zeros(w.shape[0], 32, device=dev)
                 t[:, :w.shape[1]] = w.detach()
-                self._Wdt.append(t)
-            self._Wx = []
+                Wdt.append(t)
             for w in xs:                           # (dt_rank + 2N, d_inner): rows padded to a multiple of 4 (row stride of dbc)
                 t = torch.zeros((w.shape[0] + 3) // 4 * 4, w.shape[1], device=dev)
                 t[:w.shape[0]] = w.detach()
-                self._Wx.append(t)
+                Wx.append(t)
+            _lib.derived_ready(self._train_path())  # padded on this stream, read from any: finished before they are published
+            self._Fpad, self._Win, self._Wdt, self._Wx = Fpad, Win, Wdt, Wx
             self._derived_sig = sig
 
     def drop_derived(self):
@@ -233,9 +232,14 @@ class VideoRegression(nn.Module):
         parameter changes."""
         ps = (self.regressor.weight, self.regressor.bias, self.classifier[0].weight, self.classifier[0].bias)
         sig = tuple((q.data_ptr(), q._version) for q in ps)
-        cache = self.__dict__.setdefault("_heads_cache", (None, None))
+        cache = self.__dict__.get("_heads_cache", (None, None))
         if cache[0] != sig:
-            cache = self.__dict__["_heads_cache"] = (sig, ops.pack_reg_heads(*ps))
+            with _lib.DERIVED_LOCK:
+                cache = self.__dict__.get("_heads_cache", (None, None))
+                if cache[0] != sig:
+                    packed = ops.pack_reg_heads(*ps)
+                    _lib.derived_ready()           # packed on this stream, read from any: finished before it is published
+                    cache = self.__dict__["_heads_cache"] = (sig, packed)
         return cache[1]
 
     def _conv7_silu(self, x, B, S):
@@ -264,10 +268,16 @@ class VideoRegression(nn.Module):
         ps = [getattr(self._rnn_mod, n) for n in names]
         sig = tuple((q.data_ptr(), q._version) for q in ps)
         cache = self.__dict__.setdefault("_rnn_cache", {})
-        if cache.get(l, (None,))[0] != sig:
-            per = [[q.detach() for q in ps[4 * r:4 * r + 4]] for r in range(self._dirs)]
-            cache[l] = (sig, tuple(torch.cat([per[r][k] for r in range(self._dirs)]).contiguous() for k in range(4)))
-        return cache[l][1]
+        hit = cache.get(l, (None,))
+        if hit[0] != sig:
+            with _lib.DERIVED_LOCK:
+                hit = cache.get(l, (None,))
+                if hit[0] != sig:
+                    per = [[q.detach() for q in ps[4 * r:4 * r + 4]] for r in range(self._dirs)]
+                    stacked = tuple(torch.cat([per[r][k] for r in range(self._dirs)]).contiguous() for k in range(4))
+                    _lib.derived_ready(self._train_path())          # stacked on this stream, read from any: finished first
+                    cache[l] = hit = (sig, stacked)
+        return hit[1]
 
     def _mamba(self, x, m, wdt, wx, B, L, resid, reverse):
         """MambaBlock.forward on rows x (B*L, d) + the layer's residual add (out_proj epilogue)."""

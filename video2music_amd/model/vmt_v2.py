@@ -138,22 +138,27 @@ class VideoMusicTransformer_V2(nn.Module):
         if self._learned_pos:
             srcs += [self.positional_embedding.weight, self.positional_embedding_video.weight]
         sig = tuple((q.data_ptr(), q._version) for q in srcs)
-        if sig != self._derived_sig:
+        if sig == self._derived_sig:
+            return
+        with _lib.DERIVED_LOCK:
+            if sig == self._derived_sig:
+                return
             d, F = self.d_model, self.total_vf_dim
             Wc = self.Linear_chord.weight.detach()
             Wc_main = Wc[:, :d].contiguous()
-            self._wkey = Wc[:, d].contiguous()
+            wkey = Wc[:, d].contiguous()
             if self.chord_embed:
                 # x = chord_embedding_model(x) (:431-432): one table indexed by the chord id; the attr slot adds a zero row
-                self._PR = ops.linear(self.chord_embedding_model.weight.detach().contiguous(), Wc_main)
-                self._PA = torch.zeros(CHORD_ATTR_SIZE, d, device=dev)
+                PR = ops.linear(self.chord_embedding_model.weight.detach().contiguous(), Wc_main)
+                PA = torch.zeros(CHORD_ATTR_SIZE, d, device=dev)
             else:
-                self._PR = ops.linear(self.embedding_root.weight.detach().contiguous(), Wc_main)
-                self._PA = ops.linear(self.embedding_attr.weight.detach().contiguous(), Wc_main)
-            self._wvis_cache = {}
+                PR = ops.linear(self.embedding_root.weight.detach().contiguous(), Wc_main)
+                PA = ops.linear(self.embedding_attr.weight.detach().contiguous(), Wc_main)
             # positional rows added to the chord embedding: the learned table of version '2.0' (:497-503) or none
-            self._pe_chord = (self.positional_embedding.weight.detach().contiguous() if self._learned_pos
-                              else torch.zeros(self._max_dec, d, device=dev))
+            pe_chord = (self.positional_embedding.weight.detach().contiguous() if self._learned_pos
+                        else torch.zeros(self._max_dec, d, device=dev))
+            _lib.derived_ready()                    # built on this stream, read from any: finished before it is published
+            self._wkey, self._PR, self._PA, self._pe_chord, self._wvis_cache = wkey, PR, PA, pe_chord, {}
             self._derived_sig = sig
 
     def drop_derived(self):
@@ -173,18 +178,24 @@ class VideoMusicTransformer_V2(nn.Module):
         """Linear_vis.weight laid out for the rows of `concat_features` ([semantic | scene | motion | emotion], zero-padded
         to a multiple of 32 columns).  With scene_embed the reference leaves the scene column out of the features (:463-465):
         the weight then gets a zero column at that place, so the same rows serve."""
-        if sem_dim not in self._wvis_cache:
-            W = self.Linear_vis.weight.detach()
-            d, F = W.shape
-            cols = F + 1 if self.scene_embed else F
-            Fpad = (cols + 31) // 32 * 32
-            Wv = torch.zeros(d, Fpad, device=W.device)
-            if self.scene_embed:
-                Wv[:, :sem_dim], Wv[:, sem_dim + 1:cols] = W[:, :sem_dim], W[:, sem_dim:]
-            else:
-                Wv[:, :F] = W
-            self._wvis_cache[sem_dim] = (Wv, Fpad)
-        return self._wvis_cache[sem_dim]
+        cache = self._wvis_cache
+        hit = cache.get(sem_dim)
+        if hit is None:
+            with _lib.DERIVED_LOCK:
+                hit = cache.get(sem_dim)
+                if hit is None:
+                    W = self.Linear_vis.weight.detach()
+                    d, F = W.shape
+                    cols = F + 1 if self.scene_embed else F
+                    Fpad = (cols + 31) // 32 * 32
+                    Wv = torch.zeros(d, Fpad, device=W.device)
+                    if self.scene_embed:
+                        Wv[:, :sem_dim], Wv[:, sem_dim + 1:cols] = W[:, :sem_dim], W[:, sem_dim:]
+                    else:
+                        Wv[:, :F] = W
+                    _lib.derived_ready()
+                    cache[sem_dim] = hit = (Wv, Fpad)
+        return hit
 
     def _attention(self, xq, xkv, a, Lq, Lk, B, causal, resid):
         """xq (Lq*B, E), xkv (Lk*B, E) seq-first rows; returns out-proj(attn) + resid."""
