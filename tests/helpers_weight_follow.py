@@ -604,7 +604,7 @@ STEP_FOLDS = {
 
 def step_folds(m):
     """(layers with a g1fold entry, (layer, mode) of the ffnfold entries) in the model's step-table cache."""
-    roles = list(m.__dict__.get("_pack_cache", {}))
+    roles = [r for r in m._tables.roles() if isinstance(r, tuple)]
     return ({r[1] for r in roles if r[0] == "g1fold"}, {(r[1], r[2]) for r in roles if r[0] == "ffnfold"})
 
 

@@ -12,26 +12,31 @@ import torch
 import torch.nn as nn
 
 from tests import helpers_weight_follow as W
+from video2music_amd._derived import Derived
 
 
 # ---- the harness bites -----------------------------------------------------------------------------------------------------------------
 class Toy(nn.Module):
-    """y = x [2 w | b]^T through a derived copy `_wb`, rebuilt by the rule `variant` names."""
+    """y = x [2 w | b]^T through a derived copy `_wb`, rebuilt by the rule `variant` names: "correct" is the package's own
+    `Derived.get`, the three others are hand-written wrong stand-ins."""
 
     def __init__(self, variant="correct"):
         super().__init__()
         self.variant = variant
         self.w, self.b = nn.Parameter(torch.zeros(4, 3)), nn.Parameter(torch.zeros(4))
-        self._sig, self._wb, self._by_identity = None, None, {}
+        self._sig, self._wb, self._by_identity, self._tables = None, None, {}, Derived()
 
     def drop_derived(self):
         self._sig, self._by_identity = None, {}
+        self._tables.drop()
 
     def _build(self):
         return torch.cat([2.0 * self.w.detach(), self.b.detach().unsqueeze(1)], dim=1)
 
     def derived(self):
         srcs = (self.w,) if self.variant == "missing_source" else (self.w, self.b)
+        if self.variant == "correct":
+            return self._tables.get("wb", srcs, self._build)
         if self.variant == "per_identity":              # one entry per identity, replaced only when the version differs
             ident, ver = tuple(t.data_ptr() for t in srcs), tuple(t._version for t in srcs)
             hit = self._by_identity.get(ident)

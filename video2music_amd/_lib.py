@@ -6,7 +6,6 @@ g; g.build()"`` or ``video2music_amd/csrc/build.sh``.
 """
 import ctypes as C
 import os
-import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # AMT_LIB: an alternate build of the same library (tools/ab_build.sh: A/B kernel experiments on one box); default = the in-tree build
@@ -206,24 +205,6 @@ def ptr(t):
         return None
     assert t.is_contiguous(), "libamt_hip takes contiguous tensors"
     return C.c_void_p(t.data_ptr())
-
-
-DERIVED_LOCK = threading.RLock()
-
-
-def derived_ready(training=False):
-    """Called by every lazily built cache of derived tensors (padded, stacked, packed or folded copies of parameters) between building an
-    entry and publishing it, under DERIVED_LOCK: the build was enqueued on the calling thread's current stream, and the next reader may
-    be on another stream (another host thread sharing the module, or this thread after `with torch.cuda.stream(..)`), which nothing
-    orders behind it.  A reader only ever reads parameters, so torch's stream rules ask no synchronisation of it; the builder therefore
-    finishes the build before anyone can see the entry.  Builds happen once per weight version and never inside a graph capture (the
-    eager warm-up step precedes every capture).  `training`: the call is a training step's.  Its copies are as new as the parameters
-    the optimiser has just written on this stream, and whoever reads those from another stream owes the synchronisation for both, so
-    a training step does not wait (it would, at every step)."""
-    if training:
-        return
-    import torch
-    torch.cuda.current_stream().synchronize()
 
 
 def stream_ptr():

@@ -14,6 +14,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .. import _lib
+from .._derived import HasDerived
 
 
 class _Phases:
@@ -262,14 +263,7 @@ class TemperatureScheduler(nn.Module):
         return self.t
 
 
-def drop_derived_below(module):
-    """`drop_derived()` of every submodule of `module` that has one (mixture layers, differential attentions)."""
-    for sub in module.modules():
-        if sub is not module and hasattr(sub, "drop_derived"):
-            sub.drop_derived()
-
-
-class _MoEBase(nn.Module):
+class _MoEBase(HasDerived, nn.Module):
     shared = False
     ep_group = None
     expert_parallel = False
@@ -308,27 +302,10 @@ class _MoEBase(nn.Module):
         parameter changed (the library takes one base pointer + a per-expert stride).  publish=False (the training step, whose
         parameters change with every step and which consumes the stacks on the stream that built them): a stack that is not cached is
         built for this call alone, without the wait that publishing one costs."""
-        sig = tuple((p.data_ptr(), p._version) for e in self.experts for p in e.parameters())
         build = lambda: (_stack(self.experts, "linear1", "weight"), _stack(self.experts, "linear1", "bias"),
                          _stack(self.experts, "gate", "weight"), _stack(self.experts, "gate", "bias"),
                          _stack(self.experts, "linear2", "weight"), _stack(self.experts, "linear2", "bias"))
-        hit = getattr(self, "_stack_hit", None)
-        if hit is None or hit[0] != sig:
-            if not publish:
-                return build()
-            with _lib.DERIVED_LOCK:
-                hit = getattr(self, "_stack_hit", None)
-                if hit is None or hit[0] != sig:
-                    stack = build()
-                    _lib.derived_ready()            # stacked on this stream, read from any: finished before it is published
-                    self._stack_hit = hit = (sig, stack)
-        return hit[1]
-
-    def drop_derived(self):
-        """Forgets every copy derived from the parameters (the stacked expert tensors): the next forward rebuilds them.  To be called
-        after a write torch's version counters do not see (`p.data.mul_(..)`, a write through a tensor that `p.data` aliases);
-        INTEGRATION.md, "When weights change"."""
-        self._stack_hit = None
+        return self._tables.get("stack", [p for e in self.experts for p in e.parameters()], build, keep=publish)
 
     def _train_refusal(self):
         """Why this layer does not train here, or None: the reference's callers train with fixed k and temperature 1."""

@@ -51,22 +51,8 @@ def build_step_table(self, memory, S):
             keep.append(t)
             ptrs.append(t.data_ptr())
 
-    cache = self.__dict__.setdefault("_pack_cache", {})
-    built = {}
-
-    def cached(role, srcs, build):
-        """One entry per ROLE (which table of which layer), whatever tensors currently fill it.  The entry keeps the (storage pointer,
-        version) pairs of its sources; any difference -- a new parameter version (load_state_dict, an optimiser step followed by
-        eval) or other storage in that place (`p.data = t`, `load_state_dict(assign=True)`, `.to()`) -- REPLACES it, so stale packed
-        copies do not stay resident and storage that comes back later (an EMA swap: `p.data = shadow` ... `p.data = backup` ...
-        `p.data = shadow` with the shadow updated in between, which no version counter of `p` sees) is packed again -- provided this
-        table was built at least once while the other storage was attached, or a version moved in between: a swap the step never
-        ran under looks like no change at all."""
-        sig = tuple((t.data_ptr(), t._version) for t in srcs)
-        hit = built.get(role) or cache.get(role)
-        if hit is None or hit[0] != sig:
-            built[role] = hit = (sig, build())          # this table points into it now; other callers see it once it is finished (below)
-        return hit[1]
+    pending = {}        # this table points into what it builds at once; other callers see it once it is finished (`publish`, below)
+    cached = lambda role, srcs, build: self._tables.get(role, srcs, build, into=pending)
 
     def pack_now(w, rows=None):
         src = (w if rows is None else w[:rows]).detach().contiguous()
@@ -88,9 +74,10 @@ def build_step_table(self, memory, S):
     def nbias(n):       # a norm's bias; None (RMSNorm) selects the RMS form inside the step
         return getattr(n, "bias", None)
 
-    for t in (self._PR, self._PA, self._wkey, self.Linear_chord.bias, self._rope_cache, self.transformer.decoder.norm.weight,
+    wkey, PR, PA, pe_chord = self._derived()
+    for t in (PR, PA, wkey, self.Linear_chord.bias, self._rope_cache, self.transformer.decoder.norm.weight,
               nbias(self.transformer.decoder.norm), packed("Wout", self.Wout.weight), self.Wout.bias,
-              torch.tensor([0, 1], device=dev, dtype=torch.int32), self._pe_chord if self._learned_pos else None):
+              torch.tensor([0, 1], device=dev, dtype=torch.int32), pe_chord if self._learned_pos else None):
         add(t)
     from .moe import GLUExpert, SiLUExpert, _stack, expert_dff, expert_parts
     dff, widths = None, set()
@@ -246,11 +233,7 @@ def build_step_table(self, memory, S):
                 add(None)
         widths.add(layer_dff)
         dff = layer_dff
-    if built:
-        # the new entries were packed on this thread's current stream; the next table that takes them from the cache may be built
-        # by another host thread on its own stream (`generate` of several clips at once), which nothing orders behind this one
-        _lib.derived_ready()
-        cache.update(built)
+    self._tables.publish(pending)     # (the next table may be built by another host thread on its own stream: one wait, then they show)
     st["tab"] = (C.c_void_p * len(ptrs))(*ptrs)
     st["keep"] = keep
     st["dff"] = dff

@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .._derived import signature
 from ..utilities.constants import (CHORD_ATTR_PAD, CHORD_ATTR_SIZE, CHORD_END, CHORD_PAD, CHORD_ROOT_PAD,
                                    CHORD_ROOT_SIZE, CHORD_SIZE, IS_SEPERATED, SCENE_OFFSET_MAX)
 
@@ -204,7 +205,7 @@ class VideoMusicTransformer(nn.Module):
                 _lib.call("amt_set_option", h, b"decode_chain_plain", 1)
             self._handle = h
             self._weights_sig = None
-        sig = tuple((k, v.data_ptr(), v._version) for k, v in self.state_dict().items()) + (bool(IS_SEPERATED),)
+        sig = signature(self.state_dict().values()) + (bool(IS_SEPERATED),)
         if sig != self._weights_sig:
             torch.cuda.synchronize(dev)
             # amt_load_weight is a blocking copy on the null stream, which torch's side streams do not wait for and which does not wait

@@ -30,7 +30,8 @@ import math
 import torch
 import torch.nn as nn
 
-from .. import _lib, ops
+from .. import ops
+from .._derived import HasDerived
 
 INSTRUMENT_SIZE = 40            # utilities/constants.py:84
 
@@ -130,7 +131,7 @@ class _BiMambaEncoderParams(nn.Module):
             self.layers = nn.ModuleList([_BiMambaLayerV0Params(d_model, d_hidden) for _ in range(n_layers)])
 
 
-class VideoRegression(nn.Module):
+class VideoRegression(HasDerived, nn.Module):
     def __init__(self, n_layers=2, d_model=64, d_hidden=1024, dropout=0.1, use_KAN=False, max_sequence_video=300,
                  total_vf_dim=0, regModel="bilstm", scene_embed=False, chord_embed=False):
         super().__init__()
@@ -180,11 +181,11 @@ class VideoRegression(nn.Module):
         width = d_model * (self._dirs if self._rnn else 1)           # bidirectional recurrent heads: 2 d_model (:201-206)
         self.regressor = nn.Linear(width, 2)
         self.classifier = nn.Sequential(nn.Linear(width, INSTRUMENT_SIZE), nn.Sigmoid())
-        self._derived_sig = None
         self.dropout_masks = None       # training state: multipliers to use in place of drawn ones (see _get_feature_train)
 
-    # zero-padded copies of the weights whose K (or row count) does not fit the GEMM's steps (rebuilt when they change)
     def _derived(self):
+        """-> (Fpad, Win, Wdt, Wx): zero-padded copies of the weights whose K (or row count) does not fit the GEMM's steps (rebuilt when
+        they change): the padded feature width, the in-projection padded to it, per Mamba block the padded dt and x projections."""
         if self._rnn:                                   # only the in-projection needs a padded copy
             ws, xs = [self.in_proj[0].weight], []
         else:
@@ -192,12 +193,8 @@ class VideoRegression(nn.Module):
                       else [(l[0] if isinstance(l, nn.Sequential) else l).mixer for l in self.model.layers])
             ws = [self.in_proj[0].weight] + [m.dt_proj.weight for m in blocks]
             xs = [m.x_proj.weight for m in blocks]
-        sig = tuple((w.data_ptr(), w._version) for w in ws + xs)
-        if sig == self._derived_sig:
-            return
-        with _lib.DERIVED_LOCK:
-            if sig == self._derived_sig:
-                return
+
+        def build():
             dev = ws[0].device
             F = self.total_vf_dim
             Fpad = (F + 31) // 32 * 32
@@ -212,35 +209,15 @@ class VideoRegression(nn.Module):
                 t = torch.zeros((w.shape[0] + 3) // 4 * 4, w.shape[1], device=dev)
                 t[:w.shape[0]] = w.detach()
                 Wx.append(t)
-            _lib.derived_ready(self._train_path())  # padded on this stream, read from any: finished before they are published
-            self._Fpad, self._Win, self._Wdt, self._Wx = Fpad, Win, Wdt, Wx
-            self._derived_sig = sig
+            return Fpad, Win, Wdt, Wx
 
-    def drop_derived(self):
-        """Forgets every copy derived from the parameters (the padded `_Win` / `_Wdt` / `_Wx`, the packed heads, the stacked
-        recurrent weights, the mixture layers' expert stacks): the next call rebuilds them.  Needed only after a write torch's
-        version counters do not see (`p.data.mul_(..)`, a write through a tensor that `p.data` aliases); INTEGRATION.md, "When
-        weights change"."""
-        from .moe import drop_derived_below
-        self._derived_sig = None
-        self.__dict__.pop("_heads_cache", None)
-        self.__dict__.pop("_rnn_cache", None)
-        drop_derived_below(self)
+        return self._tables.get("derived", ws + xs, build, wait=not self.training or not self._train_path())
 
     def packed_heads(self):
         """Both heads as the one packed, transposed tensor `ops.reg_metrics` reads (`ops.pack_reg_heads`); rebuilt when a head
         parameter changes."""
         ps = (self.regressor.weight, self.regressor.bias, self.classifier[0].weight, self.classifier[0].bias)
-        sig = tuple((q.data_ptr(), q._version) for q in ps)
-        cache = self.__dict__.get("_heads_cache", (None, None))
-        if cache[0] != sig:
-            with _lib.DERIVED_LOCK:
-                cache = self.__dict__.get("_heads_cache", (None, None))
-                if cache[0] != sig:
-                    packed = ops.pack_reg_heads(*ps)
-                    _lib.derived_ready()           # packed on this stream, read from any: finished before it is published
-                    cache = self.__dict__["_heads_cache"] = (sig, packed)
-        return cache[1]
+        return self._tables.get("heads", ps, lambda: ops.pack_reg_heads(*ps))
 
     def _conv7_silu(self, x, B, S):
         """CNN_GRU's Conv1d(d, d, kernel 7, padding 3) + SiLU over time (:88-91, :97-100) as seven accumulating GEMMs: the clips
@@ -266,18 +243,12 @@ class VideoRegression(nn.Module):
         names = [n + f"_l{l}" + sfx for sfx in (("", "_reverse") if self._dirs == 2 else ("",))
                  for n in ("weight_ih", "bias_ih", "weight_hh", "bias_hh")]
         ps = [getattr(self._rnn_mod, n) for n in names]
-        sig = tuple((q.data_ptr(), q._version) for q in ps)
-        cache = self.__dict__.setdefault("_rnn_cache", {})
-        hit = cache.get(l, (None,))
-        if hit[0] != sig:
-            with _lib.DERIVED_LOCK:
-                hit = cache.get(l, (None,))
-                if hit[0] != sig:
-                    per = [[q.detach() for q in ps[4 * r:4 * r + 4]] for r in range(self._dirs)]
-                    stacked = tuple(torch.cat([per[r][k] for r in range(self._dirs)]).contiguous() for k in range(4))
-                    _lib.derived_ready(self._train_path())          # stacked on this stream, read from any: finished first
-                    cache[l] = hit = (sig, stacked)
-        return hit[1]
+
+        def build():
+            per = [[q.detach() for q in ps[4 * r:4 * r + 4]] for r in range(self._dirs)]
+            return tuple(torch.cat([per[r][k] for r in range(self._dirs)]).contiguous() for k in range(4))
+
+        return self._tables.get(("rnn", l), ps, build, wait=not self.training or not self._train_path())
 
     def _mamba(self, x, m, wdt, wx, B, L, resid, reverse):
         """MambaBlock.forward on rows x (B*L, d) + the layer's residual add (out_proj epilogue)."""
@@ -299,7 +270,7 @@ class VideoRegression(nn.Module):
         return self.training and torch.is_grad_enabled() and self.regModel in ("lstm", "bilstm", "gru", "bigru", "bimamba+", "bimamba",
                                                                                 "moe_bimamba+", "sharedmoe_bimamba+")
 
-    def _get_feature_train(self, vf, B, S):
+    def _get_feature_train(self, vf, B, S, Win, Wdt, Wx):
         """get_feature's recurrent and bidirectional-Mamba branches through the autograd Functions, on the module's own parameters.
         Dropout sits where the reference has it: after in_proj (:169); between the recurrent layers, not after the last (nn.LSTM /
         nn.GRU); in a BiMambaEncoderLayer_V1 (bimamba.py:166-189) after the forward block, after the backward block, inside the FFN
@@ -323,9 +294,9 @@ class VideoRegression(nn.Module):
         drop.given, drop.used = given, used       # a mixture layer takes its own masks from, and leaves them in, the same two lists
 
         lin = self.in_proj[0]
-        x = drop(AG.LinearFn.apply(vf, lin.weight, lin.bias, 0, self._Win), self.in_proj[1].p)
+        x = drop(AG.LinearFn.apply(vf, lin.weight, lin.bias, 0, Win), self.in_proj[1].p)
         if not self._rnn:
-            x = self._bimamba_train(x, B, S, drop)
+            x = self._bimamba_train(x, B, S, drop, Wdt, Wx)
             self.__dict__["last_dropout_masks"] = used
             return x.view(B, S, self.d_model)
         gates = 4 if isinstance(self._rnn_mod, nn.LSTM) else 3
@@ -338,12 +309,12 @@ class VideoRegression(nn.Module):
         self.__dict__["last_dropout_masks"] = used
         return x.view(B, S, self._dirs * self.d_model)
 
-    def _bimamba_train(self, x, B, S, drop):
+    def _bimamba_train(self, x, B, S, drop, Wdt, Wx):
         """The encoder layers of 'bimamba+' (V1) / 'bimamba' (V0) on the graph; `drop(x, p)` applies the next dropout mask."""
         from .. import autograd as AG
 
         def block(x, m, i, reverse, p):          # dropout(MambaBlock(x)) + x, the sum left to the GEMM epilogue where it can be
-            args = (B, S, self._version, reverse, self._Wdt[i], self._Wx[i], m.in_proj.weight, m.in_proj.bias, m.conv1d.weight,
+            args = (B, S, self._version, reverse, Wdt[i], Wx[i], m.in_proj.weight, m.in_proj.bias, m.conv1d.weight,
                     m.conv1d.bias, m.x_proj.weight, m.dt_proj.weight, m.dt_proj.bias, m.A_log, m.D, m.out_proj.weight, m.out_proj.bias)
             if m.dt_rank + 2 * m.d_state < 32:
                 raise ValueError("dt_rank + 2*d_state < 32 is not supported")
@@ -382,7 +353,7 @@ class VideoRegression(nn.Module):
 
     def get_feature(self, feature_semantic_list, feature_scene_offset, feature_motion, feature_emotion):
         """video_regression.py:199-238: (B, S, d_model) encoder output.  Scene offset and motion are not used."""
-        self._derived()
+        Fpad, Win, Wdt, Wx = self._derived()
         dev = self.regressor.weight.device
         if dev.type != "cuda":
             raise RuntimeError("video2music_amd has no CPU path: move the module to the GPU")
@@ -391,10 +362,10 @@ class VideoRegression(nn.Module):
         B, S = sem.shape[0], sem.shape[1]
         if sem.shape[2] + emo.shape[2] != self.total_vf_dim:
             raise ValueError(f"semantic ({sem.shape[2]}) + emotion ({emo.shape[2]}) features != total_vf_dim ({self.total_vf_dim})")
-        vf = ops.concat2(sem.view(B * S, -1), emo.view(B * S, -1), self._Fpad)
+        vf = ops.concat2(sem.view(B * S, -1), emo.view(B * S, -1), Fpad)
         if self._train_path():
-            return self._get_feature_train(vf, B, S)
-        x = ops.linear_ex(vf, self._Win, self.in_proj[0].bias.detach())
+            return self._get_feature_train(vf, B, S, Win, Wdt, Wx)
+        x = ops.linear_ex(vf, Win, self.in_proj[0].bias.detach())
         if self._rnn:                                   # nn.LSTM / nn.GRU (:124-135): per layer and direction, input GEMM + recurrence
             gates, d = (4 if isinstance(self._rnn_mod, nn.LSTM) else 3), self.d_model
             if self._rnn_mod is not self.model:
@@ -409,7 +380,7 @@ class VideoRegression(nn.Module):
             for i, lyr in enumerate(self.model.layers):
                 blk = lyr[0] if isinstance(lyr, nn.Sequential) else lyr
                 h = ops.rmsnorm(x, blk.norm.weight.detach(), eps=blk.norm.eps)
-                x = self._mamba(h, blk.mixer, self._Wdt[i], self._Wx[i], B, S, x, False)
+                x = self._mamba(h, blk.mixer, Wdt[i], Wx[i], B, S, x, False)
                 if blk is not lyr:                      # ResidualMoE: moe_layer(norm(x)) + x (mamba.py:126-128)
                     h = ops.rmsnorm(x, lyr[1].norm.weight.detach(), eps=lyr[1].norm.eps)
                     x = ops.add(lyr[1].moe_layer(h.view(B, S, self.d_model)).reshape(B * S, self.d_model), x)
@@ -419,15 +390,15 @@ class VideoRegression(nn.Module):
             ffn = lambda t, f, resid: ops.linear_ex(ops.linear_ex(t, f[0].weight.detach(), f[0].bias.detach(), act=1),
                                                     f[3].weight.detach(), f[3].bias.detach(), resid=resid)
             for i, lyr in enumerate(self.model.layers):
-                xf = ln(self._mamba(x, lyr.mamba_forward, self._Wdt[2 * i], self._Wx[2 * i], B, S, x, False), lyr.norm1)
+                xf = ln(self._mamba(x, lyr.mamba_forward, Wdt[2 * i], Wx[2 * i], B, S, x, False), lyr.norm1)
                 xf = ln(ffn(xf, lyr.ffn1, xf), lyr.norm2)
-                xb = ln(self._mamba(x, lyr.mamba_backward, self._Wdt[2 * i + 1], self._Wx[2 * i + 1], B, S, x, True), lyr.norm3)
+                xb = ln(self._mamba(x, lyr.mamba_backward, Wdt[2 * i + 1], Wx[2 * i + 1], B, S, x, True), lyr.norm3)
                 x = ln(ffn(xf, lyr.ffn2, xb), lyr.norm4, post=xf)      # ffn2 reads x_f, as written at :94; then x_f + x_b
             return x.view(B, S, self.d_model)
         for i, lyr in enumerate(self.model.layers):
-            xf = ops.layernorm_post(self._mamba(x, lyr.mamba_forward, self._Wdt[2 * i], self._Wx[2 * i], B, S, x, False),
+            xf = ops.layernorm_post(self._mamba(x, lyr.mamba_forward, Wdt[2 * i], Wx[2 * i], B, S, x, False),
                                     lyr.norm1.weight.detach(), lyr.norm1.bias.detach(), eps=lyr.norm1.eps)
-            s = ops.layernorm_post(self._mamba(x, lyr.mamba_backward, self._Wdt[2 * i + 1], self._Wx[2 * i + 1], B, S, x, True),
+            s = ops.layernorm_post(self._mamba(x, lyr.mamba_backward, Wdt[2 * i + 1], Wx[2 * i + 1], B, S, x, True),
                                    lyr.norm2.weight.detach(), lyr.norm2.bias.detach(), post=xf, eps=lyr.norm2.eps)      # x_f + x_b
             if isinstance(lyr.ffn, nn.Sequential):
                 h = ops.linear_ex(s, lyr.ffn[0].weight.detach(), lyr.ffn[0].bias.detach(), act=1)

@@ -2,6 +2,7 @@
 Importable from ``video2music_amd.model.video_music_transformer`` like in the reference; split out for size."""
 import torch.nn as nn
 
+from .._derived import HasDerived
 from ..utilities.constants import CHORD_ATTR_SIZE, CHORD_ROOT_SIZE, CHORD_SIZE, SCENE_OFFSET_MAX
 from .vmt_v2 import VideoMusicTransformer_V2, _TransformerParamsV2
 
@@ -21,7 +22,7 @@ class VideoMusicTransformer_V1(VideoMusicTransformer_V2):
     def __init__(self, version_name="1.1", n_layers=6, num_heads=8, d_model=512, dim_feedforward=1024, dropout=0.1,
                  max_sequence_midi=2048, max_sequence_video=300, max_sequence_chord=300, total_vf_dim=0, rms_norm=False,
                  scene_embed=False, chord_embed=False, dropTokenRate=0.0):
-        nn.Module.__init__(self)
+        HasDerived.__init__(self)
         from .custom_transformer import RMSNorm
         from .moe import GLUExpert, MoELayer, SharedMoELayer, SiLUExpert
         shallow = version_name in ("1.3.3", "1.3.4")
@@ -72,4 +73,3 @@ class VideoMusicTransformer_V1(VideoMusicTransformer_V2):
             self._rope_cache = None
         # the RoPE cache caps the chord sequence at max_sequence_video, the positional table at max_sequence_chord
         self._max_dec = min(max_sequence_video, max_sequence_chord) if self._use_rope else max_sequence_chord
-        self._derived_sig = None

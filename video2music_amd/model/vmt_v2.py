@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .._derived import HasDerived
 from ..utilities.constants import (CHORD_ATTR_PAD, CHORD_ATTR_SIZE, CHORD_END, CHORD_PAD, CHORD_ROOT_PAD, CHORD_ROOT_SIZE, CHORD_SIZE,
                                    SCENE_OFFSET_MAX)
 from .video_music_transformer import _CAPTURE_LOCK, _AttnParams, _Stack, _TransformerParams
@@ -48,7 +49,7 @@ class _TransformerParamsV2(nn.Module):
     generate_square_subsequent_mask = staticmethod(_TransformerParams.generate_square_subsequent_mask)
 
 
-class VideoMusicTransformer_V2(nn.Module):
+class VideoMusicTransformer_V2(HasDerived, nn.Module):
     """Reference ``VideoMusicTransformer_V2`` (model/video_music_transformer.py:316-609), versions '2.2' (generate.py's
     default), '2.1' (same network in eval: its top-k scheduler acts in training only) and '2.0':
     RoPE (cache built for dim=d_model, applied through the raw (H, L, B, hd) view) inside every attention and no additive
@@ -116,7 +117,6 @@ class VideoMusicTransformer_V2(nn.Module):
         # longest chord sequence: the RoPE cache caps it at max_sequence_video (rotate_operation.py:148), the learned
         # table at max_sequence_chord; with neither there is no cap but the caches need a size
         self._max_dec = max_sequence_video if self._use_rope else max_sequence_chord
-        self._derived_sig = None
 
     def _resize_chord_table(self, state_dict, prefix, *_):
         w = state_dict.get(prefix + "chord_embedding_model.weight")
@@ -128,7 +128,7 @@ class VideoMusicTransformer_V2(nn.Module):
 
     # ---- derived tensors (rebuilt when a parameter changes): Linear_chord tables, padded Linear_vis ----
     def _derived(self):
-        from .. import ops
+        """-> (wkey, PR, PA, pe_chord): Linear_chord's key column, its main part times the root / attr (or chord) tables, positional rows."""
         dev = self.Wout.weight.device
         if dev.type != "cuda":
             raise _lib.AmtError("VideoMusicTransformer_V2 runs on an MI355X only; video2music_amd has no CPU fallback")
@@ -137,13 +137,10 @@ class VideoMusicTransformer_V2(nn.Module):
             srcs.append(self.chord_embedding_model.weight)
         if self._learned_pos:
             srcs += [self.positional_embedding.weight, self.positional_embedding_video.weight]
-        sig = tuple((q.data_ptr(), q._version) for q in srcs)
-        if sig == self._derived_sig:
-            return
-        with _lib.DERIVED_LOCK:
-            if sig == self._derived_sig:
-                return
-            d, F = self.d_model, self.total_vf_dim
+
+        def build():
+            from .. import ops
+            d = self.d_model
             Wc = self.Linear_chord.weight.detach()
             Wc_main = Wc[:, :d].contiguous()
             wkey = Wc[:, d].contiguous()
@@ -157,45 +154,27 @@ class VideoMusicTransformer_V2(nn.Module):
             # positional rows added to the chord embedding: the learned table of version '2.0' (:497-503) or none
             pe_chord = (self.positional_embedding.weight.detach().contiguous() if self._learned_pos
                         else torch.zeros(self._max_dec, d, device=dev))
-            _lib.derived_ready()                    # built on this stream, read from any: finished before it is published
-            self._wkey, self._PR, self._PA, self._pe_chord, self._wvis_cache = wkey, PR, PA, pe_chord, {}
-            self._derived_sig = sig
+            return wkey, PR, PA, pe_chord
 
-    def drop_derived(self):
-        """Forgets every copy derived from the parameters -- the Linear_chord / Linear_vis / positional tables of `_derived`, the
-        packed, stacked and folded weights of the cached decode step, the mixture layers' expert stacks, V3's lambda scalars --
-        so that the next call rebuilds them from the parameters as they are.  Changes torch can see (in-place operations on the
-        parameter, optimiser steps, `load_state_dict`, `p.data = t`, `.to()`) are followed without it; a write through `p.data` or
-        through a tensor that `p.data` aliases bumps no version counter and needs this call ("When weights change").
-        Step graphs are captured per `generate` call and hold no table across calls."""
-        from .moe import drop_derived_below
-        self._derived_sig = None
-        self._wvis_cache = {}
-        self.__dict__.pop("_pack_cache", None)
-        drop_derived_below(self)
+        return self._tables.get("derived", srcs, build)
 
     def _wvis(self, sem_dim):
         """Linear_vis.weight laid out for the rows of `concat_features` ([semantic | scene | motion | emotion], zero-padded
         to a multiple of 32 columns).  With scene_embed the reference leaves the scene column out of the features (:463-465):
         the weight then gets a zero column at that place, so the same rows serve."""
-        cache = self._wvis_cache
-        hit = cache.get(sem_dim)
-        if hit is None:
-            with _lib.DERIVED_LOCK:
-                hit = cache.get(sem_dim)
-                if hit is None:
-                    W = self.Linear_vis.weight.detach()
-                    d, F = W.shape
-                    cols = F + 1 if self.scene_embed else F
-                    Fpad = (cols + 31) // 32 * 32
-                    Wv = torch.zeros(d, Fpad, device=W.device)
-                    if self.scene_embed:
-                        Wv[:, :sem_dim], Wv[:, sem_dim + 1:cols] = W[:, :sem_dim], W[:, sem_dim:]
-                    else:
-                        Wv[:, :F] = W
-                    _lib.derived_ready()
-                    cache[sem_dim] = hit = (Wv, Fpad)
-        return hit
+        def build():
+            W = self.Linear_vis.weight.detach()
+            d, F = W.shape
+            cols = F + 1 if self.scene_embed else F
+            Fpad = (cols + 31) // 32 * 32
+            Wv = torch.zeros(d, Fpad, device=W.device)
+            if self.scene_embed:
+                Wv[:, :sem_dim], Wv[:, sem_dim + 1:cols] = W[:, :sem_dim], W[:, sem_dim:]
+            else:
+                Wv[:, :F] = W
+            return Wv, Fpad
+
+        return self._tables.get(("wvis", sem_dim), (self.Linear_vis.weight,), build)
 
     def _attention(self, xq, xkv, a, Lq, Lk, B, causal, resid):
         """xq (Lq*B, E), xkv (Lk*B, E) seq-first rows; returns out-proj(attn) + resid."""
@@ -307,8 +286,9 @@ class VideoMusicTransformer_V2(nn.Module):
             raise ValueError(f"chord sequence longer than the positional table ({self._max_dec}), like in the reference")
         key = feature_key.to(device=dev, dtype=torch.float32).reshape(-1)
         key = key.expand(B).contiguous() if key.numel() == 1 else key.contiguous()
-        xf = ops.chord_embed(x_root.to(dev).long().contiguous(), x_attr.to(dev).long().contiguous(), key, self._PR, self._PA,
-                             self._wkey, self.Linear_chord.bias.detach(), self._pe_chord)
+        wkey, PR, PA, pe_chord = self._derived()
+        xf = ops.chord_embed(x_root.to(dev).long().contiguous(), x_attr.to(dev).long().contiguous(), key, PR, PA,
+                             wkey, self.Linear_chord.bias.detach(), pe_chord)
         t = xf if clips else xf.view(B, L, d).permute(1, 0, 2).contiguous().view(L * B, d)
         self._clip_rows = bool(clips)
         try:
@@ -361,7 +341,8 @@ class VideoMusicTransformer_V2(nn.Module):
         hd = E // H
         scale = 1.0 / math.sqrt(hd)
         strides = (E, hd, E) * 4
-        x = ops.chord_embed(root_t, attr_t, key, self._PR, self._PA, self._wkey, self.Linear_chord.bias.detach(), self._pe_chord[t:t + 1])
+        wkey, PR, PA, pe_chord = self._derived()
+        x = ops.chord_embed(root_t, attr_t, key, PR, PA, wkey, self.Linear_chord.bias.detach(), pe_chord[t:t + 1])
         rope = self._rope_cache
         for lyr, (kc, vc), (kx, vx) in zip(self.transformer.decoder.layers, st["self"], st["cross"]):
             a = lyr.self_attn

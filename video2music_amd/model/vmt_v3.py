@@ -7,10 +7,11 @@ import torch.nn as nn
 
 from ..utilities.constants import (CHORD_ATTR_PAD, CHORD_ATTR_SIZE, CHORD_END, CHORD_PAD, CHORD_ROOT_PAD, CHORD_ROOT_SIZE, CHORD_SIZE,
                                    SCENE_OFFSET_MAX)
+from .._derived import HasDerived
 from .vmt_v2 import VideoMusicTransformer_V2, _TransformerParamsV2
 
 
-class _DiffAttnParams(nn.Module):
+class _DiffAttnParams(HasDerived, nn.Module):
     """Keys of custom_transformer.DifferentialMultiheadAttention (:610-647): bias-free q/k (E -> 2E), v, out projections,
     the four lambda vectors and the sub-layer RMSNorm over head_dim."""
 
@@ -31,16 +32,12 @@ class _DiffAttnParams(nn.Module):
     def lambda_full(self):
         """exp(lq1.lk1) - exp(lq2.lk2) + lambda_init (:818-820); a host scalar, recomputed when a lambda vector changes."""
         ps = (self.lambda_q1, self.lambda_k1, self.lambda_q2, self.lambda_k2)
-        sig = tuple((q.data_ptr(), q._version) for q in ps)
-        if getattr(self, "_lam_sig", None) != sig:
-            q1, k1, q2, k2 = (q.detach().float().cpu() for q in ps)
-            self._lam = float(torch.exp(torch.sum(q1 * k1)) - torch.exp(torch.sum(q2 * k2)) + self.lambda_init)
-            self._lam_sig = sig
-        return self._lam
 
-    def drop_derived(self):
-        """Forgets the cached lambda scalar (see `VideoMusicTransformer_V2.drop_derived`)."""
-        self._lam_sig = None
+        def build():
+            q1, k1, q2, k2 = (q.detach().float().cpu() for q in ps)
+            return float(torch.exp(torch.sum(q1 * k1)) - torch.exp(torch.sum(q2 * k2)) + self.lambda_init)
+
+        return self._tables.get("lambda", ps, build, wait=False)       # (the `.cpu()` has already blocked)
 
 
 class VideoMusicTransformer_V3(VideoMusicTransformer_V2):
@@ -62,7 +59,7 @@ class VideoMusicTransformer_V3(VideoMusicTransformer_V2):
     def __init__(self, version_name="3.0", n_layers=6, num_heads=8, d_model=512, dim_feedforward=1024, dropout=0.1,
                  max_sequence_midi=2048, max_sequence_video=300, max_sequence_chord=300, total_vf_dim=0, rms_norm=False,
                  scene_embed=False, chord_embed=False, dropTokenRate=0.0):
-        nn.Module.__init__(self)
+        HasDerived.__init__(self)
         if version_name not in ("3.0", "3.1", "3.2"):
             raise ValueError("the reference builds an encoder for '3.0', '3.1' and '3.2' only (:672-690)")
         if n_layers < 3:
@@ -108,7 +105,6 @@ class VideoMusicTransformer_V3(VideoMusicTransformer_V2):
         rope = RotaryPositionalEmbeddings(2 * d_model, max_sequence_video)          # dim = 2 d_model (:658)
         self.register_buffer("_rope_cache", rope.cache.clone(), persistent=False)
         self._max_dec = max_sequence_video
-        self._derived_sig = None
 
     def _attention(self, xq, xkv, a, Lq, Lk, B, causal, resid):
         from .. import ops
