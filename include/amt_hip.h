@@ -37,7 +37,7 @@
 #define AMT_HIP_H
 #include <stdint.h>
 
-#define AMT_ABI_VERSION 12   /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
+#define AMT_ABI_VERSION 13   /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
                                 3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights;
                                 4: amt_chord_metrics_fwd;
                                 5: amt_reg_metrics_fwd;
@@ -50,7 +50,8 @@
                                 10: amt_moe_train_scratch_floats, amt_moe_train_fwd, amt_moe_bwd_ws_floats, amt_moe_bwd;
                                 11: amt_moe_wgrad_splits;
                                 12: amt_rope_bwd, amt_rmsnorm_bwd, amt_rmsnorm_bwd_blocks, amt_glu_train_scratch_floats, amt_glu_train_fwd,
-                                    amt_glu_bwd_ws_floats, amt_glu_bwd */
+                                    amt_glu_bwd_ws_floats, amt_glu_bwd;
+                                13: amt_diff_subln_train_fwd, amt_diff_subln_bwd, amt_diff_subln_bwd_blocks, amt_moe_train_fwd_balanced */
 
 #ifdef __cplusplus
 extern "C" {
@@ -352,6 +353,20 @@ int32_t amt_moe_bwd(const float* dout, const float* x, const float* gate_w, cons
                     float* dsw1, float* dsb1, float* dswg, float* dsbg, float* dsw2, float* dsb2,
                     float* ws, int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, int32_t glu,
                     int32_t has_shared, float temperature, void* stream);
+/* amt_moe_train_fwd for SharedMoELayer(balancing=True) in training mode (moe.py:257-279): amt_moe_train_fwd's arguments, then
+ * sel_bias (n_exp), update_rate and bias_delta (n_exp).  The k experts of a token are those with the largest logit + sel_bias[e],
+ * largest first and the lower expert id first among equals; idx keeps that order; wts is the softmax over the RAW logits of those k,
+ * their own maximum subtracted.  Plan, grouped GEMMs, combine and `saved` are amt_moe_train_fwd's, and amt_moe_bwd reads `saved` as it
+ * is: the bias has no gradient.  bias_delta[e] = update_rate (mean(c) - c[e]) with c the plan's integer rows per expert as fp32 and
+ * mean(c) = (sum c) / n_exp in fp32: what the caller adds to its bias buffer (the library keeps no state).  With sel_bias all zero
+ * out / idx_out / w_out / saved are the bits of amt_moe_train_fwd. */
+int32_t amt_moe_train_fwd_balanced(const float* x, const float* gate_w, const float* gate_b,
+                    const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
+                    const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
+                    const float* mask_h, const float* mask_y, const float* mask_hs,
+                    float* out, int32_t* idx_out, float* w_out, float* saved,
+                    int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, void* stream,
+                    const float* sel_bias, float update_rate, float* bias_delta);
 /* Into how many runs amt_moe_bwd cuts each group's 128-row tiles in its weight-gradient products for this shape (1: no second pass):
  * dense = 0 the experts' products over the plan's k n_tok assignments, dense != 0 the one-group products over the tokens (shared
  * expert, router).  The launcher's own plan function, evaluated on the host: no device, no stream; a count, not a status; negative
@@ -696,6 +711,31 @@ int64_t amt_glu_bwd_ws_floats(int32_t n, int32_t d, int32_t dff);
 int32_t amt_glu_bwd(const float* dout, const float* x, const float* saved, const float* w1t, const float* wgt, const float* w2t,
                     const float* mask_h, float* dx, float* dw1, float* db1, float* dwg, float* dbg, float* dw2, float* db2,
                     float* ws, int32_t n, int32_t d, int32_t dff, int32_t dff_raw, int32_t glu, void* stream);
+
+/* Training of the differential-attention tail of the V3 chord models (csrc/diff_subln_train.hip).  Both are fp32 and stateless, use no
+ * floating-point atomic and fix the order of every addition by the shapes alone: the same inputs give the same bits.
+ *
+ * amt_diff_subln_train_fwd: amt_diff_subln_fwd with lambda_full read from one float in DEVICE memory (it is a function of four
+ * parameters, which change with every step; a host scalar would cost a synchronisation per attention per step).  hd <= 128.  For the
+ * same lambda value y is amt_diff_subln_fwd's bits.
+ * amt_diff_subln_bwd: its backward from the forward's own inputs.  dy, o1, o2, d_o1, d_o2: (rows, hd); w, dw: (hd); lambda_dev, dlambda:
+ * one float.  With u = o1 - lambda o2, r = rsqrt(mean_hd(u^2) + eps), xh = u r, g = dy w out_scale:
+ *   du = r (g - xh mean_hd(g xh)),  d_o1 = du,  d_o2 = -lambda du,  dw = out_scale sum over rows of dy xh,  dlambda = -sum over rows and
+ *   columns of du o2
+ * hd 32, 64 or 128 (amt_attn_bwd's head dims); any rows > 0; every pointer but lambda_dev / dlambda 16-byte aligned.  One pass over
+ * dy / o1 / o2 and two stores, hd / 4 lanes per row with 16-byte accesses (8 / 4 / 2 rows per wave), the row's means summed inside its
+ * lane group.  ws: AMT_DIFF_SUBLN_BWD_WS_FLOATS(hd) floats of scratch, 16-byte aligned, used by this call alone until it has finished
+ * (a ticket counter, zeroed by the call, and one [dw | dlambda] slab per workgroup; the last workgroup to finish adds the slabs in
+ * workgroup order).  amt_diff_subln_bwd_blocks(rows, hd) workgroups of 4 waves (the launcher's own rule, min(128, ceil(rows / (16 *
+ * 256 / hd))), evaluated on the host: a count, not a status; negative for rows <= 0 or another hd), workgroup b taking rows
+ * [b per, (b + 1) per) with per = ceil(rows / blocks), wave w of it the groups of 256 / hd rows w, w + 4, ... of that range. */
+#define AMT_DIFF_SUBLN_BWD_WS_FLOATS(hd) (4 + 128 * ((hd) + 4))
+int32_t amt_diff_subln_train_fwd(const float* o1, const float* o2, const float* w, const float* lambda_dev, float* y, int32_t rows,
+                                 int32_t hd, float out_scale, float eps, void* stream);
+int32_t amt_diff_subln_bwd_blocks(int32_t rows, int32_t hd);
+int32_t amt_diff_subln_bwd(const float* dy, const float* o1, const float* o2, const float* w, const float* lambda_dev, float* d_o1,
+                           float* d_o2, float* dw, float* dlambda, float* ws, int32_t rows, int32_t hd, float out_scale, float eps,
+                           void* stream);
 
 /* Training loss of the chord model (reference utilities/run_model_vevo.py:101-119) and its gradient, one launch:
  *   total = lambda CrossEntropyLoss(ignore_index=CHORD_PAD, label_smoothing=smoothing)(y, tgt)

@@ -27,6 +27,12 @@ and what the V1 / V2 chord models add to those (model/vmt_v2.py, `_forward_train
     GluFn             one plain GLUExpert / SiLUExpert with its hidden Dropout    amt_glu_train_fwd; backward: amt_glu_bwd
     RMSNormFn         RMSNorm(x (+ resid)); gradients of both addends             amt_rmsnorm_resid_fwd; backward: amt_rmsnorm_bwd
 
+and what the V3 chord models add (model/vmt_v3.py, `_forward_train`):
+
+    DiffAttentionFn   RMSNorm_hd((A1 - lambda A2) V) (1 - lambda_init), both softmax maps         2 x amt_attn_train_fwd, amt_diff_subln_train_fwd;
+                      backward: amt_diff_subln_bwd, then 2 x amt_attn_bwd
+    MoEFn with plan["sel_bias"]: the balancing router and the routing-bias step                   amt_moe_train_fwd_balanced
+
 Every dense product of the backward runs on `amt_linear_ex_fwd` (y = x w^T, K a multiple of 32): `a b` and `a^T b` go there as
 transposed, zero-padded copies made by torch (`mm_nt`, `mm_tn`).  A bias gradient is the column of ones appended to the right
 operand of its weight's product.  Nothing here uses a floating-point atomic: the same inputs give the same gradients, bit for bit.
@@ -307,6 +313,51 @@ class AttentionFn(torch.autograd.Function):
         return dq, dk, dv, dEr, None, None, None, None, None, None, None
 
 
+def diff_strides(H, Lq, Lk, hd):
+    """The twelve strides of one softmax map of the differential attention (custom_transformer.py:787-789): q / k the rotated
+    (rows, 2 H hd) buffers read through the raw (B, L, 2H, hd) view -- flat row b L + l, the map's heads at head stride 2 hd (the second
+    map's from pointer offset hd) --, v (rows, H hd) through the raw (B, S, H, hd) view, o (B, H, Lq, hd) contiguous."""
+    E = H * hd
+    return (Lq * 2 * E, 2 * hd, 2 * E, Lk * 2 * E, 2 * hd, 2 * E, Lk * E, hd, E, H * Lq * hd, Lq * hd, hd)
+
+
+class DiffAttentionFn(torch.autograd.Function):
+    """apply(q (Lq B 2E values), k (Lk B 2E), v (Lk B E), lam (1,) on the device, w_subln (hd), B, H, Lq, Lk, causal, out_scale, eps) ->
+    y (B, H, Lq, hd) = RMSNorm_hd((A1 - lam A2) V) w_subln out_scale, with A1 / A2 the softmax maps of the even / odd heads of q, k
+    (`diff_strides`; no keep mask: the reference's dropout on the differential map is commented out, custom_transformer.py:819).
+    Saves q, k, v, o1, o2, the two maps' row log-sum-exps, lam and w.  Backward: amt_diff_subln_bwd, then the two amt_attn_bwd calls one
+    after the other on the same stream with one workspace; they fill the even and the odd head columns of one dq and one dk buffer,
+    and dv = dv1 + dv2.  Returns dq, dk, dv, dlam, dw."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, lam, w_subln, B, H, Lq, Lk, causal, out_scale, eps):
+        hd = w_subln.numel()
+        q, k, v = q.contiguous().view(-1), k.contiguous().view(-1), v.contiguous().view(-1)
+        assert q.numel() == B * Lq * 2 * H * hd and k.numel() == B * Lk * 2 * H * hd and v.numel() == B * Lk * H * hd
+        lam, w = lam.detach().contiguous().view(1), w_subln.detach().contiguous()
+        st = diff_strides(H, Lq, Lk, hd)
+        scale = hd ** -0.5
+        new = lambda: torch.empty(B, H, Lq, hd, device=q.device, dtype=torch.float32)
+        o1, lse1 = ops.attention_train(q, k, v, st, B, H, Lq, Lk, hd, causal, scale, new())
+        o2, lse2 = ops.attention_train(q[hd:], k[hd:], v, st, B, H, Lq, Lk, hd, causal, scale, new())
+        y = ops.diff_subln_train(o1, o2, w, lam, out_scale, eps=eps)
+        ctx.args = (st, B, H, Lq, Lk, hd, bool(causal), scale, float(out_scale), float(eps))
+        ctx.save_for_backward(q, k, v, o1, o2, lse1, lse2, lam, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        q, k, v, o1, o2, lse1, lse2, lam, w = ctx.saved_tensors
+        st, B, H, Lq, Lk, hd, causal, scale, out_scale, eps = ctx.args
+        d_o1, d_o2, dw, dlam = ops.diff_subln_bwd(dy.contiguous(), o1, o2, w, lam, out_scale, eps=eps)
+        dq, dk = torch.empty_like(q), torch.empty_like(k)
+        dv1, dv2 = torch.empty_like(v), torch.empty_like(v)
+        ws = ops.attention_bwd_ws(B, H, Lq, Lk, hd, q.device)
+        ops.attention_bwd(d_o1, q, k, v, o1, lse1, st, B, H, Lq, Lk, hd, causal, scale, dq, dk, dv1, ws=ws)
+        ops.attention_bwd(d_o2, q[hd:], k[hd:], v, o2, lse2, st, B, H, Lq, Lk, hd, causal, scale, dq[hd:], dk[hd:], dv2, ws=ws)
+        return dq, dk, ops.add(dv1, dv2), dlam, dw, None, None, None, None, None, None, None
+
+
 class LayerNormFn(torch.autograd.Function):
     """apply(x, resid, w, b, eps) -> LayerNorm(x (+ resid)) * w + b over rows x (rows, dim); resid may be None.  The forward's inputs
     are what is saved; the backward forms the row statistics again and hands the same gradient to both addends."""
@@ -434,7 +485,9 @@ class MoEFn(torch.autograd.Function):
 
     apply(x, plan, gate_w, gate_b, *params): `plan` a dict of what is not differentiated -- k, n_exp, dff_raw, masks = (mask_h, mask_y,
     mask_hs) (multiplier tensors or None, rows by assignment token * k + j), stacked = the experts' (w1, b1, wg, bg, w2, b2) stacked at the
-    padded width, shared = the shared expert's six padded tensors or None; it receives "routing" = (idx, wts).  `params`: per expert its
+    padded width, shared = the shared expert's six padded tensors or None; it receives "routing" = (idx, wts).  With "sel_bias" (n_exp)
+    and "update_rate" in it the forward is amt_moe_train_fwd_balanced and the plan also receives "bias_delta" (n_exp); the backward is
+    the same (the bias has no gradient).  `params`: per expert its
     own parameters in the order linear1.weight, linear1.bias, gate.weight, gate.bias, linear2.weight, linear2.bias (a SiLU expert: its
     first Linear in the gate's place, no linear1), then the shared expert's the same way; they receive the gradients at their own widths.
 
@@ -444,8 +497,12 @@ class MoEFn(torch.autograd.Function):
     def forward(ctx, x, plan, gate_w, gate_b, *params):
         x = x.contiguous()
         stacked, shared = plan["stacked"], plan["shared"]
-        out, idx, wts, saved = ops.moe_train(x, gate_w.detach().contiguous(), gate_b.detach().contiguous(), stacked,
-                                             shared if shared is not None else [None] * 6, plan["masks"], plan["k"], plan["dff_raw"])
+        res = ops.moe_train(x, gate_w.detach().contiguous(), gate_b.detach().contiguous(), stacked,
+                            shared if shared is not None else [None] * 6, plan["masks"], plan["k"], plan["dff_raw"],
+                            sel_bias=plan.get("sel_bias"), update_rate=plan.get("update_rate", 0.0))
+        out, idx, wts, saved = res[:4]
+        if len(res) > 4:
+            plan["bias_delta"] = res[4]
         plan["routing"] = (idx, wts)
         t = lambda w: None if w is None else w.transpose(-1, -2).contiguous()
         ctx.plan = plan

@@ -211,7 +211,7 @@ int32_t amt_launch_moe_combine(const float* y_rows, const int32_t* slot_pos, con
 // the mixture layer's router + plan and its combine for any k, as moe_fwd_impl launches them (moe.hip; the training forward of moe_bwd.hip)
 int32_t amt_launch_moe_route_plan(const float* x, const float* gate_w, const float* gate_b, int32_t* idx, float* wts, int32_t* plan_ints,
                                   int32_t* perm, int32_t* slot_pos, int32_t* tile_group, int n_tok, int d, int n_exp, int k, int Mp,
-                                  hipStream_t stream);
+                                  hipStream_t stream, const float* sel_bias = nullptr, float update_rate = 0.f, float* bias_delta = nullptr);
 int32_t amt_launch_moe_combine_k(const float* y_rows, const int32_t* slot_pos, const int32_t* idx, const float* wts, const float* shared,
                                  float* out, int n_tok, int d, int k, hipStream_t stream);
 // decision + next chord-stream row + position advance of the lockstep V1/V2 step, one launch (sample.hip)

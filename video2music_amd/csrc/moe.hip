@@ -111,6 +111,75 @@ __global__ __launch_bounds__(256) void moe_route_k_kernel(const float* __restric
     }
 }
 
+// The router of SharedMoELayer(balancing=True) in training mode (moe.py:257-268): the k experts are those with the largest
+// logit + sel_bias[e] (largest first, the lower expert id first among equals), and the weights are the softmax over the RAW logits of
+// those k, their own maximum subtracted.  The logits are moe_route_k_kernel's sums (route_token's too: the same chunk order); with
+// sel_bias all zero the k raw logits arrive sorted and the weights are route_token's expression at k = 2, moe_route_k_kernel's
+// otherwise: the bits of the plain routers.
+__global__ __launch_bounds__(256) void moe_route_biased_kernel(const float* __restrict__ x, const float* __restrict__ gw,
+                                                               const float* __restrict__ gb, const float* __restrict__ sel_bias, int n_tok,
+                                                               int d, int n_exp, int k, int* __restrict__ idx, float* __restrict__ wts) {
+    const int lane = threadIdx.x & 63;
+    const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tok >= n_tok) return;
+    const float* xrow = x + (size_t)tok * d;
+    float bv[KMAX], rv[KMAX];                       // the selection value and the raw logit of the j-th choice
+    int bi[KMAX];
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) { bv[j] = -INFINITY; rv[j] = -INFINITY; bi[j] = 0; }
+    for (int e = 0; e < n_exp; ++e) {
+        float s = 0.f;
+        for (int c = lane * 4; c < d; c += 256) {
+            const float4 a = ld4(xrow + c), w = ld4(gw + (size_t)e * d + c);
+            s += a.x * w.x + a.y * w.y + a.z * w.z + a.w * w.w;
+        }
+        s = wave_sum(s) + (gb ? gb[e] : 0.f);
+        float cv = s + sel_bias[e], cr = s;
+        int ci = e;
+        bool ins = false;
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) {
+            if (j < k && (ins || cv > bv[j])) {
+                const float tv = bv[j], tr = rv[j]; const int ti = bi[j];
+                bv[j] = cv; rv[j] = cr; bi[j] = ci; cv = tv; cr = tr; ci = ti;
+                ins = true;
+            }
+        }
+    }
+    float ev[KMAX];
+    if (k == 2) {
+        const bool first = rv[0] >= rv[1];          // the larger raw logit takes route_token's w0
+        const float e1 = __expf(first ? rv[1] - rv[0] : rv[0] - rv[1]);
+        const float hi = 1.0f / (1.0f + e1), lo = e1 * hi;
+        ev[0] = first ? hi : lo;
+        ev[1] = first ? lo : hi;
+    } else {
+        float mx = rv[0], sum = 0.f;
+#pragma unroll
+        for (int j = 1; j < KMAX; ++j) if (j < k) mx = fmaxf(mx, rv[j]);
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) { ev[j] = j < k ? __expf(rv[j] - mx) : 0.f; sum += ev[j]; }
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) ev[j] = ev[j] / sum;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j)
+            if (j < k) { idx[tok * k + j] = bi[j]; wts[tok * k + j] = ev[j]; }
+    }
+}
+
+// bias_delta[e] = update_rate (mean(c) - c[e]) from the plan's integer counts (moe.py:270-279: c = bincount as fp32, mean = sum / n);
+// between moe_count_kernel and moe_offsets_kernel, which zeroes the counts.  One wave.
+__global__ __launch_bounds__(64) void moe_bias_delta_kernel(const int* __restrict__ counts, int n_exp, float update_rate,
+                                                            float* __restrict__ bias_delta) {
+    float sum = 0.f;
+    for (int e = 0; e < n_exp; ++e) sum += (float)counts[e];
+    const float mean = sum / (float)n_exp;
+    const int e = threadIdx.x;
+    if (e < n_exp) bias_delta[e] = update_rate * (mean - (float)counts[e]);
+}
+
 // combine for k != 2: the token's k expert rows in expert-index order (moe.py:191-199), then shared / k
 __global__ void moe_combine_k_kernel(const float* __restrict__ Y, const int* __restrict__ slot_pos, const int* __restrict__ idx,
                                      const float* __restrict__ wts, const float* __restrict__ shared, float shared_scale,
@@ -512,14 +581,17 @@ int32_t amt_launch_moe_route_combine(const float* x, const float* gate_w, const 
 // ---- the layer's first and last launches for the training forward (moe_bwd.hip): moe_fwd_impl's kernels in its order, but for the
 //      placement, which is the stable one (every output row is computed independently: the forward's values do not depend on it) ----
 // router + plan: idx / wts (n_tok, k), perm (Mp), slot_pos (n_tok k), tile_group (Mp / 128), plan_ints (256: [64..128] keeps the segment offsets)
+// sel_bias (n_exp) given: the balancing router (moe_route_biased_kernel), and bias_delta (n_exp) from the plan's counts
 int32_t amt_launch_moe_route_plan(const float* x, const float* gate_w, const float* gate_b, int32_t* idx, float* wts, int32_t* plan_ints,
                                   int32_t* perm, int32_t* slot_pos, int32_t* tile_group, int n_tok, int d, int n_exp, int k, int Mp,
-                                  hipStream_t s) {
+                                  hipStream_t s, const float* sel_bias, float update_rate, float* bias_delta) {
     AMT_HIP(hipMemsetAsync(plan_ints, 0, 64 * sizeof(int), s));
-    if (k == 2) hipLaunchKernelGGL(moe_route_kernel, dim3(cdiv(n_tok, 4)), dim3(256), 0, s, x, gate_w, gate_b, n_tok, d, n_exp, idx, wts);
+    if (sel_bias) hipLaunchKernelGGL(moe_route_biased_kernel, dim3(cdiv(n_tok, 4)), dim3(256), 0, s, x, gate_w, gate_b, sel_bias, n_tok, d, n_exp, k, idx, wts);
+    else if (k == 2) hipLaunchKernelGGL(moe_route_kernel, dim3(cdiv(n_tok, 4)), dim3(256), 0, s, x, gate_w, gate_b, n_tok, d, n_exp, idx, wts);
     else hipLaunchKernelGGL(moe_route_k_kernel, dim3(cdiv(n_tok, 4)), dim3(256), 0, s, x, gate_w, gate_b, n_tok, d, n_exp, k, idx, wts);
     AMT_LAUNCH_CHECK();
     hipLaunchKernelGGL(moe_count_kernel, dim3(cdiv(k * n_tok, 256)), dim3(256), 0, s, idx, k * n_tok, plan_ints);
+    if (bias_delta) hipLaunchKernelGGL(moe_bias_delta_kernel, dim3(1), dim3(64), 0, s, plan_ints, n_exp, update_rate, bias_delta);
     hipLaunchKernelGGL(moe_offsets_kernel, dim3(1), dim3(1024), 0, s, plan_ints, plan_ints + 64, plan_ints + 192, n_exp, perm, tile_group, Mp);
     hipLaunchKernelGGL(moe_place_stable_kernel, dim3(n_exp), dim3(256), 0, s, idx, k * n_tok, plan_ints + 64, perm, slot_pos, k);
     AMT_LAUNCH_CHECK();

@@ -210,25 +210,28 @@ extern "C" int32_t amt_moe_wgrad_splits(int32_t n_tok, int32_t d, int32_t dff, i
     return wgrad_plan_splits(n_tok, d, dff, n_exp, k, dense);
 }
 
-extern "C" int32_t amt_moe_train_fwd(const float* x, const float* gate_w, const float* gate_b,
-                                     const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
-                                     const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
-                                     const float* mask_h, const float* mask_y, const float* mask_hs,
-                                     float* out, int32_t* idx_out, float* w_out, float* saved,
-                                     int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, void* stream) {
-    AMT_CHECK_ARG(x && gate_w && wg && w2 && out && saved, "amt_moe_train_fwd: null pointer");
-    AMT_CHECK_ARG(n_tok > 0 && n_exp >= 2 && n_exp <= 64, "amt_moe_train_fwd: need 2 <= n_experts <= 64");
-    AMT_CHECK_ARG(k >= 1 && k <= KMAX && k <= n_exp, "amt_moe_train_fwd: n_experts_per_token=%d outside 1..min(%d, n_experts)", k, KMAX);
-    AMT_CHECK_ARG(d % 32 == 0 && dff % 32 == 0, "amt_moe_train_fwd: d and d_ff must be multiples of 32");
-    AMT_CHECK_ARG(dff_raw > 0 && dff_raw <= dff, "amt_moe_train_fwd: the experts' own width %d is outside 1..d_ff=%d", dff_raw, dff);
-    AMT_CHECK_ARG((long)k * n_tok + (long)TILE * (n_exp + 1) < (1L << 31) / (dff > d ? dff : d), "amt_moe_train_fwd: the plan's rows do not fit 32-bit indices");
-    AMT_CHECK_ARG(!mask_hs || swg, "amt_moe_train_fwd: mask_hs without a shared expert");
+// amt_moe_train_fwd, and with sel_bias given amt_moe_train_fwd_balanced: only the router and the bias_delta launch differ
+static int32_t moe_train_fwd_impl(const char* entry, const float* x, const float* gate_w, const float* gate_b,
+                                  const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
+                                  const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
+                                  const float* mask_h, const float* mask_y, const float* mask_hs,
+                                  float* out, int32_t* idx_out, float* w_out, float* saved,
+                                  int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, void* stream,
+                                  const float* sel_bias, float update_rate, float* bias_delta) {
+    AMT_CHECK_ARG(x && gate_w && wg && w2 && out && saved, "%s: null pointer", entry);
+    AMT_CHECK_ARG(n_tok > 0 && n_exp >= 2 && n_exp <= 64, "%s: need 2 <= n_experts <= 64", entry);
+    AMT_CHECK_ARG(k >= 1 && k <= KMAX && k <= n_exp, "%s: n_experts_per_token=%d outside 1..min(%d, n_experts)", entry, k, KMAX);
+    AMT_CHECK_ARG(d % 32 == 0 && dff % 32 == 0, "%s: d and d_ff must be multiples of 32", entry);
+    AMT_CHECK_ARG(dff_raw > 0 && dff_raw <= dff, "%s: the experts' own width %d is outside 1..d_ff=%d", entry, dff_raw, dff);
+    AMT_CHECK_ARG((long)k * n_tok + (long)TILE * (n_exp + 1) < (1L << 31) / (dff > d ? dff : d), "%s: the plan's rows do not fit 32-bit indices", entry);
+    AMT_CHECK_ARG(!mask_hs || swg, "%s: mask_hs without a shared expert", entry);
     hipStream_t s = (hipStream_t)stream;
     const int glu = w1 != nullptr;
     const Saved sv = saved_layout(saved, n_tok, d, dff, n_exp, k, glu);
     const int Mp = sv.Mp, A = k * n_tok;
     int32_t rc;
-    if ((rc = amt_launch_moe_route_plan(x, gate_w, gate_b, sv.idx, sv.wts, sv.plan_ints, sv.perm, sv.slot_pos, sv.tile_group, n_tok, d, n_exp, k, Mp, s)))
+    if ((rc = amt_launch_moe_route_plan(x, gate_w, gate_b, sv.idx, sv.wts, sv.plan_ints, sv.perm, sv.slot_pos, sv.tile_group, n_tok, d, n_exp, k, Mp, s,
+                                        sel_bias, update_rate, bias_delta)))
         return rc;
     AMT_HIP(hipMemsetAsync(sv.slot_assign, 0xFF, (size_t)Mp * sizeof(int), s));
     AMT_HIP(hipMemsetAsync(sv.dense_group, 0, ((size_t)n_tok / TILE + 2) * sizeof(int), s));
@@ -257,7 +260,7 @@ extern "C" int32_t amt_moe_train_fwd(const float* x, const float* gate_w, const 
     }
     const float* shared = nullptr;
     if (swg) {
-        AMT_CHECK_ARG(sw2 && (sw1 != nullptr) == (w1 != nullptr), "amt_moe_train_fwd: incomplete shared expert");
+        AMT_CHECK_ARG(sw2 && (sw1 != nullptr) == (w1 != nullptr), "%s: incomplete shared expert", entry);
         // the eval path's gate launch as it is for GLU experts; where that path has an epilogue the tiled kernel needs (the SiLU of
         // a SiLU expert, the gate of the up projection) the plain product takes the same kernel through a one-group tile plan
         GemmParams a = gemm_params(x, d, swg, d, sv.Gs, dff, n_tok, dff, d, sbg);
@@ -276,6 +279,28 @@ extern "C" int32_t amt_moe_train_fwd(const float* x, const float* gate_w, const 
         shared = sv.Ys;
     }
     return amt_launch_moe_combine_k(sv.Y, sv.slot_pos, sv.idx, sv.wts, shared, out, n_tok, d, k, s);
+}
+
+extern "C" int32_t amt_moe_train_fwd(const float* x, const float* gate_w, const float* gate_b,
+                                     const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
+                                     const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
+                                     const float* mask_h, const float* mask_y, const float* mask_hs,
+                                     float* out, int32_t* idx_out, float* w_out, float* saved,
+                                     int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, void* stream) {
+    return moe_train_fwd_impl("amt_moe_train_fwd", x, gate_w, gate_b, w1, b1, wg, bg, w2, b2, sw1, sb1, swg, sbg, sw2, sb2, mask_h, mask_y, mask_hs,
+                              out, idx_out, w_out, saved, n_tok, d, dff, dff_raw, n_exp, k, stream, nullptr, 0.f, nullptr);
+}
+
+extern "C" int32_t amt_moe_train_fwd_balanced(const float* x, const float* gate_w, const float* gate_b,
+                                              const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
+                                              const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
+                                              const float* mask_h, const float* mask_y, const float* mask_hs,
+                                              float* out, int32_t* idx_out, float* w_out, float* saved,
+                                              int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, void* stream,
+                                              const float* sel_bias, float update_rate, float* bias_delta) {
+    AMT_CHECK_ARG(sel_bias && bias_delta, "amt_moe_train_fwd_balanced: null pointer");
+    return moe_train_fwd_impl("amt_moe_train_fwd_balanced", x, gate_w, gate_b, w1, b1, wg, bg, w2, b2, sw1, sb1, swg, sbg, sw2, sb2, mask_h, mask_y,
+                              mask_hs, out, idx_out, w_out, saved, n_tok, d, dff, dff_raw, n_exp, k, stream, sel_bias, update_rate, bias_delta);
 }
 
 extern "C" int32_t amt_moe_bwd(const float* dout, const float* x, const float* gate_w, const float* saved,

@@ -5,7 +5,10 @@ Same parameter names (``experts.{e}.linear1|linear2|gate``, ``gate``, ``shared_e
 ``bias`` when ``balancing``).  The reference's module-global logging side effects
 (``update_maxvio`` / ``update_expert_counts``) are deliberately not replicated.
 In training mode ``forward`` goes through ``autograd.MoEFn`` (``amt_moe_train_fwd`` / ``amt_moe_bwd``) with fixed k and
-temperature 1; top-k / temperature schedulers, balancing-bias updates and expert-parallel execution are refused there with the reason.
+temperature 1; top-k / temperature schedulers and expert-parallel execution are refused there with the reason.  A layer with
+``balancing=True`` is refused too unless its ``train_balancing`` is set (``VideoMusicTransformer_V2.enable_training()`` sets it on a
+model's layers): it then routes on ``logits + bias``, weighs with the raw logits (``amt_moe_train_fwd_balanced``) and adds
+``update_rate (mean(c) - c)`` to its ``bias`` buffer in every training-mode forward, as the reference does (``moe.py:257-279``).
 """
 import copy
 
@@ -267,6 +270,9 @@ class _MoEBase(HasDerived, nn.Module):
     shared = False
     ep_group = None
     expert_parallel = False
+    # opt-in: a layer with balancing=True trains (the biased router and the bias step) only when this is true, and then only with
+    # gradients enabled (the rule of the models' `_train_path`): every other state answers as it did before the opt-in existed
+    train_balancing = False
 
     def enable_expert_parallel(self, group=None):
         """Config 5: rank r runs experts [r*E/W, (r+1)*E/W); token rows travel by all_to_all (RCCL over xGMI)."""
@@ -311,8 +317,9 @@ class _MoEBase(HasDerived, nn.Module):
         """Why this layer does not train here, or None: the reference's callers train with fixed k and temperature 1."""
         if hasattr(self, "topk_scheduler") or hasattr(self, "temperature_scheduler"):
             return "MoE training with a top-k / temperature scheduler is not built (no reference caller trains with one)"
-        if getattr(self, "balancing", False):
-            return "MoE training with balancing=True (the routing-bias update) is not built"
+        if getattr(self, "balancing", False) and not (self.train_balancing and torch.is_grad_enabled()):
+            return ("MoE training with balancing=True (the routing-bias update) is not built into the default path: set "
+                    "`train_balancing = True` on the layer (the model's `enable_training()` does)")
         if self.expert_parallel:
             return "MoE training under expert-parallel execution is not built"
         return None
@@ -359,11 +366,18 @@ class _MoEBase(HasDerived, nn.Module):
         shared = expert_tensors(self.shared_expert) if self.shared else None
         plan = {"k": k, "n_exp": self.n_experts, "dff_raw": raw, "masks": tuple(masks), "stacked": self._stacked_expert_weights(publish=False),
                 "shared": shared}
+        balancing = bool(getattr(self, "balancing", False))
+        if balancing:                           # moe.py:257-268: chosen on logits + bias, weighed by the raw logits
+            plan["sel_bias"] = self.bias.detach().to(torch.float32).reshape(-1).contiguous()
+            plan["update_rate"] = float(self.update_rate)
         own = lambda e: [q for name in ("linear1", "gate", "linear2") for lin in [expert_parts(e)[name]] if lin is not None
                          for q in (lin.weight, lin.bias)]
         params = [q for e in self.experts for q in own(e)] + (own(self.shared_expert) if self.shared else [])
         out = AG.MoEFn.apply(x.to(torch.float32).reshape(n_tok, d), plan, self.gate.weight, self.gate.bias, *params)
         idx, wts = plan.pop("routing")
+        if balancing:                           # moe.py:274-279: in the forward, once per training-mode call; no host synchronisation
+            with torch.no_grad():
+                self.bias.add_(plan.pop("bias_delta").view(self.n_experts, 1))
         self.last_routing = (idx.view(L, B, k), wts.view(L, B, k))
         self.__dict__["last_dropout_masks"] = used
         return out.view(L, B, d)

@@ -59,7 +59,7 @@ class VideoMusicTransformer_V2(HasDerived, nn.Module):
     (``video2music_amd/ops.py``): ``generate`` runs the video encoder once and the decoder one token at a time over
     cached keys/values (the reference re-runs both stacks on the whole prefix every step, :547-548).  In training mode with
     gradients enabled ``forward`` builds an autograd graph on the module's own parameters instead (``_forward_train``; '2.2' trains,
-    '2.0' / '2.1' are refused there with the reason).
+    '2.0' / '2.1' are refused there with the reason; ``balancing=True`` and the V3 family train after ``enable_training()``).
     """
 
     def __init__(self, version_name="2.0", n_layers=6, num_heads=8, d_model=512, dim_feedforward=1024, dropout=0.1,
@@ -389,20 +389,36 @@ class VideoMusicTransformer_V2(HasDerived, nn.Module):
         from .moe import _MoEBase
         if IS_SEPERATED:
             return "IS_SEPERATED: training the separate root / attr heads is not built"
-        if self.version_name.startswith("3"):
-            return f"version {self.version_name!r}: the differential attention of the V3 family has no backward"
+        opted_in = getattr(self, "_training_enabled", False)
+        if self.version_name.startswith("3") and not opted_in:
+            return (f"version {self.version_name!r}: the differential attention of the V3 family has no backward on the default path; "
+                    "call `enable_training()` on the model (`python -m video2music_amd.train_v3` does)")
         if self.version_name in ("2.0", "2.1"):
             return (f"version {self.version_name!r}: the reference gives it a TopKScheduler that acts in training, and the mixture layers "
                     "do not train with one")
-        if any(getattr(m, "balancing", False) for m in self.modules() if isinstance(m, _MoEBase)):
-            return "balancing=True: the routing-bias update of the mixture layers in training is not built"
+        if not opted_in and any(getattr(m, "balancing", False) for m in self.modules() if isinstance(m, _MoEBase)):
+            return ("balancing=True: the routing-bias update of the mixture layers in training is not built into the default path; "
+                    "call `enable_training()` on the model (`python -m video2music_amd.train_v3` does)")
         hd = self.d_model // self.nhead
         if hd not in (32, 64, 128):
             return f"head_dim {hd}: the attention backward (amt_attn_bwd) is built for head dims 32 / 64 / 128"
         return None
 
+    def enable_training(self):
+        """Opt in to the training paths that are not the default: the differential attention's backward (`autograd.DiffAttentionFn`,
+        the V3 family) and the mixture layers' balancing router with its routing-bias step (`train_balancing` is set on every mixture
+        layer of the model).  Lifts those two refusals of `_train_refusal` and no other; eval mode, `no_grad`, `generate` and
+        `generate_batch` run what they ran before.  Returns self."""
+        from .moe import _MoEBase
+        self.__dict__["_training_enabled"] = True
+        for m in self.modules():
+            if isinstance(m, _MoEBase):
+                m.train_balancing = True
+        return self
+
     def _forward_train(self, x, x_root, x_attr, sem, key, scene, motion, emotion, mask):
-        """`_encode_memory`, `_decode`, `_enc_layer` and `_dec_layer` line for line (post-norm, no residual dropout) on seq-first rows,
+        """`_encode_memory`, `_decode`, `_enc_layer` and `_dec_layer` line for line (post-norm, or the pre-norm form of '3.2'; no
+        residual dropout) on seq-first rows,
         composed through `autograd`'s Functions, so that `loss.backward()` reaches every parameter that takes part: `embedding` and
         `condition_linear` do not, nor -- with chord_embed -- `embedding_root` / `embedding_attr`, as in the reference; the frozen chord
         table is gathered without a gradient.
@@ -417,7 +433,14 @@ class VideoMusicTransformer_V2(HasDerived, nn.Module):
         default CPU generator); then per encoder layer the attention's keep mask and, for a plain GLU layer, its hidden multipliers
         (S B, d_ff) by seq-first row; then per decoder layer the self-attention's keep mask, the cross-attention's, and a plain GLU
         layer's hidden multipliers (L B, d_ff).  Sites with dropout 0 are skipped.  The mixture layers keep their own lists
-        (`MoELayer.dropout_masks`, rows by seq-first token)."""
+        (`MoELayer.dropout_masks`, rows by seq-first token).
+
+        The V3 family (model/vmt_v3.py; after `enable_training()`): a differential attention is bias-free `LinearFn` projections
+        (E -> 2E for q and k), `RopeFn` through the raw (2H, L, B, hd) view with the 2 d_model cache, `DiffAttentionFn` with lambda a
+        1-element device tensor built by torch under autograd from the four lambda vectors (no host read, no `_derived` entry), and
+        the bias-free out projection over the raw (L B, E) view of the (B, H, L, hd) result.  It contributes no dropout mask (the
+        reference's dropout on the differential map is commented out).  '3.0' keeps the V2 attention, keep mask included, in the
+        encoder."""
         from .. import autograd as AG
         from .moe import GLUExpert, SiLUExpert, expert_parts, expert_tensors
         why = self._train_refusal()
@@ -461,7 +484,22 @@ class VideoMusicTransformer_V2(HasDerived, nn.Module):
         def seq_first(t, n):                                    # (B, n, ...) -> rows (n B, ...)
             return t.transpose(0, 1).reshape(n * B, *t.shape[2:]).contiguous()
 
+        def diff_attn(a, x_q, x_kv, Lq, Lk, causal):            # custom_transformer.py:775-827
+            zero = lambda n: torch.zeros(n, device=dev)         # LinearFn takes a bias; these projections have none
+            x_kv = x_q if x_kv is None else x_kv
+            q = AG.LinearFn.apply(x_q, a.q_proj.weight, zero(2 * d))
+            k = AG.LinearFn.apply(x_kv, a.k_proj.weight, zero(2 * d))
+            v = AG.LinearFn.apply(x_kv, a.v_proj.weight, zero(d))
+            q = AG.RopeFn.apply(q.view(2 * H, Lq, B, hd), self._rope_cache).view(-1)
+            k = AG.RopeFn.apply(k.view(2 * H, Lk, B, hd), self._rope_cache).view(-1)
+            lam = (torch.exp(torch.sum(a.lambda_q1 * a.lambda_k1).float()) - torch.exp(torch.sum(a.lambda_q2 * a.lambda_k2).float())
+                   + a.lambda_init).reshape(1)
+            y = AG.DiffAttentionFn.apply(q, k, v.view(-1), lam, a.subln.weight, B, H, Lq, Lk, causal, 1.0 - a.lambda_init, a.subln.eps)
+            return AG.LinearFn.apply(y.view(Lq * B, d), a.out_proj.weight, zero(d))       # attn.view(tgt_len, bsz, E) (:825)
+
         def attn(a, x_q, x_kv, Lq, Lk, causal):
+            if hasattr(a, "lambda_q1"):
+                return diff_attn(a, x_q, x_kv, Lq, Lk, causal)
             w, b_ = a.in_proj_weight, a.in_proj_bias
             if x_kv is None:                                    # self-attention: one packed product
                 qkv = AG.LinearFn.apply(x_q, w, b_)
@@ -527,11 +565,21 @@ class VideoMusicTransformer_V2(HasDerived, nn.Module):
 
         tr = self.transformer
         mem = vf
+        pre_norm = getattr(self, "pre_norm", False)             # '3.2' (custom_transformer.py:1239-1247, 1278-1291)
         for lyr in tr.encoder.layers:
+            if pre_norm:
+                mem = mem + attn(lyr.self_attn, norm(lyr.norm1, mem), None, S, S, False)
+                mem = mem + ffn(lyr.ff, norm(lyr.norm2, mem), S)
+                continue
             mem = norm(lyr.norm1, attn(lyr.self_attn, mem, None, S, S, False), mem)
             mem = norm(lyr.norm2, ffn(lyr.ff, mem, S), mem)
         mem = norm(tr.encoder.norm, mem)
         for lyr in tr.decoder.layers:
+            if pre_norm:
+                t = t + attn(lyr.self_attn, norm(lyr.norm1, t), None, L, L, mask is True)
+                t = t + attn(lyr.cross_attn, norm(lyr.norm2, t), mem, L, S, False)
+                t = t + ffn(lyr.ff, norm(lyr.norm3, t), L)
+                continue
             t = norm(lyr.norm1, attn(lyr.self_attn, t, None, L, L, mask is True), t)
             t = norm(lyr.norm2, attn(lyr.cross_attn, t, mem, L, S, False), t)
             t = norm(lyr.norm3, ffn(lyr.ff, t, L), t)

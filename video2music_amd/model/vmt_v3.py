@@ -54,6 +54,12 @@ class VideoMusicTransformer_V3(VideoMusicTransformer_V2):
     decoder on the whole prefix every step (the encoder still runs once).  Here both maps run on the tiled attention
     kernel (two launches over strided views, no copies), the subtraction + sub-norm + scale is one kernel
     (``amt_diff_subln_fwd``) writing the (B, H, L, hd) layout the reference reinterprets.
+
+    Training: refused by default ("the differential attention ... has no backward" on the default path).  After
+    ``enable_training()`` (inherited from the V2 class; ``python -m video2music_amd.train_v3`` calls it) ``forward`` in training mode
+    with gradients enabled runs ``VideoMusicTransformer_V2._forward_train`` with ``autograd.DiffAttentionFn`` in the attentions'
+    place -- lambda then is a 1-element device tensor under autograd, not the host scalar of ``lambda_full`` -- and the balancing
+    mixture layers train and step their ``bias`` buffers.  ``IS_SEPERATED`` and head dims other than 32 / 64 / 128 stay refused.
     """
 
     def __init__(self, version_name="3.0", n_layers=6, num_heads=8, d_model=512, dim_feedforward=1024, dropout=0.1,

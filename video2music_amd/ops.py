@@ -41,6 +41,40 @@ def diff_subln(o1, o2, w, lam, out_scale, eps=1e-5):
     return y
 
 
+def diff_subln_train(o1, o2, w, lam, out_scale, eps=1e-5):
+    """amt_diff_subln_train_fwd: `diff_subln` with lam a 1-element fp32 tensor on the device; the same bits for the same value."""
+    hd = o1.shape[-1]
+    assert lam.numel() == 1 and lam.dtype == torch.float32 and lam.device == o1.device
+    y = torch.empty_like(o1)
+    _lib.call("amt_diff_subln_train_fwd", p(o1), p(o2), p(w), p(lam), p(y), o1.numel() // hd, hd, float(out_scale), float(eps), _st())
+    return y
+
+
+def diff_subln_bwd_blocks(rows, hd):
+    """The workgroups `diff_subln_bwd` launches for this many rows of hd values (amt_diff_subln_bwd_blocks, the rule of
+    csrc/diff_subln_train.hip; needs no GPU): workgroup b takes the rows [b per, (b + 1) per), per = ceil(rows / blocks), and dw / dlam
+    are the sums of the workgroups' slabs in that order."""
+    n = _lib.call("amt_diff_subln_bwd_blocks", rows, hd)
+    if n < 1:
+        raise _lib.AmtError(f"amt_diff_subln_bwd_blocks: amt_diff_subln_bwd refuses rows={rows} hd={hd}")
+    return n
+
+
+def diff_subln_bwd(dy, o1, o2, w, lam, out_scale, eps=1e-5):
+    """amt_diff_subln_bwd: the backward of `diff_subln_train(o1, o2, w, lam, out_scale, eps)` from dy and the forward's own inputs;
+    hd 32 / 64 / 128.  Returns d_o1, d_o2 (as o1), dw (hd) and dlam (1)."""
+    hd = o1.shape[-1]
+    assert dy.shape == o1.shape == o2.shape and w.shape == (hd,) and lam.numel() == 1
+    for t in (dy, o1, o2, w, lam):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    d_o1, d_o2 = torch.empty_like(o1), torch.empty_like(o2)
+    dw, dlam = torch.empty_like(w), torch.empty_like(lam)
+    ws = torch.empty(4 + 128 * (hd + 4), device=o1.device, dtype=torch.float32)  # AMT_DIFF_SUBLN_BWD_WS_FLOATS(hd); a call's own scratch
+    _lib.call("amt_diff_subln_bwd", p(dy), p(o1), p(o2), p(w), p(lam), p(d_o1), p(d_o2), p(dw), p(dlam), p(ws), o1.numel() // hd, hd,
+              float(out_scale), float(eps), _st())
+    return d_o1, d_o2, dw, dlam
+
+
 def add(a, b):
     y = torch.empty_like(a)
     _lib.call("amt_add_fwd", p(a), p(b), p(y), a.numel(), _st())
@@ -90,12 +124,19 @@ def attention_train(q, k, v, strides, B, H, Lq, Lk, hd, causal, q_scale, out, kv
     return out, lse
 
 
+def attention_bwd_ws(B, H, Lq, Lk, hd, device, rpr=False):
+    """The scratch of one `attention_bwd` call (amt_attn_bwd_ws_floats); calls of one shape that follow one another on a stream may share it."""
+    return torch.empty(_lib.call("amt_attn_bwd_ws_floats", B, H, Lq, Lk, hd, int(rpr)), device=device, dtype=torch.float32)
+
+
 def attention_bwd(dO, q, k, v, o, lse, strides, B, H, Lq, Lk, hd, causal, q_scale, dq, dk, dv, kv_group=1, Er=None, keep=None,
-                  keep_scale=1.0, need_dEr=True):
-    """amt_attn_bwd: fills dq / dk / dv (buffers laid out as q / k / v; dO as o) and returns dEr (er_len, hd) or None."""
+                  keep_scale=1.0, need_dEr=True, ws=None):
+    """amt_attn_bwd: fills dq / dk / dv (buffers laid out as q / k / v; dO as o) and returns dEr (er_len, hd) or None.  ws: the
+    call's scratch (`attention_bwd_ws`), its own when not given."""
     s = (C.c_int64 * 12)(*strides)
     dEr = torch.empty_like(Er) if Er is not None and need_dEr else None
-    ws = torch.empty(_lib.call("amt_attn_bwd_ws_floats", B, H, Lq, Lk, hd, int(Er is not None)), device=dO.device, dtype=torch.float32)
+    if ws is None:
+        ws = attention_bwd_ws(B, H, Lq, Lk, hd, dO.device, Er is not None)
     _lib.call("amt_attn_bwd", p(dO), p(q), p(k), p(v), p(o), p(lse), p(Er), 0 if Er is None else Er.shape[0], p(keep), float(keep_scale),
               p(dq), p(dk), p(dv), p(dEr), s, B, H, Lq, Lk, hd, int(causal), int(kv_group), float(q_scale), p(ws), _st())
     return dEr
@@ -398,11 +439,13 @@ def reg_metrics(feat, w_heads, note_density, loudness, instrument, return_rows=F
     return (clip, ln_nd, inst) if return_rows else clip
 
 
-def moe_train(x, gate_w, gate_b, experts, shared, masks, k, dff_raw):
+def moe_train(x, gate_w, gate_b, experts, shared, masks, k, dff_raw, sel_bias=None, update_rate=0.0):
     """amt_moe_train_fwd on x (n_tok, d): `experts` = (w1, b1, wg, bg, w2, b2) stacked over the experts at the padded hidden width
     (w1 / b1 None: SiLU experts), `shared` the shared expert's six or six Nones, `masks` = (mask_h (n_tok k, dff_raw), mask_y
     (n_tok k, d), mask_hs (n_tok, dff_raw)), each a multiplier tensor or None.  Returns out (n_tok, d), idx (n_tok, k) int32,
-    wts (n_tok, k) and `saved`, the buffer `moe_bwd` reads."""
+    wts (n_tok, k) and `saved`, the buffer `moe_bwd` reads.
+    sel_bias (n_exp) given: amt_moe_train_fwd_balanced -- the experts are chosen on logit + sel_bias and weighed by the raw logits -- and
+    a fifth result, bias_delta (n_exp) = update_rate (mean(c) - c) from the plan's rows per expert."""
     n_tok, d = x.shape
     n_exp, dff = experts[2].shape[0], experts[2].shape[1]
     mask_h, mask_y, mask_hs = masks
@@ -416,9 +459,15 @@ def moe_train(x, gate_w, gate_b, experts, shared, masks, k, dff_raw):
     idx = torch.empty(n_tok, k, device=x.device, dtype=torch.int32)
     wts = torch.empty(n_tok, k, device=x.device, dtype=torch.float32)
     saved = torch.empty(_lib.call("amt_moe_train_scratch_floats", n_tok, d, dff, n_exp, k, glu), device=x.device, dtype=torch.float32)
-    _lib.call("amt_moe_train_fwd", p(x), p(gate_w), p(gate_b), *[p(t) for t in experts], *[p(t) for t in shared], p(mask_h), p(mask_y),
-              p(mask_hs), p(out), p(idx), p(wts), p(saved), n_tok, d, dff, dff_raw, n_exp, k, _st())
-    return out, idx, wts, saved
+    args = (p(x), p(gate_w), p(gate_b), *[p(t) for t in experts], *[p(t) for t in shared], p(mask_h), p(mask_y),
+            p(mask_hs), p(out), p(idx), p(wts), p(saved), n_tok, d, dff, dff_raw, n_exp, k, _st())
+    if sel_bias is None:
+        _lib.call("amt_moe_train_fwd", *args)
+        return out, idx, wts, saved
+    assert sel_bias.dtype == torch.float32 and sel_bias.is_contiguous() and sel_bias.numel() == n_exp and sel_bias.device == x.device
+    bias_delta = torch.empty(n_exp, device=x.device, dtype=torch.float32)
+    _lib.call("amt_moe_train_fwd_balanced", *args, p(sel_bias), float(update_rate), p(bias_delta))
+    return out, idx, wts, saved, bias_delta
 
 
 def moe_bwd(dout, x, gate_w, saved, experts_t, shared_t, masks, k, dff_raw, n_exp, temperature=1.0):

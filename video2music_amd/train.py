@@ -18,7 +18,8 @@ Refused, with the reason: ``-music_gen_version`` 1.x / 2.x / 3.x, ``-is_video Fa
 
 ``main(argv, families=...)`` / ``refuse(args, families=...)`` admit the listed V1 / V2 versions as well (``train_families`` is that
 entry point): the class the reference's ``train.py:136-168`` builds, trained through ``VideoMusicTransformer_V2._forward_train`` with
-the same loop, files and schedule.  With the default empty ``families`` every answer is the one above.
+the same loop, files and schedule.  With the default empty ``families`` every answer is the one above.  ``train_v3`` adds the V3
+family and ``-balancing`` (``opt_in=True``: the model's ``enable_training()`` is called after it is built).
 
     python -m video2music_amd.train -dataset_dir ./dataset/ -music_gen_version None -chord_embed "" -motion_type 1
 """
@@ -79,8 +80,8 @@ def parse_args(argv=None):
     return args
 
 
-def refuse_family(args, families):
-    """`refuse` for a -music_gen_version other than None when the entry point admits `families`."""
+def refuse_family(args, families, balancing=False):
+    """`refuse` for a -music_gen_version other than None when the entry point admits `families`; balancing: it admits -balancing too."""
     v = args.music_gen_version
     if v not in families:
         why = {"2.0": "the reference gives it a TopKScheduler that acts in training, and the mixture layers do not train with one",
@@ -88,7 +89,7 @@ def refuse_family(args, families):
                "2.3": "it swaps the experts for efficient_kan.KANLinear, a package the reference does not vendor"}.get(
                    v, "the differential attention of the V3 family has no backward" if v.startswith("3.") else "the reference builds no such model")
         return f"-music_gen_version {v}: {why}; the versions that train are {', '.join(families)}"
-    if args.balancing:
+    if args.balancing and not balancing:
         return "-balancing: the routing-bias update of the mixture layers in training is not built"
     if args.chord_embed and not (args.chord_embed_table or args.synthetic_weights or args.continue_weights):
         return ("-chord_embed: the frozen chord table needs a source -- --chord_embed_table PATH (.npy, (n_chords, d_model) float32), "
@@ -101,16 +102,17 @@ def refuse_family(args, families):
     return None
 
 
-def refuse(args, families=()):
+def refuse(args, families=(), balancing=False):
     """The reason this build does not run `args`, or None.  families: the -music_gen_version strings the caller trains beside the base
-    model (`train_families.TRAINABLE`); empty, the answers are the base entry point's."""
+    model (`train_families.TRAINABLE`); empty, the answers are the base entry point's.  balancing (default off; `train_v3` sets it):
+    -balancing is admitted for a family version."""
     family = bool(families) and args.music_gen_version is not None
     if args.force_cpu:
         return "--force_cpu: video2music_amd has no CPU path (the CPU oracle lives in oracle/ for tests only)"
     if not args.is_video:
         return "-is_video False (MusicTransformer) is not built"
     if family:
-        why = refuse_family(args, families)
+        why = refuse_family(args, families, balancing)
         if why:
             return why
     if args.music_gen_version is not None and not family:
@@ -226,17 +228,20 @@ def build_model(args, total_vf_dim):
     v = args.music_gen_version
     if v is None:
         return VideoMusicTransformer(total_vf_dim=total_vf_dim, rpr=bool(args.rpr), scene_embed=False, chord_embed=False, **kw)
-    from .model.video_music_transformer import VideoMusicTransformer_V1, VideoMusicTransformer_V2
+    from .model.video_music_transformer import VideoMusicTransformer_V1, VideoMusicTransformer_V2, VideoMusicTransformer_V3
     fam = dict(version_name=v, total_vf_dim=total_vf_dim - int(bool(args.scene_embed)), rms_norm=bool(args.rms_norm),
                scene_embed=bool(args.scene_embed), chord_embed=bool(args.chord_embed), dropTokenRate=args.droptoken, **kw)
     if v.startswith("1."):
         return VideoMusicTransformer_V1(**fam)
+    if v.startswith("3."):
+        return VideoMusicTransformer_V3(**fam)
     return VideoMusicTransformer_V2(balancing=bool(args.balancing), **fam)
 
 
-def main(argv=None, families=()):
+def main(argv=None, families=(), opt_in=False):
+    """opt_in (`train_v3`): -balancing is admitted and the model's `enable_training()` is called after building it."""
     args = parse_args(argv)
-    why = refuse(args, families)
+    why = refuse(args, families, balancing=opt_in)
     if why:
         raise SystemExit(why)
     device = get_device()
@@ -256,6 +261,8 @@ def main(argv=None, families=()):
     from .generate import total_vf_dim_of
     torch.manual_seed(args.seed)
     model = build_model(args, total_vf_dim_of(args, sem_dim=train["semantic"].shape[-1]))
+    if opt_in and hasattr(model, "enable_training"):
+        model.enable_training()
     if args.synthetic_weights:
         from . import synthetic
         shapes = [(k, tuple(v.shape)) for k, v in model.state_dict().items()]

@@ -9,8 +9,9 @@ Flags, loop, output files, CSV header, schedule and optimisers are ``train``'s. 
 The frozen table of ``-chord_embed`` (the reference fills it from a gensim Word2Vec file) comes from ``--chord_embed_table PATH`` (a
 ``.npy`` of shape (n_chords, d_model), float32), from ``--synthetic_weights`` (the procedural fill), or with ``-continue_weights`` in the
 state dict; with none of the three the command refuses.  Still refused, each with its reason: '2.0' / '2.1' (a top-k scheduler that acts
-in training), '2.3', every 3.x (no backward of the differential attention), ``-balancing``, ``-auxiliary_loss``, ``-drop_loss``,
-``-augmentation``, tensorboard, optimisers other than Adam / AdamW, head dims other than 32 / 64 / 128.
+in training), '2.3', every 3.x and ``-balancing`` (both train through ``train_v3``, which opts in to the differential attention's
+backward and the routing-bias step), ``-auxiliary_loss``, ``-drop_loss``, ``-augmentation``, tensorboard, optimisers other than
+Adam / AdamW, head dims other than 32 / 64 / 128.
 
     python -m video2music_amd.train_families -dataset_dir ./dataset/ --chord_embed_table chord_table.npy -motion_type 1
 """
