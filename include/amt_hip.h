@@ -37,7 +37,7 @@
 #define AMT_HIP_H
 #include <stdint.h>
 
-#define AMT_ABI_VERSION 13   /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
+#define AMT_ABI_VERSION 14   /* 2: argument structs for the step / skinny-GEMM calls, options in place of amt_debug_set_skip;
                                 3: the lockstep step's stacked gate | linear1 matrix is packed from rows interleaved in eights;
                                 4: amt_chord_metrics_fwd;
                                 5: amt_reg_metrics_fwd;
@@ -51,7 +51,9 @@
                                 11: amt_moe_wgrad_splits;
                                 12: amt_rope_bwd, amt_rmsnorm_bwd, amt_rmsnorm_bwd_blocks, amt_glu_train_scratch_floats, amt_glu_train_fwd,
                                     amt_glu_bwd_ws_floats, amt_glu_bwd;
-                                13: amt_diff_subln_train_fwd, amt_diff_subln_bwd, amt_diff_subln_bwd_blocks, amt_moe_train_fwd_balanced */
+                                13: amt_diff_subln_train_fwd, amt_diff_subln_bwd, amt_diff_subln_bwd_blocks, amt_moe_train_fwd_balanced;
+                                14: amt_selective_scan_wide_train_fwd, amt_selective_scan_wide_ckpt_steps, amt_selective_scan_wide_bwd,
+                                    amt_selective_scan_wide_bwd_ws_floats, amt_silu_bwd */
 
 #ifdef __cplusplus
 extern "C" {
@@ -551,6 +553,31 @@ int64_t amt_dwconv1d_silu_bwd_ws_floats(int32_t B, int32_t L, int32_t C, int32_t
 int32_t amt_dwconv1d_silu_bwd(const float* dy, int32_t lddy, const float* x, int32_t ldx, const float* w, const float* bias,
                               float* dx, int32_t lddx, float* dw, float* dbias, float* ws, int32_t B, int32_t L, int32_t C,
                               int32_t K, int32_t reverse, void* stream);
+/* ---- training the wide-state heads ('moemamba': d_state = d_hidden): N = 32, 64, 128 or 256; N = 16 is refused with a pointer to
+ * the calls above.  Same rules: accurate expf / log1pf, no floating-point atomics, the same inputs give the same bits. ---- */
+/* amt_selective_scan_fwd at that N (y: the same bits) that also writes y_pre (B*L, ld_ypre) and h_chunks [B][ceil(L / I)][ED][N], the
+ * state at the start of every I-step chunk in walking order, I = amt_selective_scan_wide_ckpt_steps(N) = 32 (two of the kernel's
+ * 16-step passes; 0 for an N the call refuses). */
+int32_t amt_selective_scan_wide_ckpt_steps(int32_t N);
+int32_t amt_selective_scan_wide_train_fwd(const float* x, int32_t ldx, const float* delta_raw, int32_t ld_delta, const float* dt_bias,
+                                          const float* A_log, const float* Bm, const float* Cm, int32_t ld_bc, const float* D,
+                                          const float* z, int32_t ldz, float* y, int32_t ldy, float* y_pre, int32_t ld_ypre,
+                                          float* h_chunks, int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse,
+                                          void* stream);
+/* amt_selective_scan_bwd's outputs at that N.  One workgroup per (16 channels, clip, 16 states).  ws:
+ * amt_selective_scan_wide_bwd_ws_floats(B, L, ED, N) floats = ceil(ED / 16) per-block copies of dB | dC (B*L x 2N each), per-clip
+ * partials of dA (ED x N) and dD (ED), and N / 16 per-slice partials (B*L x ED each) of d delta and of the scan's part of dx; a second
+ * launch adds each in index order and does the element-wise part (softplus', dz, the D x and Mamba+ terms of dx) once. */
+int64_t amt_selective_scan_wide_bwd_ws_floats(int32_t B, int32_t L, int32_t ED, int32_t N);
+int32_t amt_selective_scan_wide_bwd(const float* dout, int32_t ld_dout, const float* x, int32_t ldx, const float* delta_raw,
+                                    int32_t ld_delta, const float* dt_bias, const float* A_log, const float* Bm, const float* Cm,
+                                    int32_t ld_bc, const float* D, const float* z, int32_t ldz, const float* y_pre, int32_t ld_ypre,
+                                    const float* h_chunks, float* dx, int32_t lddx, float* ddraw, int32_t ld_ddraw, float* dz,
+                                    int32_t lddz, float* dBm, float* dCm, int32_t ld_dbc, float* dA_log, float* dD, float* ws,
+                                    int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse, void* stream);
+/* da[i] = dy[i] s (1 + a[i] (1 - s)), s = sigmoid(a[i]) with the accurate expf: the SiLU's derivative at the pre-activation a, the one
+ * launch the backward of CNN_GRU's Conv1d + SiLU front (autograd.ConvSiluFn) adds to the GEMMs. */
+int32_t amt_silu_bwd(const float* dy, const float* a, float* da, int64_t n, void* stream);
 /* out[row] = [a[row][0:da] | b[row][0:db] | 0 ...] (ld_out columns): cat(semantic, emotion) of get_feature
  * (video_regression.py:199-216), zero-padded to the GEMM's K step. */
 int32_t amt_concat2_fwd(const float* a, int32_t da, const float* b, int32_t db, float* out, int32_t rows, int32_t ld_out,

@@ -13,9 +13,13 @@ import sys
 KINDS = (("moe_wgrad", "mixture layer: grouped weight-gradient product (moe_wgrad_kernel / _reduce)"),
          ("moe_bwd", "mixture layer: backward's row kernels (moe_bwd_dy / dlogit / act / dx)"),
          ("moe_", "mixture layer: router, plan, gating, combine"),
+         ("selective_scan_wide_bwd", "wide scan backward (selective_scan_wide_bwd_kernel)"),
+         ("scan_wide_bwd_reduce", "wide scan backward's ordered sums and element-wise part (scan_wide_bwd_reduce_kernel)"),
+         ("selective_scan_wide_kernel", "wide scan forward (selective_scan_wide_kernel<NS, true>)"),
          ("selective_scan_bwd", "scan backward (selective_scan_bwd_kernel)"), ("scan_bwd_reduce", "scan backward's ordered sums (scan_bwd_reduce_kernel)"),
          ("selective_scan_kernel", "scan forward (selective_scan_kernel<16, true>)"), ("dwconv_silu_bwd", "conv backward (dwconv_silu_bwd / _reduce)"),
          ("dwconv_silu_dacc", "conv backward (dwconv_silu_dacc_kernel)"), ("dwconv_silu", "conv forward (dwconv_silu_kernel)"),
+         ("silu_bwd_kernel", "dense conv front's SiLU derivative (silu_bwd_kernel)"), ("norm_bwd_kernel<true>", "RMSNorm backward"),
          ("norm_bwd_kernel<false>", "LayerNorm backward"), ("norm_kernel", "LayerNorm forward"),
          ("rnn_seq_bwd", "recurrence backward (rnn_seq_bwd_kernel)"), ("rnn_seq_train", "recurrence forward (rnn_seq_train_kernel)"),
          ("reg_loss", "fused loss (reg_loss_kernel)"), ("gemm_f32_kernel", "dense GEMM (gemm_f32_kernel)"), ("decode_gemm", "skinny GEMM"),

@@ -146,16 +146,23 @@ SIGNATURES = {
     "amt_diff_subln_bwd_blocks": [_I, _I],
     "amt_diff_subln_bwd": [_P] * 10 + [_I, _I, _F, _F, _P],
     "amt_moe_train_fwd_balanced": [_P] * 22 + [_I] * 6 + [_P, _P, _F, _P],
+    "amt_selective_scan_wide_ckpt_steps": [_I],
+    "amt_selective_scan_wide_train_fwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
+    "amt_selective_scan_wide_bwd_ws_floats": [_I, _I, _I, _I],
+    "amt_selective_scan_wide_bwd": [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P,
+                                    _P, _I, _I, _I, _I, _I, _I, _P],
+    "amt_silu_bwd": [_P, _P, _P, C.c_int64, _P],
 }
 _RESTYPES = {"amt_last_error": C.c_char_p, "amt_decode_step_bytes": C.c_int64, "amt_moe_scratch_floats": C.c_int64, "amt_moe_topk_scratch_floats": C.c_int64,
              "amt_v2_step_ws_floats": C.c_int64, "amt_v2_step_batch_ws_floats": C.c_int64, "amt_moe_ep_expert_scratch_floats": C.c_int64,
              "amt_chord_loss_ws_floats": C.c_int64, "amt_attn_bwd_ws_floats": C.c_int64, "amt_selective_scan_bwd_ws_floats": C.c_int64,
              "amt_dwconv1d_silu_bwd_ws_floats": C.c_int64, "amt_moe_train_scratch_floats": C.c_int64, "amt_moe_bwd_ws_floats": C.c_int64,
-             "amt_glu_train_scratch_floats": C.c_int64, "amt_glu_bwd_ws_floats": C.c_int64}
+             "amt_glu_train_scratch_floats": C.c_int64, "amt_glu_bwd_ws_floats": C.c_int64,
+             "amt_selective_scan_wide_bwd_ws_floats": C.c_int64}
 _NO_STATUS = set(_RESTYPES) | {"amt_abi_version", "amt_v2_last_step_launches", "amt_gemm_route", "amt_attn_route", "amt_moe_wgrad_splits",
-                                  "amt_rmsnorm_bwd_blocks", "amt_diff_subln_bwd_blocks"}
+                                  "amt_rmsnorm_bwd_blocks", "amt_diff_subln_bwd_blocks", "amt_selective_scan_wide_ckpt_steps"}
 
-ABI_VERSION = 13        # AMT_ABI_VERSION of include/amt_hip.h these prototypes were written against
+ABI_VERSION = 14        # AMT_ABI_VERSION of include/amt_hip.h these prototypes were written against
 
 _lib = None
 

@@ -1,5 +1,5 @@
 """`torch.autograd.Function`s over the library calls: what `VideoRegression` is built from in the training state
-(regModel 'lstm' / 'bilstm' / 'gru' / 'bigru' / 'bimamba+' / 'bimamba' / 'moe_bimamba+' / 'sharedmoe_bimamba+'), so that `loss.backward()` and any torch optimiser work on the
+(every regModel; 'mamba' / 'mamba+' / 'moemamba' / 'cnngru' / 'cnnbigru' after `enable_training()`), so that `loss.backward()` and any torch optimiser work on the
 module's own parameters.
 
     LinearFn          y = act(x w^T + b) (+ resid), act 0 none / 1 ReLU / 2 sigmoid   amt_linear_ex_fwd; backward: two GEMMs
@@ -9,6 +9,8 @@ module's own parameters.
                       backward: amt_rnn_seq_bwd + GEMMs
     MambaBlockFn      one MambaBlock (+ the layer's residual)           amt_linear_ex_fwd, amt_dwconv1d_silu_fwd,
                       amt_selective_scan_train_fwd; backward: amt_selective_scan_bwd, amt_dwconv1d_silu_bwd + GEMMs
+                      (more than 16 states per channel: amt_selective_scan_wide_train_fwd / amt_selective_scan_wide_bwd)
+    ConvSiluFn        CNN_GRU's Conv1d(d, d, 7, padding 3) + SiLU       7 x amt_linear_ex_fwd; backward: the same, amt_silu_bwd + GEMMs
     MoEFn             one MoELayer / SharedMoELayer (the mixture heads' FFN)  amt_moe_train_fwd; backward: amt_moe_bwd (grouped GEMMs
                       for the data gradients, the grouped weight-gradient product of csrc/moe_train_kernels.h for the experts' parameters)
     RegLossFn         SmoothL1 + BCE and both gradients                 amt_reg_loss_fwd_bwd
@@ -192,8 +194,9 @@ class MambaBlockFn(torch.autograd.Function):
     `wx` (R + 2N rounded up to 4, ED) are their zero-padded copies, the tensors the GEMMs read.  version 1: the Mamba+ gate; reverse:
     the block of the time-flipped sequence, un-flipped.
 
-    Saved: x, xz, xc, dbc, draw, the gated and the un-gated scan output and one state per 32 steps (B * ceil(L / 32) * ED * N floats);
-    the states in between are recomputed by the backward."""
+    Saved: x, xz, xc, dbc, draw, the gated and the un-gated scan output and one state per checkpoint interval I = ops.scan_ckpt_steps(N)
+    (B * ceil(L / I) * ED * N floats); the states in between are recomputed by the backward.  N = 16 runs amt_selective_scan_train_fwd /
+    amt_selective_scan_bwd, N = 32 .. 256 ('moemamba') the wide-state pair; d_conv up to 8."""
 
     @staticmethod
     def forward(ctx, x, resid, B, L, version, reverse, wdt, wx, in_w, in_b, conv_w, conv_b, xproj_w, dt_w, dt_b, A_log, D, out_w, out_b):
@@ -245,6 +248,76 @@ class MambaBlockFn(torch.autograd.Function):
                 d_in_wb[:, :d].contiguous(), d_in_wb[:, d].contiguous(), d_cw.view(ED, 1, -1), d_cb, d_x_w,
                 d_dt_wb[:, :R].contiguous(), d_dt_wb[:, R].contiguous(), dA_log, dD,
                 d_out_wb[:, :ED].contiguous(), d_out_wb[:, ED].contiguous())
+
+
+class ConvSiluFn(torch.autograd.Function):
+    """CNN_GRU's Conv1d(d, d, K = 7, padding K // 2) + SiLU over time on rows x (B*S, d): `VideoRegression._conv7_silu`'s launches.
+
+    apply(x, B, S, weight (d, d, K), bias (d), taps=None).  `taps` = (per tap j the contiguous W[:, :, j], per tap its transpose), the
+    tensors the GEMMs read, as the module keeps them in its derived-table cache (`VideoRegression._conv_taps`); None: they are made
+    here, zero-padded where d is no multiple of 32.  Forward: the clips laid end to end with K // 2 zero frames on each side, K accumulating
+    GEMMs (tap j of output row r reads padded row r + j), the SiLU on the last; rows between two clips are computed and thrown away.
+    A d that is no multiple of 32 is zero-padded to one for the GEMM's K.
+    Saved: the padded input and the taps.  Backward: the pre-activation again (the same GEMMs, no activation), da = dy silu'(a) (amt_silu_bwd; dy is
+    zero on the thrown-away rows, so they reach neither dx nor dW), dx as K accumulating GEMMs over da with W[:, :, j] transposed,
+    dW | db as one `mm_tn(da, [x shifted by 0 | ... | x shifted by K - 1], ones=True)`."""
+
+    @staticmethod
+    def _taps(W, dp):
+        K = W.shape[2]
+        return tuple(_padded(W[:, :, j], dp) for j in range(K)), tuple(_padded(W[:, :, j].t(), dp) for j in range(K))
+
+    @staticmethod
+    def _gemms(flat, taps, bias, M, act):
+        K = len(taps)
+        acc = None
+        for j in range(K):
+            acc = ops.linear_ex(flat[j:j + M], taps[j], bias if j == 0 else None, resid=acc, act=act if j == K - 1 else 0)
+        return acc
+
+    @staticmethod
+    def forward(ctx, x, B, S, weight, bias, taps=None):
+        d, K = weight.shape[0], weight.shape[2]
+        pad, dp = K // 2, _ceil32(d)
+        assert K % 2 == 1 and x.shape == (B * S, d)
+        b = bias.detach()
+        fwd_taps, bwd_taps = ConvSiluFn._taps(weight.detach(), dp) if taps is None else taps
+        xp = torch.zeros(B, S + 2 * pad, dp, device=x.device, dtype=torch.float32)
+        xp[:, pad:pad + S, :d] = x.view(B, S, d)
+        flat = xp.view(B * (S + 2 * pad), dp)
+        M = flat.shape[0] - 2 * pad
+        acc = ConvSiluFn._gemms(flat, fwd_taps, b, M, 3)
+        out = torch.zeros(B, S + 2 * pad, d, device=x.device, dtype=torch.float32)
+        out.view(-1, d)[:M] = acc
+        ctx.dims = (B, S, d, K)
+        ctx.save_for_backward(flat, bias, *fwd_taps, *bwd_taps)
+        return out[:, :S].contiguous().view(B * S, d)
+
+    @staticmethod
+    def backward(ctx, dy):
+        flat, bias, *taps = ctx.saved_tensors
+        B, S, d, K = ctx.dims
+        fwd_taps, bwd_taps = taps[:K], taps[K:]
+        b = bias.detach()
+        pad, dp = K // 2, flat.shape[1]
+        rows = flat.shape[0]
+        M = rows - 2 * pad
+        a = ConvSiluFn._gemms(flat, fwd_taps, b, M, 0)
+        dyp = torch.zeros(B, S + 2 * pad, d, device=dy.device, dtype=torch.float32)
+        dyp[:, :S] = dy.view(B, S, d)
+        da = ops.silu_bwd(dyp.view(rows, d)[:M], a)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            # padded row q read by output row q - j through tap j: d flat[q] = sum_j da[q - j] W[:, :, j], da zero outside [0, M)
+            dap = torch.zeros(M + 2 * (K - 1), dp, device=dy.device, dtype=torch.float32)
+            dap[K - 1:K - 1 + M, :d] = da
+            acc = None
+            for j in range(K):
+                acc = ops.linear_ex(dap[K - 1 - j:K - 1 - j + rows], bwd_taps[j], resid=acc)
+            dx = acc.view(B, S + 2 * pad, d)[:, pad:pad + S].reshape(B * S, d)
+        shifted = torch.cat([flat[j:j + M, :d] for j in range(K)], dim=1)            # (M, K d): column j d + i = x[r + j][i]
+        dwb = mm_tn(da, shifted, ones=True)                                          # (d, K d + 1): dW[o][i][j] at column j d + i | db
+        return dx, None, None, dwb[:, :K * d].reshape(d, K, d).permute(0, 2, 1).contiguous(), dwb[:, K * d].contiguous(), None
 
 
 class RegLossFn(torch.autograd.Function):

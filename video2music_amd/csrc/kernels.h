@@ -253,6 +253,8 @@ constexpr int SCAN_TCH = 32;            // time steps per chunk of the N = 16 sc
 constexpr int SCAN_CPB = 16;            // channels per 256-thread block of the scan kernels
 int32_t amt_launch_selective_scan(const ScanParams& p, hipStream_t stream);
 int32_t amt_launch_selective_scan_train(const ScanParams& p, hipStream_t stream);      // N = 16 only; fills ypre and hck too
+constexpr int SCAN_WIDE_CKPT = 32;      // the wide-state training scan's checkpoint interval: two of its 16-step passes
+int32_t amt_launch_selective_scan_wide_train(const ScanParams& p, hipStream_t stream); // N = 32 .. 256; hck every SCAN_WIDE_CKPT steps
 // out[row] = [a[row][0:da] | b[row][0:db] | 0-pad to ld_out]
 int32_t amt_launch_concat2(const float* a, int da, const float* b, int db, float* out, int rows, int ld_out, hipStream_t stream);
 

@@ -123,7 +123,9 @@ __global__ __launch_bounds__(CPB * N) void selective_scan_kernel(ScanParams p) {
 // The same scan for wider state spaces, N = 16 * NS states per channel ('moemamba' builds its blocks with d_state = d_hidden,
 // video_regression.py:143-147): a channel still owns 16 lanes, each lane carries NS states; operands are staged straight into
 // LDS (no register prefetch -- B and C rows alone are 2 * TCH * N floats per pass).
-template <int NS>
+// TRAIN: the same arithmetic, and two more stores for amt_selective_scan_wide_bwd (mamba_bwd.hip): the un-gated y_t and, every
+// SCAN_WIDE_CKPT steps (two passes), the state at the start of the pass, hck [B][ceil(L / SCAN_WIDE_CKPT)][ED][N] in walking order.
+template <int NS, bool TRAIN>
 __global__ __launch_bounds__(CPB * 16) void selective_scan_wide_kernel(ScanParams p) {
     constexpr int N = 16 * NS, NT = CPB * 16, TW = 16;      // TW steps staged per pass (B and C rows: 2 * TW * N floats)
     __shared__ float sx[TW][CPB], sd[TW][CPB], sz[TW][CPB], sy[TW][CPB], sB[TW][N], sC[TW][N];
@@ -155,6 +157,11 @@ __global__ __launch_bounds__(CPB * 16) void selective_scan_wide_kernel(ScanParam
             sC[s][nn] = s < steps ? p.Cm[row * p.ldbc + nn] : 0.f;
         }
         __syncthreads();
+        if (TRAIN && s0 % SCAN_WIDE_CKPT == 0 && ch < p.ED) {
+            float* ck = p.hck + (((size_t)b * ((p.L + SCAN_WIDE_CKPT - 1) / SCAN_WIDE_CKPT) + s0 / SCAN_WIDE_CKPT) * p.ED + ch) * N;
+#pragma unroll
+            for (int j = 0; j < NS; ++j) ck[j * 16 + n] = h[j];
+        }
 #pragma unroll 2
         for (int s = 0; s < TW; ++s) {
             const float delta = sd[s][cl], xv = sx[s][cl];
@@ -176,6 +183,7 @@ __global__ __launch_bounds__(CPB * 16) void selective_scan_wide_kernel(ScanParam
                 const float xv = sx[s][cc], zs = sz[s][cc];
                 const float yv = sy[s][cc] + p.D[c0 + cc] * xv;
                 p.y[((size_t)b * p.L + t) * p.ldy + c0 + cc] = p.version == 1 ? yv * zs + xv * (1.0f - 1.0f / (1.0f + __expf(-zs))) : yv * zs;
+                if (TRAIN) p.ypre[((size_t)b * p.L + t) * p.ldyp + c0 + cc] = yv;
             }
         }
         __syncthreads();
@@ -212,10 +220,10 @@ int32_t amt_launch_selective_scan(const ScanParams& p, hipStream_t stream) {
     const dim3 grid(cdiv(p.ED, CPB), p.B), block(CPB * 16);
     switch (p.N) {
         case 16: hipLaunchKernelGGL((selective_scan_kernel<16, false>), grid, block, 0, stream, p); break;
-        case 32: hipLaunchKernelGGL(selective_scan_wide_kernel<2>, grid, block, 0, stream, p); break;
-        case 64: hipLaunchKernelGGL(selective_scan_wide_kernel<4>, grid, block, 0, stream, p); break;
-        case 128: hipLaunchKernelGGL(selective_scan_wide_kernel<8>, grid, block, 0, stream, p); break;
-        default: hipLaunchKernelGGL(selective_scan_wide_kernel<16>, grid, block, 0, stream, p); break;
+        case 32: hipLaunchKernelGGL((selective_scan_wide_kernel<2, false>), grid, block, 0, stream, p); break;
+        case 64: hipLaunchKernelGGL((selective_scan_wide_kernel<4, false>), grid, block, 0, stream, p); break;
+        case 128: hipLaunchKernelGGL((selective_scan_wide_kernel<8, false>), grid, block, 0, stream, p); break;
+        default: hipLaunchKernelGGL((selective_scan_wide_kernel<16, false>), grid, block, 0, stream, p); break;
     }
     AMT_LAUNCH_CHECK();
     return 0;
@@ -228,6 +236,24 @@ int32_t amt_launch_selective_scan_train(const ScanParams& p, hipStream_t stream)
     AMT_CHECK_ARG(p.ldx >= p.ED && p.ldd >= p.ED && p.ldz >= p.ED && p.ldy >= p.ED && p.ldyp >= p.ED && p.ldbc >= p.N,
                   "selective_scan_train: bad leading dimension");
     hipLaunchKernelGGL((selective_scan_kernel<16, true>), dim3(cdiv(p.ED, CPB), p.B), dim3(CPB * 16), 0, stream, p);
+    AMT_LAUNCH_CHECK();
+    return 0;
+}
+
+int32_t amt_launch_selective_scan_wide_train(const ScanParams& p, hipStream_t stream) {
+    AMT_CHECK_ARG(p.B > 0 && p.L > 0 && p.ED > 0, "selective_scan_wide_train: bad shape B=%d L=%d ED=%d", p.B, p.L, p.ED);
+    AMT_CHECK_ARG(p.N != 16, "selective_scan_wide_train: d_state=16 trains through amt_selective_scan_train_fwd / amt_selective_scan_bwd");
+    AMT_CHECK_ARG(p.N == 32 || p.N == 64 || p.N == 128 || p.N == 256, "selective_scan_wide_train: d_state=%d not in {32, 64, 128, 256}", p.N);
+    AMT_CHECK_ARG(p.ldx >= p.ED && p.ldd >= p.ED && p.ldz >= p.ED && p.ldy >= p.ED && p.ldyp >= p.ED && p.ldbc >= p.N,
+                  "selective_scan_wide_train: bad leading dimension");
+    AMT_CHECK_ARG(p.B <= 65535, "selective_scan_wide_train: B=%d exceeds the launch grid", p.B);
+    const dim3 grid(cdiv(p.ED, CPB), p.B), block(CPB * 16);
+    switch (p.N) {
+        case 32: hipLaunchKernelGGL((selective_scan_wide_kernel<2, true>), grid, block, 0, stream, p); break;
+        case 64: hipLaunchKernelGGL((selective_scan_wide_kernel<4, true>), grid, block, 0, stream, p); break;
+        case 128: hipLaunchKernelGGL((selective_scan_wide_kernel<8, true>), grid, block, 0, stream, p); break;
+        default: hipLaunchKernelGGL((selective_scan_wide_kernel<16, true>), grid, block, 0, stream, p); break;
+    }
     AMT_LAUNCH_CHECK();
     return 0;
 }
@@ -272,6 +298,24 @@ extern "C" int32_t amt_selective_scan_train_fwd(const float* x, int32_t ldx, con
     p.D = D; p.z = z; p.ldz = ldz; p.y = y; p.ldy = ldy; p.B = B; p.L = L; p.ED = ED; p.N = N; p.version = version; p.reverse = reverse;
     p.ypre = y_pre; p.ldyp = ld_ypre; p.hck = h_chunks;
     return amt_launch_selective_scan_train(p, (hipStream_t)stream);
+}
+
+extern "C" int32_t amt_selective_scan_wide_ckpt_steps(int32_t N) {
+    return N == 32 || N == 64 || N == 128 || N == 256 ? SCAN_WIDE_CKPT : 0;
+}
+
+extern "C" int32_t amt_selective_scan_wide_train_fwd(const float* x, int32_t ldx, const float* delta_raw, int32_t ld_delta, const float* dt_bias,
+                                                     const float* A_log, const float* Bm, const float* Cm, int32_t ld_bc, const float* D,
+                                                     const float* z, int32_t ldz, float* y, int32_t ldy, float* y_pre, int32_t ld_ypre,
+                                                     float* h_chunks, int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version,
+                                                     int32_t reverse, void* stream) {
+    AMT_CHECK_ARG(x && delta_raw && dt_bias && A_log && Bm && Cm && D && z && y && y_pre && h_chunks, "amt_selective_scan_wide_train_fwd: null pointer");
+    AMT_CHECK_ARG(version == 0 || version == 1, "amt_selective_scan_wide_train_fwd: version %d not in {0,1}", version);
+    ScanParams p{};
+    p.x = x; p.ldx = ldx; p.draw = delta_raw; p.ldd = ld_delta; p.dt_bias = dt_bias; p.A_log = A_log; p.Bm = Bm; p.Cm = Cm; p.ldbc = ld_bc;
+    p.D = D; p.z = z; p.ldz = ldz; p.y = y; p.ldy = ldy; p.B = B; p.L = L; p.ED = ED; p.N = N; p.version = version; p.reverse = reverse;
+    p.ypre = y_pre; p.ldyp = ld_ypre; p.hck = h_chunks;
+    return amt_launch_selective_scan_wide_train(p, (hipStream_t)stream);
 }
 
 extern "C" int32_t amt_concat2_fwd(const float* a, int32_t da, const float* b, int32_t db, float* out, int32_t rows, int32_t ld_out,

@@ -15,6 +15,16 @@
 // LDS, and over the ceil(ED / 16) blocks by a second launch that reads the workspace in a fixed order; dA and dD are per-(clip, block)
 // partials that the same second launch sums over the clips.  The same inputs give the same bits.
 // exp / sigmoid here are the accurate expf: the gradients are held to an fp64 yardstick at fp32 training noise.
+//
+//   amt_selective_scan_wide_bwd   the same for N = 32 / 64 / 128 / 256 states per channel ('moemamba': d_state = d_hidden), from
+//                                 amt_selective_scan_wide_train_fwd's y_pre and checkpoints (every 32 steps, the same interval)
+//   amt_silu_bwd                  da = dy silu'(a), the launch the backward of CNN_GRU's dense convolution front lacks
+// The wide backward is the N = 16 kernel run per slice of 16 states, grid (ceil(ED / 16), B, N / 16), and not a lane that owns
+// N / 16 states: hs[32] and as[32] per lane would become 32 N / 16 values each (1024 at N = 256), far past the register file, and a
+// checkpoint interval short enough to fit them would multiply the checkpoint memory (already B ceil(L / 32) ED N floats).  Sliced, the
+// register and LDS footprint is the N = 16 kernel's, and a B = 1 call has N / 16 times the workgroups.  The price is that every
+// slice forms softplus and the gate's dy again (element-wise, cheap beside the recurrence) and that the sums over all states cross
+// blocks: they go through the workspace as per-slice partials and are added in slice order by the second launch.
 #include "../../include/amt_hip.h"
 #include "amt_common.h"
 #include "kernels.h"
@@ -193,6 +203,190 @@ __global__ void scan_bwd_reduce_kernel(const float* __restrict__ ws, const float
     }
 }
 
+// ---- the wide-state scan (N = 32 .. 256 states per channel) ----
+// State slices: grid (ceil(ED / 16), B, N / 16); slice z does the kernel above's work on states [16 z, 16 z + 16) of its 16 channels.
+// What a slice cannot finish alone goes to the workspace and is finished by the second launch in index order: its 16 columns of the
+// per-channel-block dB | dC copies, its dA, and the two sums over all N states (d delta and the scan's part of dx) as per-slice
+// partials.  The element-wise part that does not depend on the state (softplus', dz, the D x and Mamba+ terms of dx) is done once,
+// in the second launch; slice 0 keeps the per-clip partial of dD, as the kernel above does.
+// The staging, the recomputation, the sweep and the dB | dC write-out below are selective_scan_bwd_kernel's, line for line, with the
+// state offset z16 and the row width NF in the indices: a change to either kernel belongs in both.  They are two kernels and not one
+// templated body because the merged body compiled to 225 (N = 16) and 210 (sliced) VGPRs against 171 and 157 apart, which takes the
+// sliced kernel from 3 waves per SIMD to 2.
+struct ScanWideBwdParams {
+    ScanBwdParams q;                    // q.ws: [B][nblk][L][2N] dB | dC, [B][ED][N] dA, [B][ED] dD, [N/16][B*L][ED] d delta, the same of dx
+    int N;
+};
+
+__global__ __launch_bounds__(NT) void selective_scan_wide_bwd_kernel(ScanWideBwdParams pw) {
+    const ScanBwdParams& p = pw.q;
+    __shared__ float sx[TCH][CPB], sd[TCH][CPB], sdy[TCH][CPB], sdd[TCH][CPB], sdxs[TCH][CPB], sB[TCH][N], sC[TCH][N];
+    __shared__ float pB[TCH][WAVES][N], pC[TCH][WAVES][N], sDp[NT / CPB][CPB];
+    const int NF = pw.N, z16 = blockIdx.z * N;
+    const int tid = threadIdx.x, n = tid % N, cl = tid / N, wave = tid / 64, lane = tid % 64;
+    const int c0 = blockIdx.x * CPB, b = blockIdx.y, nblk = gridDim.x, nch = (p.L + TCH - 1) / TCH;
+    const int ch = c0 + cl;
+    const float A = ch < p.ED ? -expf(p.A_log[(size_t)ch * NF + z16 + n]) : 0.f;
+    constexpr int EPT = TCH * CPB / NT, BPT = TCH * N / NT, ESTEP = NT / CPB;
+    const int ecc = tid % CPB, es = tid / CPB;
+    const bool ech = c0 + ecc < p.ED;
+    const float e_bias = ech ? p.dt_bias[c0 + ecc] : 0.f;
+    const size_t rows = (size_t)p.B * p.L;
+    float* wsBC = p.ws + ((size_t)b * nblk + blockIdx.x) * p.L * (2 * NF);
+    float* wsA = p.ws + (size_t)p.B * nblk * p.L * (2 * NF);
+    float* wsD = wsA + (size_t)p.B * p.ED * NF;
+    float* wsDd = wsD + (size_t)p.B * p.ED + (size_t)blockIdx.z * rows * p.ED;
+    float* wsDx = wsDd + (size_t)gridDim.z * rows * p.ED;
+    float dh = 0.f, dA = 0.f, dDp = 0.f;
+
+    for (int k = nch - 1; k >= 0; --k) {
+        const int s0 = k * TCH, steps = min(TCH, p.L - s0);
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            const int s = es + e * ESTEP;
+            const int t = p.reverse ? p.L - 1 - (s0 + s) : s0 + s;
+            const size_t row = (size_t)b * p.L + t;
+            float xv = 0.f, delta = 0.f, dy = 0.f;
+            if (s < steps && ech) {
+                xv = p.x[row * p.ldx + c0 + ecc];
+                const float dr = p.draw[row * p.ldd + c0 + ecc] + e_bias, zv = p.z[row * p.ldz + c0 + ecc];
+                delta = dr > 20.f ? dr : log1pf(expf(dr));
+                dy = p.dout[row * p.lddo + c0 + ecc] * (zv * sigmoid_acc(zv));
+                dDp += dy * xv;
+            }
+            sx[s][ecc] = xv; sd[s][ecc] = delta; sdy[s][ecc] = dy;
+        }
+#pragma unroll
+        for (int e = 0; e < BPT; ++e) {
+            const int i = tid + e * NT, s = i / N, nn = i % N;
+            const int t = p.reverse ? p.L - 1 - (s0 + s) : s0 + s;
+            const size_t row = (size_t)b * p.L + t;
+            sB[s][nn] = s < steps ? p.Bm[row * p.ldbc + z16 + nn] : 0.f;
+            sC[s][nn] = s < steps ? p.Cm[row * p.ldbc + z16 + nn] : 0.f;
+        }
+        const float h0 = ch < p.ED ? p.hck[(((size_t)b * nch + k) * p.ED + ch) * NF + z16 + n] : 0.f;
+        __syncthreads();
+        float hs[TCH], as[TCH];
+        {
+            float h = h0;
+#pragma unroll
+            for (int s = 0; s < TCH; ++s) {
+                const float delta = sd[s][cl];
+                as[s] = expf(delta * A);
+                h = as[s] * h + (delta * sB[s][n]) * sx[s][cl];
+                hs[s] = h;
+            }
+        }
+#pragma unroll
+        for (int s = TCH - 1; s >= 0; --s) {
+            const float delta = sd[s][cl], xv = sx[s][cl], dy = sdy[s][cl], Bn = sB[s][n], Cn = sC[s][n];
+            const float hp = s > 0 ? hs[s - 1] : h0;
+            dh += Cn * dy;
+            float cC = hs[s] * dy, cB = dh * delta * xv;
+            cC += __shfl_xor(cC, 16, 64); cC += __shfl_xor(cC, 32, 64);
+            cB += __shfl_xor(cB, 16, 64); cB += __shfl_xor(cB, 32, 64);
+            if (lane < N) { pC[s][wave][n] = cC; pB[s][wave][n] = cB; }
+            const float t1 = dh * as[s] * hp;
+            const float dd = group_sum<N>(A * t1 + dh * Bn * xv);
+            const float dxs = group_sum<N>(dh * delta * Bn);
+            if (n == 0) { sdd[s][cl] = dd; sdxs[s][cl] = dxs; }
+            dA += delta * t1;
+            dh = as[s] * dh;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            const int s = es + e * ESTEP;
+            const int t = p.reverse ? p.L - 1 - (s0 + s) : s0 + s;
+            const size_t row = (size_t)b * p.L + t;
+            if (s < steps && ech) {
+                wsDd[row * p.ED + c0 + ecc] = sdd[s][ecc];
+                wsDx[row * p.ED + c0 + ecc] = sdxs[s][ecc];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < BPT; ++e) {
+            const int i = tid + e * NT, s = i / N, nn = i % N;
+            const int t = p.reverse ? p.L - 1 - (s0 + s) : s0 + s;
+            if (s < steps) {
+                float vB = pB[s][0][nn], vC = pC[s][0][nn];
+#pragma unroll
+                for (int w = 1; w < WAVES; ++w) { vB += pB[s][w][nn]; vC += pC[s][w][nn]; }
+                wsBC[(size_t)t * (2 * NF) + z16 + nn] = vB;
+                wsBC[(size_t)t * (2 * NF) + NF + z16 + nn] = vC;
+            }
+        }
+        __syncthreads();
+    }
+    if (ch < p.ED) wsA[((size_t)b * p.ED + ch) * NF + z16 + n] = dA;
+    if (blockIdx.z == 0) {
+        sDp[es][ecc] = dDp;
+        __syncthreads();
+        if (tid < CPB && c0 + tid < p.ED) {
+            float v = sDp[0][tid];
+            for (int i = 1; i < NT / CPB; ++i) v += sDp[i][tid];
+            wsD[(size_t)b * p.ED + c0 + tid] = v;
+        }
+    }
+}
+
+// The second launch: dB | dC over the channel blocks, dA (times A) and dD over the clips, and per (row, channel) the slices' partials in
+// slice order with the element-wise part: ddraw = d delta softplus', dx = the scan's part + D dy (+ the Mamba+ term), dz.
+__global__ void scan_wide_bwd_reduce_kernel(ScanWideBwdParams pw, float* __restrict__ dBm, float* __restrict__ dCm, int ldbc,
+                                            float* __restrict__ dA_log, float* __restrict__ dD, int nblk) {
+    const ScanBwdParams& p = pw.q;
+    const int NF = pw.N, B = p.B, L = p.L, ED = p.ED, nsl = NF / N;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t rows = (size_t)B * L, nBC = rows * (2 * NF), nA = (size_t)ED * NF, nE = rows * ED;
+    const float* wsA = p.ws + (size_t)B * nblk * L * (2 * NF);
+    const float* wsD = wsA + (size_t)B * nA;
+    const float* wsDd = wsD + (size_t)B * ED;
+    const float* wsDx = wsDd + (size_t)nsl * nE;
+    if (idx < nBC) {
+        const size_t row = idx / (2 * NF);
+        const int j = (int)(idx % (2 * NF)), b = (int)(row / L), t = (int)(row % L);
+        float v = 0.f;
+        for (int blk = 0; blk < nblk; ++blk) v += p.ws[(((size_t)b * nblk + blk) * L + t) * (2 * NF) + j];
+        if (j < NF) dBm[row * ldbc + j] = v;
+        else dCm[row * ldbc + (j - NF)] = v;
+    } else if (idx < nBC + nA) {
+        const size_t i = idx - nBC;
+        float v = 0.f;
+        for (int b = 0; b < B; ++b) v += wsA[(size_t)b * nA + i];
+        dA_log[i] = v * -expf(p.A_log[i]);
+    } else if (idx < nBC + nA + (size_t)ED) {
+        const size_t c = idx - nBC - nA;
+        float v = 0.f;
+        for (int b = 0; b < B; ++b) v += wsD[(size_t)b * ED + c];
+        dD[c] = v;
+    } else if (idx < nBC + nA + (size_t)ED + nE) {
+        const size_t i = idx - nBC - nA - ED, row = i / ED;
+        const int c = (int)(i % ED);
+        float dd = 0.f, dxs = 0.f;
+        for (int s = 0; s < nsl; ++s) { dd += wsDd[(size_t)s * nE + i]; dxs += wsDx[(size_t)s * nE + i]; }
+        const float xv = p.x[row * p.ldx + c], dr = p.draw[row * p.ldd + c] + p.dt_bias[c], zv = p.z[row * p.ldz + c];
+        const float dov = p.dout[row * p.lddo + c], yp = p.ypre[row * p.ldyp + c];
+        const float sgz = sigmoid_acc(zv), zs = zv * sgz, dy = dov * zs;
+        float dzs = dov * yp, dxe = p.D[c] * dy;
+        if (p.version == 1) {
+            const float sg = sigmoid_acc(zs);
+            dzs -= dov * xv * (sg * (1.0f - sg));
+            dxe += dov * (1.0f - sg);
+        }
+        p.dz[row * p.lddz + c] = dzs * (sgz * (1.0f + zv * (1.0f - sgz)));
+        p.ddraw[row * p.lddd + c] = dd * (dr > 20.f ? 1.0f : sigmoid_acc(dr));
+        p.dx[row * p.lddx + c] = dxs + dxe;
+    }
+}
+
+// da = dy silu'(a)
+__global__ void silu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ a, float* __restrict__ da, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = a[i], sg = sigmoid_acc(v);
+    da[i] = dy[i] * (sg * (1.0f + v * (1.0f - sg)));
+}
+
 // ---- depthwise conv + SiLU ----
 // dacc = dy silu'(acc), acc the forward's pre-activation formed again
 __global__ void dwconv_silu_dacc_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx,
@@ -310,6 +504,53 @@ extern "C" int32_t amt_selective_scan_bwd(const float* dout, int32_t ld_dout, co
     AMT_LAUNCH_CHECK();
     hipLaunchKernelGGL(scan_bwd_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws, A_log, dBm, dCm,
                        ld_dbc, dA_log, dD, B, L, ED, nblk);
+    AMT_LAUNCH_CHECK();
+    return 0;
+}
+
+static_assert(SCAN_WIDE_CKPT == TCH, "the wide backward recomputes one checkpoint interval per chunk");
+
+extern "C" int64_t amt_selective_scan_wide_bwd_ws_floats(int32_t B, int32_t L, int32_t ED, int32_t Ns) {
+    if (B <= 0 || L <= 0 || ED <= 0 || !(Ns == 32 || Ns == 64 || Ns == 128 || Ns == 256)) return 0;
+    return (int64_t)B * cdiv(ED, CPB) * L * (2 * Ns) + (int64_t)B * ED * (Ns + 1) + 2 * (int64_t)(Ns / N) * B * L * ED;
+}
+
+extern "C" int32_t amt_selective_scan_wide_bwd(const float* dout, int32_t ld_dout, const float* x, int32_t ldx, const float* delta_raw,
+                                               int32_t ld_delta, const float* dt_bias, const float* A_log, const float* Bm, const float* Cm,
+                                               int32_t ld_bc, const float* D, const float* z, int32_t ldz, const float* y_pre, int32_t ld_ypre,
+                                               const float* h_chunks, float* dx, int32_t lddx, float* ddraw, int32_t ld_ddraw, float* dz,
+                                               int32_t lddz, float* dBm, float* dCm, int32_t ld_dbc, float* dA_log, float* dD, float* ws,
+                                               int32_t B, int32_t L, int32_t ED, int32_t Ns, int32_t version, int32_t reverse, void* stream) {
+    AMT_CHECK_ARG(dout && x && delta_raw && dt_bias && A_log && Bm && Cm && D && z && y_pre && h_chunks, "amt_selective_scan_wide_bwd: null input pointer");
+    AMT_CHECK_ARG(dx && ddraw && dz && dBm && dCm && dA_log && dD && ws, "amt_selective_scan_wide_bwd: null output pointer");
+    AMT_CHECK_ARG(B > 0 && L > 0 && ED > 0, "amt_selective_scan_wide_bwd: bad shape B=%d L=%d ED=%d", B, L, ED);
+    AMT_CHECK_ARG(Ns != N, "amt_selective_scan_wide_bwd: d_state=16 trains through amt_selective_scan_train_fwd / amt_selective_scan_bwd");
+    AMT_CHECK_ARG(Ns == 32 || Ns == 64 || Ns == 128 || Ns == 256, "amt_selective_scan_wide_bwd: d_state=%d not in {32, 64, 128, 256}", Ns);
+    AMT_CHECK_ARG(version == 0 || version == 1, "amt_selective_scan_wide_bwd: version %d not in {0,1}", version);
+    AMT_CHECK_ARG(ld_dout >= ED && ldx >= ED && ld_delta >= ED && ldz >= ED && ld_ypre >= ED && lddx >= ED && ld_ddraw >= ED && lddz >= ED &&
+                  ld_bc >= Ns && ld_dbc >= Ns, "amt_selective_scan_wide_bwd: bad leading dimension");
+    const int64_t total = (int64_t)B * L * (2 * Ns) + (int64_t)ED * (Ns + 1) + (int64_t)B * L * ED;     // elements of the second launch
+    AMT_CHECK_ARG(B <= 65535 && (total + 255) / 256 <= 0x7fffffff, "amt_selective_scan_wide_bwd: B=%d L=%d exceed the launch grid", B, L);
+    ScanWideBwdParams pw{};
+    ScanBwdParams& p = pw.q;
+    pw.N = Ns;
+    p.dout = dout; p.lddo = ld_dout; p.x = x; p.ldx = ldx; p.draw = delta_raw; p.ldd = ld_delta; p.dt_bias = dt_bias; p.A_log = A_log;
+    p.Bm = Bm; p.Cm = Cm; p.ldbc = ld_bc; p.D = D; p.z = z; p.ldz = ldz; p.ypre = y_pre; p.ldyp = ld_ypre; p.hck = h_chunks;
+    p.dx = dx; p.lddx = lddx; p.ddraw = ddraw; p.lddd = ld_ddraw; p.dz = dz; p.lddz = lddz; p.ws = ws;
+    p.B = B; p.L = L; p.ED = ED; p.version = version; p.reverse = reverse;
+    const int nblk = cdiv(ED, CPB);
+    hipLaunchKernelGGL(selective_scan_wide_bwd_kernel, dim3(nblk, B, Ns / N), dim3(NT), 0, (hipStream_t)stream, pw);
+    AMT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(scan_wide_bwd_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pw, dBm, dCm,
+                       ld_dbc, dA_log, dD, nblk);
+    AMT_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int32_t amt_silu_bwd(const float* dy, const float* a, float* da, int64_t n, void* stream) {
+    AMT_CHECK_ARG(dy && a && da, "amt_silu_bwd: null pointer");
+    AMT_CHECK_ARG(n > 0 && (n + 255) / 256 <= 0x7fffffff, "amt_silu_bwd: n=%lld", (long long)n);
+    hipLaunchKernelGGL(silu_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, a, da, n);
     AMT_LAUNCH_CHECK();
     return 0;
 }

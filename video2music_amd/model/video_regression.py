@@ -22,8 +22,14 @@ Training: for 'lstm' / 'bilstm' / 'gru' / 'bigru' and for 'bimamba+' / 'bimamba'
 state with gradients enabled build their result through the autograd Functions of `video2music_amd/autograd.py` on the module's own
 parameters (amt_rnn_seq_train_fwd / amt_rnn_seq_bwd; amt_selective_scan_train_fwd / amt_selective_scan_bwd / amt_dwconv1d_silu_bwd /
 amt_layernorm_bwd; the same GEMMs), so `loss.backward()` and a torch optimiser work; every other state and regModel runs the
-inference path above on detached parameters ('mamba' / 'mamba+' and 'moemamba' lack an RMSNorm backward).  'moe_bimamba+' /
-'sharedmoe_bimamba+' train too: their mixture layer goes through autograd.MoEFn (amt_moe_train_fwd / amt_moe_bwd).
+inference path above on detached parameters.  'moe_bimamba+' / 'sharedmoe_bimamba+' train too: their mixture layer goes through
+autograd.MoEFn (amt_moe_train_fwd / amt_moe_bwd).
+
+The other five heads train after `enable_training()` (an opt-in: a module that never called it runs the inference path in every
+state, as before): 'mamba' / 'mamba+' through autograd.RMSNormFn (amt_rmsnorm_bwd) around MambaBlockFn; 'moemamba' the same with
+its blocks' d_state = d_hidden states per channel on the wide-state training scan (amt_selective_scan_wide_train_fwd /
+amt_selective_scan_wide_bwd) and its mixture layer through MoEFn; 'cnngru' / 'cnnbigru' through autograd.ConvSiluFn (the seven GEMMs
+of the convolution front, amt_silu_bwd) in front of RnnLayerFn.
 """
 import math
 
@@ -182,6 +188,15 @@ class VideoRegression(HasDerived, nn.Module):
         self.regressor = nn.Linear(width, 2)
         self.classifier = nn.Sequential(nn.Linear(width, INSTRUMENT_SIZE), nn.Sigmoid())
         self.dropout_masks = None       # training state: multipliers to use in place of drawn ones (see _get_feature_train)
+        self._training_enabled = False  # enable_training(): the opt-in of the heads in OPT_IN_TRAINABLE
+
+    OPT_IN_TRAINABLE = ("mamba", "mamba+", "moemamba", "cnngru", "cnnbigru")
+
+    def enable_training(self):
+        """Lets 'mamba' / 'mamba+' / 'moemamba' / 'cnngru' / 'cnnbigru' build an autograd graph in the training state with gradients
+        enabled (the other heads do without being asked).  Eval mode and no_grad run what they ran before.  Returns self."""
+        self._training_enabled = True
+        return self
 
     def _derived(self):
         """-> (Fpad, Win, Wdt, Wx): zero-padded copies of the weights whose K (or row count) does not fit the GEMM's steps (rebuilt when
@@ -238,6 +253,18 @@ class VideoRegression(HasDerived, nn.Module):
         out.view(-1, d)[:M] = acc
         return out[:, :S].contiguous().view(B * S, d)
 
+    def _conv_taps(self):
+        """CNN_GRU's convolution weight as autograd.ConvSiluFn's GEMMs read it: per tap j the contiguous W[:, :, j], and per tap its
+        transpose (the backward's dx); rebuilt when the weight changes."""
+        conv = self.model.cnn[0]
+
+        def build():
+            W = conv.weight.detach()
+            K = W.shape[2]
+            return tuple(W[:, :, j].contiguous() for j in range(K)), tuple(W[:, :, j].t().contiguous() for j in range(K))
+
+        return self._tables.get("conv7", [conv.weight], build, wait=not self.training or not self._train_path())
+
     def _rnn_layer(self, l):
         """(W_ih, b_ih, W_hh, b_hh) of layer l with the directions stacked along the rows; rebuilt when a parameter changes."""
         names = [n + f"_l{l}" + sfx for sfx in (("", "_reverse") if self._dirs == 2 else ("",))
@@ -266,9 +293,12 @@ class VideoRegression(HasDerived, nn.Module):
 
     def _train_path(self):
         """The state in which the four recurrent regModels, 'bimamba+' / 'bimamba' and the two mixture heads build an autograd graph
-        (video2music_amd/autograd.py); every other state and regModel runs the inference kernels on detached parameters."""
-        return self.training and torch.is_grad_enabled() and self.regModel in ("lstm", "bilstm", "gru", "bigru", "bimamba+", "bimamba",
-                                                                                "moe_bimamba+", "sharedmoe_bimamba+")
+        (video2music_amd/autograd.py), and after `enable_training()` the five of OPT_IN_TRAINABLE too; every other state and regModel
+        runs the inference kernels on detached parameters."""
+        if not (self.training and torch.is_grad_enabled()):
+            return False
+        return (self.regModel in ("lstm", "bilstm", "gru", "bigru", "bimamba+", "bimamba", "moe_bimamba+", "sharedmoe_bimamba+")
+                or (self._training_enabled and self.regModel in self.OPT_IN_TRAINABLE))
 
     def _get_feature_train(self, vf, B, S, Win, Wdt, Wx):
         """get_feature's recurrent and bidirectional-Mamba branches through the autograd Functions, on the module's own parameters.
@@ -279,7 +309,12 @@ class VideoRegression(HasDerived, nn.Module):
         259-290): none here.  The multipliers (0 or 1 / (1 - p), shape (B*S, width)) are drawn by torch on the device, or taken in
         this order from `self.dropout_masks` when that is a list; the ones used are kept in `self.last_dropout_masks`.  Where no
         mask intervenes the launches are those of the inference path (residuals in the GEMM epilogues): at dropout 0 the result is
-        the same bits."""
+        the same bits.
+
+        After `enable_training()`: 'mamba' / 'mamba+' have the one site after in_proj (mamba.py's ResidualBlock has none); 'moemamba'
+        has it and then, per layer, the mixture layer's own sites in `dropout_rates()` order (inside the experts, on the chosen
+        experts' outputs, inside the shared expert), none after the mixture (ResidualMoE, mamba.py:117-129); 'cnngru' / 'cnnbigru'
+        have it, then the one after the convolution front's SiLU (CNN_GRU.cnn[2]), then the ones between the GRU layers."""
         from .. import autograd as AG
         given = list(self.dropout_masks) if self.dropout_masks is not None else None
         used = []
@@ -296,9 +331,12 @@ class VideoRegression(HasDerived, nn.Module):
         lin = self.in_proj[0]
         x = drop(AG.LinearFn.apply(vf, lin.weight, lin.bias, 0, Win), self.in_proj[1].p)
         if not self._rnn:
-            x = self._bimamba_train(x, B, S, drop, Wdt, Wx)
+            x = (self._bimamba_train if self._bidirectional else self._mamba_stack_train)(x, B, S, drop, Wdt, Wx)
             self.__dict__["last_dropout_masks"] = used
             return x.view(B, S, self.d_model)
+        if self._rnn_mod is not self.model:          # CNN_GRU.cnn: Conv1d + SiLU + Dropout
+            conv = self.model.cnn[0]
+            x = drop(AG.ConvSiluFn.apply(x, B, S, conv.weight, conv.bias, self._conv_taps()), self.model.cnn[2].p)
         gates = 4 if isinstance(self._rnn_mod, nn.LSTM) else 3
         for l in range(self.n_layers):
             names = [n + f"_l{l}" + sfx for sfx in (("", "_reverse") if self._dirs == 2 else ("",))
@@ -308,6 +346,30 @@ class VideoRegression(HasDerived, nn.Module):
                 x = drop(x, self._rnn_mod.dropout)
         self.__dict__["last_dropout_masks"] = used
         return x.view(B, S, self._dirs * self.d_model)
+
+    def _mamba_stack_train(self, x, B, S, drop, Wdt, Wx):
+        """The layers of 'mamba' / 'mamba+' (x = MambaBlock(RMSNorm(x)) + x, the sum in the out-projection's epilogue) and of 'moemamba'
+        (then x = moe_layer(RMSNorm(x)) + x) on the graph.  The mixture layer takes its masks from, and leaves them in, `drop`'s lists."""
+        from .. import autograd as AG
+        for i, lyr in enumerate(self.model.layers):
+            blk = lyr[0] if isinstance(lyr, nn.Sequential) else lyr
+            m = blk.mixer
+            if m.dt_rank + 2 * m.d_state < 32:
+                raise ValueError("dt_rank + 2*d_state < 32 is not supported")
+            h = AG.RMSNormFn.apply(x, None, blk.norm.weight, blk.norm.eps)
+            x = AG.MambaBlockFn.apply(h, x, B, S, self._version, False, Wdt[i], Wx[i], m.in_proj.weight, m.in_proj.bias, m.conv1d.weight,
+                                      m.conv1d.bias, m.x_proj.weight, m.dt_proj.weight, m.dt_proj.bias, m.A_log, m.D, m.out_proj.weight,
+                                      m.out_proj.bias)
+            if blk is not lyr:
+                layer = lyr[1].moe_layer
+                h = AG.RMSNormFn.apply(x, None, lyr[1].norm.weight, lyr[1].norm.eps)
+                n = sum(q > 0.0 for q in layer.dropout_rates())
+                layer.dropout_masks = [drop.given.pop(0) for _ in range(n)] if drop.given is not None else None
+                f = layer(h.view(B, S, self.d_model)).reshape(B * S, self.d_model)
+                layer.dropout_masks = None
+                drop.used.extend(layer.last_dropout_masks)
+                x = f + x
+        return x
 
     def _bimamba_train(self, x, B, S, drop, Wdt, Wx):
         """The encoder layers of 'bimamba+' (V1) / 'bimamba' (V0) on the graph; `drop(x, p)` applies the next dropout mask."""

@@ -336,21 +336,35 @@ def selective_scan(xc, draw, dt_bias, A_log, dbc, R, D, xz, B, L, version=1, rev
 SCAN_CHUNK = 32                 # steps between two state checkpoints of the training scan (SCAN_TCH of csrc/kernels.h)
 
 
+def scan_ckpt_steps(N):
+    """Steps between two state checkpoints of the training scan at N states per channel: SCAN_CHUNK at 16, the library's own figure
+    (amt_selective_scan_wide_ckpt_steps) for the wide-state kernels."""
+    if N == 16:
+        return SCAN_CHUNK
+    steps = _lib.call("amt_selective_scan_wide_ckpt_steps", N)
+    if steps <= 0:
+        raise ValueError(f"the training scan takes 16, 32, 64, 128 or 256 states per channel, not {N}")
+    return steps
+
+
 def selective_scan_train(xc, draw, dt_bias, A_log, dbc, R, D, xz, B, L, version=1, reverse=False):
     """`selective_scan` (the same bits) that also returns what `selective_scan_bwd` reads: y_pre (B*L, ED), the un-gated scan output,
-    and h_chunks (B, ceil(L / 32), ED, N), the state at the start of every chunk in walking order.  N = 16."""
+    and h_chunks (B, ceil(L / I), ED, N), the state at the start of every chunk of I = `scan_ckpt_steps(N)` steps in walking order.
+    N = 16: amt_selective_scan_train_fwd; N = 32 .. 256: amt_selective_scan_wide_train_fwd."""
     ED, N = A_log.shape
+    I = scan_ckpt_steps(N)
     y = torch.empty(B * L, ED, device=xc.device, dtype=torch.float32)
     y_pre = torch.empty_like(y)
-    h_chunks = torch.empty(B, (L + SCAN_CHUNK - 1) // SCAN_CHUNK, ED, N, device=xc.device, dtype=torch.float32)
-    _lib.call("amt_selective_scan_train_fwd", p(xc), ED, p(draw), ED, p(dt_bias), p(A_log), _off(dbc, R), _off(dbc, R + N), dbc.shape[1],
+    h_chunks = torch.empty(B, (L + I - 1) // I, ED, N, device=xc.device, dtype=torch.float32)
+    _lib.call("amt_selective_scan_train_fwd" if N == 16 else "amt_selective_scan_wide_train_fwd", p(xc), ED, p(draw), ED, p(dt_bias), p(A_log), _off(dbc, R), _off(dbc, R + N), dbc.shape[1],
               p(D), _off(xz, ED), xz.shape[1], p(y), ED, p(y_pre), ED, p(h_chunks), B, L, ED, N, int(version), int(reverse), _st())
     return y, y_pre, h_chunks
 
 
 def selective_scan_bwd(dout, xc, draw, dt_bias, A_log, dbc, R, D, xz, y_pre, h_chunks, dxz, ddbc, B, L, version=1, reverse=False):
-    """amt_selective_scan_bwd: from dout (B*L, ED) and what `selective_scan_train` read and left.  Fills the z half of dxz (B*L, 2 ED)
-    and columns R .. R + 2N of ddbc (B*L, ld) with dB | dC; returns dx (the gradient of xc), ddraw, dA_log, dD."""
+    """amt_selective_scan_bwd (N = 16) / amt_selective_scan_wide_bwd (N = 32 .. 256): from dout (B*L, ED) and what
+    `selective_scan_train` read and left.  Fills the z half of dxz (B*L, 2 ED) and columns R .. R + 2N of ddbc (B*L, ld) with dB | dC;
+    returns dx (the gradient of xc), ddraw, dA_log, dD."""
     ED, N = A_log.shape
     M = B * L
     assert dout.shape == (M, ED) and dxz.shape == (M, 2 * ED) and ddbc.shape == dbc.shape
@@ -358,11 +372,20 @@ def selective_scan_bwd(dout, xc, draw, dt_bias, A_log, dbc, R, D, xz, y_pre, h_c
         assert t.dtype == torch.float32 and t.is_contiguous()
     dx, ddraw = torch.empty_like(xc), torch.empty_like(draw)
     dA_log, dD = torch.empty_like(A_log), torch.empty_like(D)
-    ws = torch.empty(_lib.call("amt_selective_scan_bwd_ws_floats", B, L, ED, N), device=dout.device, dtype=torch.float32)   # a call's own scratch
-    _lib.call("amt_selective_scan_bwd", p(dout), ED, p(xc), ED, p(draw), ED, p(dt_bias), p(A_log), _off(dbc, R), _off(dbc, R + N),
+    name = "amt_selective_scan_bwd" if N == 16 else "amt_selective_scan_wide_bwd"
+    ws = torch.empty(_lib.call(name + "_ws_floats", B, L, ED, N), device=dout.device, dtype=torch.float32)   # a call's own scratch
+    _lib.call(name, p(dout), ED, p(xc), ED, p(draw), ED, p(dt_bias), p(A_log), _off(dbc, R), _off(dbc, R + N),
               dbc.shape[1], p(D), _off(xz, ED), xz.shape[1], p(y_pre), ED, p(h_chunks), p(dx), ED, p(ddraw), ED, _off(dxz, ED), dxz.shape[1],
               _off(ddbc, R), _off(ddbc, R + N), ddbc.shape[1], p(dA_log), p(dD), p(ws), B, L, ED, N, int(version), int(reverse), _st())
     return dx, ddraw, dA_log, dD
+
+
+def silu_bwd(dy, a):
+    """amt_silu_bwd: dy silu'(a), element-wise."""
+    assert dy.shape == a.shape and dy.dtype == a.dtype == torch.float32 and dy.is_contiguous() and a.is_contiguous()
+    da = torch.empty_like(a)
+    _lib.call("amt_silu_bwd", p(dy), p(a), p(da), a.numel(), _st())
+    return da
 
 
 def dwconv1d_silu_bwd(dy, xz, C_, w, bias, dxz, B, L, reverse=False):

@@ -1,7 +1,9 @@
 """``train_regression.py`` entry point (reference ``train_regression.py:35-236``, ``utilities/run_model_regression.py:10-68``):
 trains the loudness / note-density / instrument head ``VideoRegression(regModel = lstm | bilstm | gru | bigru)`` on the GPU; the
 Mamba heads ``bimamba+`` (the reference's default head) and ``bimamba`` train through the same loop from
-``python -m video2music_amd.train_regression_mamba`` (``main(argv, trainable=...)``).
+``python -m video2music_amd.train_regression_mamba`` (``main(argv, trainable=...)``), and every regModel, the one-directional Mamba
+stacks, ``moemamba`` and the CNN heads included, from ``python -m video2music_amd.train_regression_all``
+(``main(argv, trainable=..., opt_in=True)``).
 
 A step is the model's training-state forward (``video2music_amd/autograd.py``: the library's GEMMs and recurrence, saved
 activations), the fused loss (``losses.regression_train_loss``), ``backward()`` (``amt_rnn_seq_bwd`` and GEMMs) and a torch
@@ -61,11 +63,13 @@ class LrStepTracker:
         return self.invsqrt_dim * (1 / math.sqrt(step))
 
 
-UNBUILT = {"mamba": "the RMSNorm backward is not built", "mamba+": "the RMSNorm backward is not built",
-           "moemamba": "the mixture layer's and the RMSNorm backward are not built (nor the backward of its wide-state scan)",
+_ALL = "; it trains through python -m video2music_amd.train_regression_all"
+UNBUILT = {"mamba": "the RMSNorm backward is not built" + _ALL, "mamba+": "the RMSNorm backward is not built" + _ALL,
+           "moemamba": "the mixture layer's and the RMSNorm backward are not built (nor the backward of its wide-state scan)" + _ALL,
            "moe_bimamba+": "the mixture heads train through python -m video2music_amd.train_regression_moe",
            "sharedmoe_bimamba+": "the mixture heads train through python -m video2music_amd.train_regression_moe",
-           "cnngru": "the backward of its convolution front is not built", "cnnbigru": "the backward of its convolution front is not built"}
+           "cnngru": "the backward of its convolution front is not built" + _ALL,
+           "cnnbigru": "the backward of its convolution front is not built" + _ALL}
 
 
 def refuse(args, trainable=TRAINABLE):
@@ -160,7 +164,8 @@ def train_epoch(cur_epoch, model, data, order, batch_size, opt, lr_scheduler=Non
             print("")
 
 
-def main(argv=None, trainable=TRAINABLE):
+def main(argv=None, trainable=TRAINABLE, opt_in=False):
+    """opt_in: call the model's `enable_training()` (train_regression_all: the heads that build a graph only when asked to)."""
     args = parse_train_args(argv)[0]
     why = refuse(args, trainable)
     if why:
@@ -190,6 +195,8 @@ def main(argv=None, trainable=TRAINABLE):
         model.load_state_dict(torch.load(args.continue_weights, map_location="cpu"))
         start_epoch = args.continue_epoch
     model = model.to(device)
+    if opt_in:
+        model.enable_training()
 
     bs = max(1, args.batch_size)
     n_batches = (len(train_names) + bs - 1) // bs

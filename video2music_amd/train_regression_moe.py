@@ -5,9 +5,9 @@ model/video_regression.py:143-178) -- and the six heads ``train_regression_mamba
 Flags, loop, output files, CSV header and ``weights_regression_<regModel>/`` naming are ``train_regression``'s; ``-regModel``
 defaults to ``sharedmoe_bimamba+`` here.  A step runs ``autograd.MoEFn`` (``amt_moe_train_fwd``, ``amt_moe_bwd``: the grouped
 weight-gradient product of ``csrc/moe_bwd.hip`` and the library's grouped GEMMs) beside ``MambaBlockFn``, ``LayerNormFn`` and
-``LinearFn``.  Still refused, with the reason: ``moemamba`` (no backward of its wide-state scan; its RMSNorms are not wired to
-``autograd.RMSNormFn``), ``mamba`` / ``mamba+`` (their RMSNorms are not wired to ``autograd.RMSNormFn`` either: the library has the
-backward, ``amt_rmsnorm_bwd``, since the V1 chord models train), ``cnngru`` / ``cnnbigru``.
+``LinearFn``.  Refused here, with a pointer to ``python -m video2music_amd.train_regression_all``, which trains them: ``moemamba``,
+``mamba`` / ``mamba+``, ``cnngru`` / ``cnnbigru`` (they build a graph only after ``VideoRegression.enable_training()``, which that
+entry calls).
 
     python -m video2music_amd.train_regression_moe -dataset_dir ./dataset/ -epochs 50
 """
