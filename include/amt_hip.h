@@ -146,6 +146,10 @@ int32_t amt_generate_run(amt_handle* h, int32_t n_steps, float* logits_out, void
  *   "gemm_tile_pipeline" = 0 (any time): the skinny GEMMs of the decode step run their serial tile loop; 1, the default: the pipelined
  *   one (wave-uniform control, next k-tile's LDS reads and folded-FFN fix under this tile's MFMAs).  Part of the key of
  *   a captured graph; results are bit-identical either way.
+ *   "gemm_scalar_front" = 0 (any time): the skinny GEMMs of the decode step keep their generic front; 1, the default: the launches
+ *   of the folded step take the lean front (row, tile and weight addresses worked out on the scalar unit from one block of kernel
+ *   arguments).
+ *   Part of the key of a captured graph; results are bit-identical either way.
  *   "scalar_key_stream" = 0 (any time): the decode attentions of this handle keep the per-lane controlled key stream (every load
  *   clamped, every key guarded, one batch requested past a wave's last); 1, the default: the scalar-controlled one (per wave a scalar
  *   batch count, buffer loads on a scalar base, nothing requested behind the last batch).  Part of the key of a captured
@@ -275,6 +279,10 @@ int32_t amt_attn_decode_fold_fwd(const float* raw, int32_t ldq, float* kcache, f
  * of the pipelined one (next tile's reads and fix under this tile's MFMAs).  Same arithmetic in the same order: y_low / y_high are
  * bit-identical either way. */
 #define AMT_GEMM_PRO_SERIAL_LOOP 0x100
+/* Bit of amt_decode_gemm_args.pro: keep the kernel's generic front (per-lane 64-bit addresses, options decided at run time) where
+ * the launch would take the lean one (wave-uniform address work on the scalar unit; see "gemm_scalar_front").  The serial loop
+ * implies it.  What is loaded and summed is the same: y_low / y_high are bit-identical either way. */
+#define AMT_GEMM_PRO_GENERIC_FRONT 0x200
 typedef struct amt_decode_gemm_args {
     const float* x;  int32_t ldx;          /* first K1 columns of the rows (all K when x2 is null) */
     const float* x2; int32_t ldx2;         /* remaining K - K1 columns, or null */
@@ -282,13 +290,17 @@ typedef struct amt_decode_gemm_args {
     const float* w_low;  const float* bias_low;  const float* resid; int32_t relu;   /* y_low = act(x . w_low^T + b (+ resid)) */
     const float* w_high; const float* bias_high;                                     /* y_high = [x | x2] . w_high^T + b_high */
     int32_t n_low, n_high;
-    int32_t pro;                           /* 1: folded-FFN prologue (see above); | AMT_GEMM_PRO_SERIAL_LOOP: the serial tile loop */
+    int32_t pro;                           /* 1: folded-FFN prologue (see above); | AMT_GEMM_PRO_SERIAL_LOOP: the serial tile loop; | AMT_GEMM_PRO_GENERIC_FRONT */
     const float* fold_g; const float* fold_c; const float* ln_w; const float* ln_b;
     float* y_low; float* y_high;
     float* scratch_low; float* scratch_high;   /* packed copies of the weights, ceil(n/16)*16*K floats each */
     int32_t B; float eps;
 } amt_decode_gemm_args;
 int32_t amt_decode_gemm_ex_fwd(const amt_decode_gemm_args* a, void* stream);
+/* Whether amt_decode_gemm_ex_fwd would run this argument block on the kernel's lean front: 1 yes, 0 the generic front (a shape or
+ * option outside the lean front's range, or one of the two bits above), negative for a block amt_decode_gemm_ex_fwd refuses.  The
+ * launcher's own rule, evaluated on the host: no device, no stream, nothing is read through the pointers; a code, not a status. */
+int32_t amt_decode_gemm_ex_lean(const amt_decode_gemm_args* a);
 /* MultiheadGQA.forward (grouped_query_attention.py:286-358) without RoPE: query/key/value are the
  * caller's (L,B,E) buffers, weights in nn.Linear layout; scratch >= 4*L*B*E floats. */
 int32_t amt_gqa_fwd(const float* query, const float* key, const float* value,

@@ -5,7 +5,7 @@
 // GEMMs also the matrix phase of the workgroup (staging barrier -> the last wave's MFMA results; median and maximum over the
 // workgroups, the maximum being the high-column tiles that own every k-tile) and the shader clock during it (s_memtime ticks of
 // wave 0 between the two barriers over the 100 MHz stamps).
-// usage: ubench_step.bin [t = 511] [cache padding rows = 0] [1 = the serial tile loop of the skinny GEMMs]
+// usage: ubench_step.bin [t = 511] [cache padding rows = 0] [1 = the serial tile loop of the skinny GEMMs] [1 = their generic front]
 // (-DAMT_FIXUP_PACKED on the same command line builds the folded-FFN fix of the pipelined loop in packed pairs)
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DAMT_STAMPS tools/ubench_step.cpp \
 //        video2music_amd/csrc/{decode_gemm,attn_decode,tuning}.hip -o tools/ubench_step.bin
@@ -27,6 +27,7 @@ int main(int argc, char** argv) {
     const int t = argc > 1 ? atoi(argv[1]) : 511;
     const int cap = 1024 + (argc > 2 ? atoi(argv[2]) : 0);      // rows per (clip, head) of the self-attention cache: 1024 + padding
     const int serial = argc > 3 ? atoi(argv[3]) : 0;
+    const int generic = argc > 4 ? atoi(argv[4]) : 0;
     auto falloc = [](size_t n) { float* p; CK(hipMalloc(&p, n * 4)); CK(hipMemset(p, 0, n * 4)); return p; };
     float *ob = falloc(B * d), *xa = falloc(B * d), *xb = falloc(B * d), *u1 = falloc(B * d), *u2 = falloc(B * d), *u3 = falloc(B * d);
     float *qraw = falloc(B * d), *hraw = falloc(B * dff), *qkvraw = falloc(B * 3 * d), *vecs = falloc(16384);
@@ -48,7 +49,7 @@ int main(int argc, char** argv) {
         DecodeGemmParams g1{};
         g1.B = B; g1.eps = 1e-5f; g1.scale = 1.f; g1.x = ob; g1.ldx = d; g1.x2 = xa; g1.ldx2 = d; g1.K1 = d; g1.K = 2 * d;
         g1.Wp = p_sao; g1.bias = vecs; g1.resid = xa; g1.ldr = d; g1.y = u1; g1.ldy = d;
-        g1.n_split = d; g1.N = 2 * d; g1.Wp2 = pf_a; g1.bias2 = vecs; g1.y2 = qraw; g1.ldy2 = d; g1.serial_loop = serial;
+        g1.n_split = d; g1.N = 2 * d; g1.Wp2 = pf_a; g1.bias2 = vecs; g1.y2 = qraw; g1.ldy2 = d; g1.serial_loop = serial; g1.generic_front = generic;
         L.push_back({"G1  K=1024 N=1024", 0, g1, {}, (2 * d / 16) * 2, nullptr});
         AttnDecodeParams x{};
         x.k = kx; x.v = vx; x.o = ob; x.B = B; x.H = H; x.hd = hd; x.cap = S; x.n_keys = S;
@@ -62,7 +63,7 @@ int main(int argc, char** argv) {
         g3.B = B; g3.eps = 1e-5f; g3.scale = 1.f; g3.pro = 1; g3.x = hraw; g3.ldx = dff; g3.x2 = u2; g3.ldx2 = d;
         g3.K1 = dff; g3.K = dff + d; g3.fold_g = vecs; g3.fold_c = vecs; g3.ln_w = vecs; g3.ln_b = vecs;
         g3.Wp = p_l2; g3.bias = vecs; g3.y = u3; g3.ldy = d; g3.n_split = d; g3.N = 4 * d; g3.Wp2 = pf_c; g3.bias2 = vecs;
-        g3.y2 = qkvraw; g3.ldy2 = 3 * d; g3.serial_loop = serial;
+        g3.y2 = qkvraw; g3.ldy2 = 3 * d; g3.serial_loop = serial; g3.generic_front = generic;
         L.push_back({"G3  K=1536 N=2048", 0, g3, {}, (4 * d / 16) * 2, nullptr});
     }
     for (auto& l : L) {
@@ -83,8 +84,8 @@ int main(int argc, char** argv) {
     CK(hipStreamSynchronize(s));
     CK(hipEventRecord(a, s)); for (int w = 0; w < 10; ++w) CK(hipGraphLaunch(ge, s)); CK(hipEventRecord(b, s)); CK(hipStreamSynchronize(s));
     float ms; CK(hipEventElapsedTime(&ms, a, b));
-    printf("t = %d: %.1f us per step of %zu launches (stamped build; no sampling head; %s tile loop)\n", t, ms * 1e3 / (10.0 * steps), L.size(),
-           serial ? "serial" : "pipelined");
+    printf("t = %d: %.1f us per step of %zu launches (stamped build; no sampling head; tile loop: %s)\n", t, ms * 1e3 / (10.0 * steps), L.size(),
+           serial ? "serial" : generic ? "pipelined, generic front" : "pipelined, lean front");
     const char* gph[] = {"issue loads", "rows+prologue", "barrier", "weights+MFMA", "partials", "reduce+store"};
     const char* aph[] = {"prologue: query ready", "keys streamed (wave 0)", "group merge", "barrier", "final combine+store"};
     unsigned long long prev_end = 0;

@@ -86,6 +86,7 @@ SIGNATURES = {
     "amt_decode_linear_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "amt_attn_decode_fold_fwd": [_P, _I] + [_P] * 10 + [_I, _I, _I, _I, _P, _I, _I, _I, _F, _F, _P],
     "amt_decode_gemm_ex_fwd": [C.POINTER(DecodeGemmArgs), _P],
+    "amt_decode_gemm_ex_lean": [C.POINTER(DecodeGemmArgs)],
     "amt_gqa_fwd": [_P] * 15 + [_I] * 7 + [_F, _P],
     "amt_gqa_rope_fwd": [_P] * 15 + [_I] * 7 + [_F, _P, _I, _I, _P],
     "amt_moe_scratch_floats": [_I, _I, _I, _I],
@@ -159,7 +160,7 @@ _RESTYPES = {"amt_last_error": C.c_char_p, "amt_decode_step_bytes": C.c_int64, "
              "amt_dwconv1d_silu_bwd_ws_floats": C.c_int64, "amt_moe_train_scratch_floats": C.c_int64, "amt_moe_bwd_ws_floats": C.c_int64,
              "amt_glu_train_scratch_floats": C.c_int64, "amt_glu_bwd_ws_floats": C.c_int64,
              "amt_selective_scan_wide_bwd_ws_floats": C.c_int64}
-_NO_STATUS = set(_RESTYPES) | {"amt_abi_version", "amt_v2_last_step_launches", "amt_gemm_route", "amt_attn_route", "amt_moe_wgrad_splits",
+_NO_STATUS = set(_RESTYPES) | {"amt_abi_version", "amt_v2_last_step_launches", "amt_gemm_route", "amt_attn_route", "amt_decode_gemm_ex_lean", "amt_moe_wgrad_splits",
                                   "amt_rmsnorm_bwd_blocks", "amt_diff_subln_bwd_blocks", "amt_selective_scan_wide_ckpt_steps"}
 
 ABI_VERSION = 14        # AMT_ABI_VERSION of include/amt_hip.h these prototypes were written against

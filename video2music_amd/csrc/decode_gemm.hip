@@ -14,6 +14,7 @@
 //    fixed order through LDS (deterministic, no atomics);
 //  * the (normalised) input rows are staged once in LDS ([16][K+8] floats: conflict-free
 //    ds_read_b128 A-fragments).
+#include <limits.h>
 #include <stdlib.h>
 
 #include <mutex>
@@ -264,46 +265,119 @@ __device__ __forceinline__ f32x4 tiles_partial(const float* xa, const float* fg,
     return acc;
 }
 
+// a float4 at a wave-uniform base plus the lane's byte offset: `global_load_dwordx4 v, v_off, s[base:base+1]`, no per-lane 64-bit address
+// (the global address space spelled out: a base that went through an opaque asm is otherwise loaded from as a flat address)
+__device__ __forceinline__ float4 ld4_s(const char* sbase, unsigned lane_off) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) char* gptr;
+    const f4 t = *(const __attribute__((address_space(1))) f4*)((gptr)sbase + lane_off);
+    return make_float4(t.x, t.y, t.z, t.w);
+}
+
+// ... and through a buffer descriptor: a wave-uniform byte offset in an SGPR, the lane's in a VGPR (as attn_decode.hip's key stream)
+using wbuf_t = __amdgpu_buffer_rsrc_t;
+__device__ __forceinline__ float4 ld4_buf(wbuf_t r, unsigned voff, unsigned soff) {
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4 t = __builtin_bit_cast(f4, (u4)__builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
+    return make_float4(t.x, t.y, t.z, t.w);
+}
+
 // PIPE: the tile loop with wave-uniform control and one tile of read-ahead; false keeps the serial loop
 // (DecodeGemmParams::serial_loop: A/B and the bit-identity tests)
-template <int KCH, bool FULL, Pro PRO, bool PIPE>
+// LEAN: the scalar address front (amt_decode_gemm_lean_ok: two-source rows of whole 256-column chunks, packed weights, none of the
+// options below).  Between kernel entry and the last load request everything wave-uniform is SALU work on kernel arguments that
+// arrive in one round of scalar loads (DecodeGemmFront): the row, the side of K1 a chunk lies on, the column tile's weight base and
+// the clamped tile indices are scalars, a load is a scalar base plus ONE lane offset (lane * 16 bytes).  What is loaded, and
+// everything behind the loads, is the generic kernel's.
+template <int KCH, bool FULL, Pro PRO, bool PIPE, bool LEAN = false>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p) {
+    static_assert(!LEAN || (PIPE && FULL && (PRO == Pro::Plain || PRO == Pro::FoldedFfn)), "the lean front serves the folded chain's launches");
     extern __shared__ __attribute__((aligned(16))) float smem[];
 #ifdef AMT_STAMPS
     unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     STAMP(0);
-    const int K = p.K, LD = K + XPAD;
+    constexpr bool FFN = pro_folded(PRO), LN1 = pro_layernorm(PRO);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int nt = blockIdx.x, m0 = blockIdx.y * MT;
     float* xs = smem;                               // [16][LD]
+    // what the two fronts hand to the rest of the kernel
+    int K, LD, wave, nts, K1, kt_n, tpw, kt0, zg, grp;
+    bool high;
+    float* red;
+    float4 v[KCH], wt[KCH];
+    // FoldedGlu: at least one 256-column chunk belongs to the u half (two at K = 1536, where the launcher asks for K - K1 >= 512: one
+    // float4 more per lane would spill at the 128-VGPR budget of a 16-wave workgroup)
+    constexpr int GCH = PRO == Pro::FoldedGlu ? (KCH == 6 ? 4 : KCH > 1 ? KCH - 1 : 1) : KCH;
+    float4 gv[pro_gated(PRO) ? GCH : 1];
+    float4 g0[LN1 ? KCH : 1], h0[LN1 ? KCH : 1], g1[PRO == Pro::LayerNorm2 ? KCH : 1], h1[PRO == Pro::LayerNorm2 ? KCH : 1];
+    float4 gs_val = make_float4(0.f, 0.f, 0.f, 0.f), gs2_val = make_float4(0.f, 0.f, 0.f, 0.f);
+    int gs_vec = 0, gs_i = 0, gs2_vec = 0, gs2_i = 0;
+    if constexpr (LEAN) {
+        const DecodeGemmFront& f = p.front;
+        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const unsigned loff = (unsigned)lane * 16u;
+        wave = wv; zg = 0; grp = 0;
+        K = f.K; LD = f.LD; K1 = f.K1; nts = f.nts;
+        red = smem + f.red_off;
+        high = nt >= nts;
+        kt_n = high ? f.ktn_hi : f.ktn_lo; tpw = high ? f.tpw_hi : f.tpw_lo;
+        kt0 = wv * tpw;
+        // ---- 1. the row this wave stages (32-bit byte offsets: checked by the launcher) ----
+        const unsigned rc = (unsigned)min(m0 + wv, f.B - 1);
+        const char* xr = reinterpret_cast<const char*>(f.x) + rc * f.x_row_bytes;
+        const char* x2r = reinterpret_cast<const char*>(f.x2b) + rc * f.x2_row_bytes;
+#pragma unroll
+        for (int c = 0; c < KCH; ++c) {
+            // chunks 0-3 ride in the instruction's immediate offset; from the fourth on 4 KiB go into the base on the scalar unit (opaque:
+            // the compiler otherwise adds them to the lane's 64-bit address)
+            const char* side = (256 * c < K1 ? xr : x2r) + (c >= 4 ? 4096 : 0);
+            if (c >= 4) asm volatile("" : "+s"(side));
+            v[c] = ld4_s(side + 1024 * (c & 3), loff);
+        }
+        // rows first: the prologue's wait counts the loads behind them.  (A compiler barrier for memory operations, not a scheduling
+        // boundary: behind sched_barrier(0) the epilogue's kernel arguments are requested and waited for between the rows and the weights.)
+        asm volatile("" ::: "memory");
+        // ---- 2. folded FFN: wave w of the first K / 128 takes 256 columns of one of the two vectors (the others repeat the last of them) ----
+        if (FFN) {
+            const int gw = min(wv, (K >> 7) - 1), vec = gw >= (K >> 8) ? 1 : 0, col0 = (gw - vec * (K >> 8)) * 256;
+            const float* a = col0 < K1 ? (vec ? f.fold_c : f.fold_g) : (vec ? f.ln_bb : f.ln_wb);
+            gs_vec = vec; gs_i = col0 + lane * 4;
+            gs_val = ld4_s(reinterpret_cast<const char*>(a + col0), loff);
+            asm volatile("" ::: "memory");
+        }
+        // ---- 3. this wave's weight tiles (tile index clamped on the scalar unit) ----
+        // through a buffer descriptor on the column tile's k-tiles (`buffer_load_dwordx4 v, v_off, s[rsrc], s_off offen`): the tile part of
+        // the address is the scalar offset.  (As a pointer sum the compiler adds the lane offset first and each tile's 64-bit address on the VALU.)
+        const float* wb = (high ? f.Wp2 : f.Wp) + (size_t)((unsigned)((high ? nt - nts : nt) * kt_n) * 1024u) / 4;
+        const wbuf_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wb), 0, kt_n * 1024, 0x00020000);
+#pragma unroll
+        for (int i = 0; i < KCH; ++i) wt[i] = ld4_buf(wr, loff, (unsigned)min(kt0 + i, kt_n - 1) * 1024u);
+    } else {
+    wave = tid >> 6;
+    K = p.K; LD = K + XPAD;
     // [16 waves][4 r][64 lanes] partial tiles in a region of their own (behind the staged rows and the folded-FFN vectors): a wave stores its
     // partials as soon as its MFMAs are done, with no barrier in between (sharing the rows' region cost one: +0.6 % tokens/s without it)
-    constexpr bool FFN = pro_folded(PRO), LN1 = pro_layernorm(PRO);
-    float* red = smem + MT * LD + (PRO == Pro::FoldedFfn ? 2 * K + 2 * MT : PRO == Pro::FoldedGlu ? 2 * K + 2 * p.K1 : 0);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nt = blockIdx.x, m0 = blockIdx.y * MT;
+    red = smem + MT * LD + (PRO == Pro::FoldedFfn ? 2 * K + 2 * MT : PRO == Pro::FoldedGlu ? 2 * K + 2 * p.K1 : 0);
     // column split: tiles below n_split multiply the first K1 input columns by Wp, the others all K by Wp2
-    const int nts = p.n_split >> 4;
-    const bool high = p.n_split > 0 && nt >= nts;
-    const int K1 = p.x2 ? p.K1 : K;                 // first column taken from x2
+    nts = p.n_split >> 4;
+    high = p.n_split > 0 && nt >= nts;
+    K1 = p.x2 ? p.K1 : K;                           // first column taken from x2
     const int Kw = (p.n_split > 0 && !high) ? p.K1 : K;
-    const int kt_n = Kw / 16, tpw = (kt_n + NW - 1) / NW;
-    const int kt0 = wave * tpw;
+    kt_n = Kw / 16; tpw = (kt_n + NW - 1) / NW;
+    kt0 = wave * tpw;
 
     // ---- 1. the row this wave stages: row m0+wave (clamped to the last valid row) ----
-    const int zg = p.n_groups > 1 ? (int)blockIdx.z : 0;     // grouped launch: one expert per blockIdx.z
+    zg = p.n_groups > 1 ? (int)blockIdx.z : 0;      // grouped launch: one expert per blockIdx.z
     const int r = m0 + wave, rc = min(r, p.B - 1);
     const float* xr = p.x + (size_t)zg * p.x_group_off + (size_t)rc * p.ldx;
     const float* x2r = p.x2 ? p.x2 + (size_t)rc * p.ldx2 - K1 : xr;
-    float4 v[KCH];
 #pragma unroll
     for (int c = 0; c < KCH; ++c) {
         const int ic = chunk_col<FULL>(c, lane, K);
         v[c] = ld4((ic < K1 ? xr : x2r) + ic);
     }
-    // FoldedGlu: at least one 256-column chunk belongs to the u half (two at K = 1536, where the launcher asks for K - K1 >= 512: one
-    // float4 more per lane would spill at the 128-VGPR budget of a 16-wave workgroup)
-    constexpr int GCH = PRO == Pro::FoldedGlu ? (KCH == 6 ? 4 : KCH > 1 ? KCH - 1 : 1) : KCH;
-    float4 gv[pro_gated(PRO) ? GCH : 1];
     if (PRO == Pro::Glu) {
         const float* gr = p.glu_gate + (size_t)zg * p.x_group_off + (size_t)rc * p.ldx;
 #pragma unroll
@@ -315,24 +389,22 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
         for (int c = 0; c < GCH; ++c) gv[c] = ld4(gr + min(chunk_col(c, lane), K1 - 4));
     }
     // ---- 2. prologue vectors ----
-    float4 g0[LN1 ? KCH : 1], h0[LN1 ? KCH : 1], g1[PRO == Pro::LayerNorm2 ? KCH : 1], h1[PRO == Pro::LayerNorm2 ? KCH : 1];
     if constexpr (LN1) load_ln<KCH, FULL>(g0, h0, p.ln_w, p.ln_b, lane, K);
     if constexpr (PRO == Pro::LayerNorm2) load_ln<KCH, FULL>(g1, h1, p.ln2_w, p.ln2_b, lane, K);
     // folded FFN: the per-column vectors (same for all 16 rows) go through LDS, one float4 per thread (K/2 <= 1024)
-    float4 gs_val = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int gs_t = min(tid, K / 2 - 1), gs_vec = gs_t >= K / 4, gs_i = (gs_t - gs_vec * (K / 4)) * 4;
+    const int gs_t = min(tid, K / 2 - 1);
+    gs_vec = gs_t >= K / 4; gs_i = (gs_t - gs_vec * (K / 4)) * 4;
     if (FFN) {
         const float* a = gs_i < K1 ? p.fold_g + gs_i : p.ln_w + (gs_i - K1);
         const float* b = gs_i < K1 ? p.fold_c + gs_i : p.ln_b + (gs_i - K1);
         gs_val = ld4(gs_vec ? b : a);
     }
     // folded gated FFN: the gate's two vectors [g2 (K1) | c2 (K1)], one more float4 for the first K1/2 threads (clamped)
-    float4 gs2_val = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int gs2_t = min(tid, K1 / 2 - 1), gs2_vec = gs2_t >= K1 / 4, gs2_i = (gs2_t - gs2_vec * (K1 / 4)) * 4;
+    const int gs2_t = min(tid, K1 / 2 - 1);
+    gs2_vec = gs2_t >= K1 / 4; gs2_i = (gs2_t - gs2_vec * (K1 / 4)) * 4;
     if (PRO == Pro::FoldedGlu) gs2_val = ld4((gs2_vec ? p.fold_c2 : p.fold_g2) + gs2_i);
     // ---- 3. this wave's weight tiles (tile index clamped: surplus loads repeat the last tile) ----
-    float4 wt[KCH];
-    const int grp = p.sel ? *p.sel : zg;            // device-chosen weight group (mixture-of-experts, one token) or the launch's group
+    grp = p.sel ? *p.sel : zg;                      // device-chosen weight group (mixture-of-experts, one token) or the launch's group
     const float* wbase = high ? p.Wp2 + (size_t)(nt - nts) * kt_n * 256 : p.Wp + (size_t)grp * p.sel_w_stride + (size_t)nt * kt_n * 256;
     // un-packed weights (ldw > 0): lane (n = lane & 15, k-quad = lane >> 4) reads its float4 of row n directly: 16 rows x 64 B
     // per tile instead of one 1 KiB run, still one fully used 64-B segment per row
@@ -342,7 +414,16 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
         const int kt = min(kt0 + i, kt_n - 1);
         wt[i] = ld4(p.ldw ? wrow + (size_t)kt * 16 : wbase + ((size_t)kt * 64 + lane) * 4);
     }
+    }
+    int n_u = K - K1;                               // width of the u half (the folded prologues' statistics)
     __builtin_amdgcn_sched_barrier(0);              // the scheduler must not sink any of these loads below this point
+    if constexpr (LEAN) {
+        // ... and nothing that reads a row may rise above it (with every operand of the statistics in SGPRs early, instruction selection
+        // otherwise places them, and their wait, between the row loads and the weight loads)
+#pragma unroll
+        for (int c = 0; c < KCH; ++c) asm volatile("" : "+v"(v[c].x), "+v"(v[c].y), "+v"(v[c].z), "+v"(v[c].w));
+        asm volatile("" : "+s"(n_u));               // (the division by the u half's width as well)
+    }
     STAMP(1);
     const int el = tid & 63, er = (tid >> 6) & 3;
     const int row = m0 + 4 * (el >> 4) + er, n = nt * 16 + (el & 15);
@@ -357,7 +438,7 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
         // when they are read for the MFMAs -- under the shadow of the weight tiles still in flight, every element exactly once (a wave
         // owns its k range), and with ONE barrier instead of two (1.56 us of a 6.5 us launch were this prologue)
         float* gs = smem + MT * LD;                 // [2][K]: g|gamma , c|beta ; then [16][2]: mu, rstd per staged row
-        const RowStats st = row_stats<true>(v, u_half, (float)(K - K1), p.eps);
+        const RowStats st = row_stats<true>(v, u_half, (float)n_u, p.eps);
         gs[2 * K + 2 * wave + (lane & 1)] = (lane & 1) ? st.rstd : st.mean;      // (every lane stores one of the two words: no branch)
         st4(gs + gs_vec * K + gs_i, gs_val);        // unconditional (surplus threads repeat the last float4): a guarded
                                                     // store lets the compiler sink the load behind the weight loads
@@ -366,7 +447,7 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
         float* gs = smem + MT * LD;                 // [2][K]: g|gamma , c|beta , then [2][K1]: the gate's g2 , c2
         st4(gs + gs_vec * K + gs_i, gs_val);
         st4(gs + 2 * K + gs2_vec * K1 + gs2_i, gs2_val);
-        const RowStats st = row_stats<true>(v, u_half, (float)(K - K1), p.eps);
+        const RowStats st = row_stats<true>(v, u_half, (float)n_u, p.eps);
         const float mean = st.mean, rstd = st.rstd;
         __syncthreads();
         // one half of the gated unit, folded: (raw - mu*g)*rstd + c
@@ -581,19 +662,43 @@ int32_t allow_big_lds() {
     return 0;
 }
 
-template <int KCH, bool FULL, Pro PRO, bool PIPE>
+template <int KCH, bool FULL, Pro PRO, bool PIPE, bool LEAN = false>
 int32_t launch_one_loop(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
-    if (int32_t rc = allow_big_lds<decode_gemm_kernel<KCH, FULL, PRO, PIPE>>()) return rc;
-    hipLaunchKernelGGL((decode_gemm_kernel<KCH, FULL, PRO, PIPE>), dim3(cdiv(p.N, 16), cdiv(p.B, MT), p.n_groups > 1 ? p.n_groups : 1), dim3(NW * 64), lds, stream, p);
+    if (int32_t rc = allow_big_lds<decode_gemm_kernel<KCH, FULL, PRO, PIPE, LEAN>>()) return rc;
+    hipLaunchKernelGGL((decode_gemm_kernel<KCH, FULL, PRO, PIPE, LEAN>), dim3(cdiv(p.N, 16), cdiv(p.B, MT), p.n_groups > 1 ? p.n_groups : 1), dim3(NW * 64), lds, stream, p);
     AMT_LAUNCH_CHECK();
     return 0;
 }
 
+// what the lean front reads, from the parameters of a launch that amt_decode_gemm_lean_ok() accepts
+DecodeGemmFront lean_front(const DecodeGemmParams& p) {
+    DecodeGemmFront f{};
+    f.x = p.x; f.x2b = p.x2 - p.K1; f.Wp = p.Wp; f.Wp2 = p.Wp2;
+    f.fold_g = p.fold_g; f.fold_c = p.fold_c; f.ln_wb = p.ln_w ? p.ln_w - p.K1 : nullptr; f.ln_bb = p.ln_b ? p.ln_b - p.K1 : nullptr;
+    f.x_row_bytes = (unsigned)p.ldx * 4u; f.x2_row_bytes = (unsigned)p.ldx2 * 4u;
+    f.B = p.B; f.K = p.K; f.K1 = p.K1; f.LD = p.K + XPAD;
+    f.nts = p.n_split > 0 ? p.n_split >> 4 : INT_MAX;
+    f.ktn_lo = (p.n_split > 0 ? p.K1 : p.K) / 16; f.tpw_lo = cdiv(f.ktn_lo, NW);
+    f.ktn_hi = p.K / 16; f.tpw_hi = cdiv(f.ktn_hi, NW);
+    f.red_off = MT * f.LD + (p.pro == 1 ? 2 * p.K + 2 * MT : 0);
+    return f;
+}
+
 // The pipelined tile loop serves the plain and the folded-FFN prologue (every skinny GEMM of the folded decode chain); the other
-// prologues keep the serial loop (LayerNorm2 / FoldedGlu sit at 114 - 126 VGPRs of the 128 a 16-wave workgroup may use)
+// prologues keep the serial loop (LayerNorm2 / FoldedGlu sit at 114 - 126 VGPRs of the 128 a 16-wave workgroup may use).
+// With it goes the lean front wherever the launcher's rule admits it.
 template <int KCH, bool FULL, Pro PRO>
 int32_t launch_one(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
-    if constexpr (PRO == Pro::Plain || PRO == Pro::FoldedFfn) { if (!p.serial_loop) return launch_one_loop<KCH, FULL, PRO, true>(p, lds, stream); }
+    if constexpr (PRO == Pro::Plain || PRO == Pro::FoldedFfn) {
+        if constexpr (FULL && KCH >= 2) {
+            if (amt_decode_gemm_lean_ok(p)) {
+                DecodeGemmParams q = p;
+                q.front = lean_front(p);
+                return launch_one_loop<KCH, FULL, PRO, true, true>(q, lds, stream);
+            }
+        }
+        if (!p.serial_loop) return launch_one_loop<KCH, FULL, PRO, true>(p, lds, stream);
+    }
     return launch_one_loop<KCH, FULL, PRO, false>(p, lds, stream);
 }
 
@@ -862,6 +967,24 @@ int32_t launch_variant(const DecodeGemmParams& p, size_t lds, hipStream_t stream
 }
 
 }  // namespace
+
+// The lean front's rule, in one place: the folded chain's form of launch.  (launch_variant maps pro and the prologue pointers onto
+// Plain / FoldedFfn exactly when glu_gate, ln2_w and -- with pro 0 -- ln_w are absent; two sources of whole 256-column chunks make
+// K one of 512 / 768 / 1024 / 1536, i.e. a FULL instantiation.)
+bool amt_decode_gemm_lean_ok(const DecodeGemmParams& p) {
+    if (p.generic_front || p.serial_loop) return false;
+    if (!p.x || !p.x2 || !p.Wp || p.B <= 0 || p.ldw != 0 || p.K1 <= 0 || p.K1 >= p.K || p.K1 % 256 != 0 || p.K % 256 != 0 || p.K > 1536 || p.K == 1280) return false;
+    if (p.sel || p.n_groups > 1 || p.pos || p.mode != 0 || p.rope || p.glu_pair || p.glu_gate || p.ln2_w || p.xn) return false;
+    if (p.pro == 1 ? !(p.fold_g && p.fold_c && p.ln_w && p.ln_b) : (p.pro != 0 || p.ln_w)) return false;
+    if (p.n_split > 0 && p.n_split < p.N && !p.Wp2) return false;
+    // 32-bit byte offsets: the last row's end in x and x2, the last output, and the last tile of either packed weight
+    const unsigned long long lim = 1ull << 32, rows = (unsigned long long)(p.B - 1);
+    const unsigned long long n_lo = p.n_split > 0 ? p.n_split : p.N, n_hi = p.N - n_lo;
+    if ((rows * p.ldx + p.K1) * 4 >= lim || (rows * p.ldx2 + (p.K - p.K1)) * 4 >= lim) return false;
+    if ((rows * p.ldy + n_lo) * 4 >= lim || (rows * p.ldy2 + n_hi) * 4 >= lim) return false;
+    if ((n_lo + 15) / 16 * (p.n_split > 0 ? p.K1 : p.K) * 64 >= lim || (n_hi + 15) / 16 * p.K * 64 >= lim) return false;
+    return true;
+}
 
 int32_t amt_launch_pack_weight(const float* W, float* P, int N, int K, hipStream_t stream, int ldw) {
     AMT_CHECK_ARG(K % 16 == 0 && (ldw == 0 || (ldw >= K && ldw % 4 == 0)), "pack_weight: K=%d must be a multiple of 16 (ldw=%d)", K, ldw);

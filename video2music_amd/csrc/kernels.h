@@ -137,7 +137,24 @@ bool amt_attn_decode_tables_fit(int hd, int cap, int ra_rows);
 // ---------------- decode-step skinny GEMM (decode_gemm.hip) ----------------
 // packed weight: tiles of 16(n) x 16(k): P[((nt*(K/16)+kt)*64 + lane)*4 + e] = W[nt*16+(lane&15)][kt*16+4*(lane>>4)+e]
 int32_t amt_launch_pack_weight(const float* W, float* P, int N, int K, hipStream_t stream, int ldw = 0);   // ldw: W's row stride (0 = K)
+// Everything the lean front of decode_gemm_kernel needs between kernel entry and its last load request, worked out by the launcher
+// (it depends on the launch alone) and kept at the front of the parameters: one contiguous run of kernel arguments, one round of
+// scalar loads.  Filled by amt_launch_decode_gemm when amt_decode_gemm_lean_ok() holds; callers leave it zero.
+struct DecodeGemmFront {
+    const float* x;             // rows of the first K1 columns
+    const float* x2b;           // x2 - K1: column i >= K1 of row r is x2b[r * ldx2 + i]
+    const float* Wp; const float* Wp2;
+    const float* fold_g; const float* fold_c;       // FoldedFfn: the vectors of the columns below K1 ...
+    const float* ln_wb; const float* ln_bb;         // ... and ln_w - K1, ln_b - K1 for the columns from K1 on
+    unsigned x_row_bytes, x2_row_bytes;             // row strides in bytes
+    int B, K, K1, LD;                               // LD = K + 8: row stride of the staged rows in LDS
+    int nts;                                        // first high column tile (n_split / 16; INT_MAX without a column split)
+    int ktn_lo, tpw_lo, ktn_hi, tpw_hi;             // k-tiles of a low / high column tile, and of them per wave
+    int red_off;                                    // the partial tiles' offset in LDS, in floats
+};
+
 struct DecodeGemmParams {
+    DecodeGemmFront front;
     const float* x; int ldx;    // [B][K] input rows (pre-LN sum when ln_w != null)
     const float* Wp;            // packed weight
     const float* bias;          // [N]
@@ -199,8 +216,14 @@ struct DecodeGemmParams {
     // 1: the serial tile loop of rounds 2-4 (LDS read, fix, wait, four MFMAs per tile under a lane predicate) instead of the pipelined one
     // (wave-uniform control, next tile's reads and fix under this tile's MFMAs).  Same arithmetic in the same order: bit-identical results
     int serial_loop;
+    // 1: the generic front (per-lane 64-bit addresses, options decided at run time) where the launch could take the lean one
+    // (amt_decode_gemm_lean_ok); serial_loop implies it.  What is loaded and summed is the same: bit-identical results
+    int generic_front;
 };
 int32_t amt_launch_decode_gemm(const DecodeGemmParams& p, hipStream_t stream);
+// The launcher's rule for the lean front (decode_gemm.hip), evaluated on the host on the parameters alone: does this launch take
+// the LEAN instantiation of decode_gemm_kernel?
+bool amt_decode_gemm_lean_ok(const DecodeGemmParams& p);
 // allocates the per-device zero words (hipMalloc): call once outside any stream capture
 int32_t amt_decode_gemm_init();
 

@@ -213,24 +213,40 @@ extern "C" int32_t amt_attn_decode_fold_fwd(const float* raw, int32_t ldq, float
     return amt_launch_attn_decode(a, (hipStream_t)stream);
 }
 
-extern "C" int32_t amt_decode_gemm_ex_fwd(const amt_decode_gemm_args* a, void* stream) {
-    AMT_CHECK_ARG(a, "amt_decode_gemm_ex_fwd: null argument block");
-    AMT_CHECK_ARG(a->x && a->w_low && a->y_low && a->scratch_low && a->n_low > 0 && a->n_low % 16 == 0, "amt_decode_gemm_ex_fwd: bad low part");
-    AMT_CHECK_ARG(a->n_high == 0 || (a->w_high && a->y_high && a->scratch_high && a->x2), "amt_decode_gemm_ex_fwd: incomplete high part");
-    hipStream_t s = (hipStream_t)stream;
-    const int Klow = a->x2 ? a->K1 : a->K;
-    int32_t rc;
-    if ((rc = amt_launch_pack_weight(a->w_low, a->scratch_low, a->n_low, Klow, s))) return rc;
-    if (a->n_high > 0 && (rc = amt_launch_pack_weight(a->w_high, a->scratch_high, a->n_high, a->K, s))) return rc;
+// the launch amt_decode_gemm_ex_fwd makes of an argument block (the weights as packed into the scratch buffers)
+static int32_t decode_gemm_ex_params(const amt_decode_gemm_args* a, const char* who, DecodeGemmParams* out) {
+    constexpr int32_t LOOP_BITS = AMT_GEMM_PRO_SERIAL_LOOP | AMT_GEMM_PRO_GENERIC_FRONT;
+    AMT_CHECK_ARG(a, "%s: null argument block", who);
+    AMT_CHECK_ARG(a->x && a->w_low && a->y_low && a->scratch_low && a->n_low > 0 && a->n_low % 16 == 0, "%s: bad low part", who);
+    AMT_CHECK_ARG(a->n_high == 0 || (a->w_high && a->y_high && a->scratch_high && a->x2), "%s: incomplete high part", who);
+    AMT_CHECK_ARG((a->pro & ~LOOP_BITS) == 0 || (a->pro & ~LOOP_BITS) == 1, "%s: pro takes 0 or 1 (| AMT_GEMM_PRO_SERIAL_LOOP | AMT_GEMM_PRO_GENERIC_FRONT)", who);
     DecodeGemmParams g{};
     g.B = a->B; g.eps = a->eps; g.scale = 1.f; g.x = a->x; g.ldx = a->ldx; g.x2 = a->x2; g.ldx2 = a->ldx2; g.K1 = a->K1; g.K = a->K;
     g.Wp = a->scratch_low; g.bias = a->bias_low; g.resid = a->resid; g.ldr = a->n_low; g.relu = a->relu; g.y = a->y_low; g.ldy = a->n_low;
-    AMT_CHECK_ARG((a->pro & ~AMT_GEMM_PRO_SERIAL_LOOP) == 0 || (a->pro & ~AMT_GEMM_PRO_SERIAL_LOOP) == 1, "amt_decode_gemm_ex_fwd: pro takes 0 or 1 (| AMT_GEMM_PRO_SERIAL_LOOP)");
     g.serial_loop = (a->pro & AMT_GEMM_PRO_SERIAL_LOOP) ? 1 : 0;
-    g.pro = a->pro & ~AMT_GEMM_PRO_SERIAL_LOOP; g.fold_g = a->fold_g; g.fold_c = a->fold_c; g.ln_w = a->ln_w; g.ln_b = a->ln_b;
+    g.generic_front = (a->pro & AMT_GEMM_PRO_GENERIC_FRONT) ? 1 : 0;
+    g.pro = a->pro & ~LOOP_BITS; g.fold_g = a->fold_g; g.fold_c = a->fold_c; g.ln_w = a->ln_w; g.ln_b = a->ln_b;
     g.N = a->n_low + a->n_high;
     if (a->x2) { g.n_split = a->n_low; g.Wp2 = a->scratch_high; g.bias2 = a->bias_high; g.y2 = a->y_high; g.ldy2 = a->n_high; }
+    *out = g;
+    return 0;
+}
+
+extern "C" int32_t amt_decode_gemm_ex_fwd(const amt_decode_gemm_args* a, void* stream) {
+    DecodeGemmParams g{};
+    int32_t rc;
+    if ((rc = decode_gemm_ex_params(a, "amt_decode_gemm_ex_fwd", &g))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int Klow = a->x2 ? a->K1 : a->K;
+    if ((rc = amt_launch_pack_weight(a->w_low, a->scratch_low, a->n_low, Klow, s))) return rc;
+    if (a->n_high > 0 && (rc = amt_launch_pack_weight(a->w_high, a->scratch_high, a->n_high, a->K, s))) return rc;
     return amt_launch_decode_gemm(g, s);
+}
+
+extern "C" int32_t amt_decode_gemm_ex_lean(const amt_decode_gemm_args* a) {
+    DecodeGemmParams g{};
+    if (decode_gemm_ex_params(a, "amt_decode_gemm_ex_lean", &g)) return -1;
+    return amt_decode_gemm_lean_ok(g) ? 1 : 0;
 }
 
 extern "C" int32_t amt_decode_linear_fwd(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b,
