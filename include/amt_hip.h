@@ -797,6 +797,30 @@ int64_t amt_chord_loss_ws_floats(int32_t B, int32_t L);
 int32_t amt_chord_loss_fwd_bwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, int32_t B, int32_t L,
                                float lambda, float smoothing, float* loss, float* clip_out, float* dlogits, float* ws, void* stream);
 
+/* The same loss with the reference's -auxiliary_loss (train.py:221-229, model/loss.py:85-141) and free weights:
+ *   chord = (CE + A_3 + A_5) / count,  total = w_chord chord + w_emotion emotion
+ * CE and emotion as above.  For an auxiliary row z of 159 values with target t, p = softmax(z) and a_k = relu(mean(top-k of p) - p_t);
+ * A_k = w_k (sum of a_k over the valid rows) / n_valid with (k, w_k) = (3, 3.0), (5, 5.0); count = how many of the three fp32 terms
+ * exceed 1e-10 (a constant under differentiation; 0 gives the reference's division by zero).
+ * layout: AMT_CHORD_AUX_ROWS -- auxiliary row (b, l) is logits[b, l, :159], as the reference's eval_model passes them;
+ *         AMT_CHORD_AUX_VIEW -- as its train_epoch does, the (B, 159, L) permute RESHAPED to (B, L, 159): element j of row (b, r) is
+ *         logits[b, f % L, f / L] with f = 159 r + j.  Either way the row pairs with tgt[b, r].
+ * loss[7] = {total, chord, emotion, CE, A_3, A_5, count}.  A weight of exactly 0 drops its term from total and from dlogits.
+ * clip_out (B, 6) = the four columns above, then the clip's sums of a_3 and a_5 over its valid rows (unweighted).
+ * dlogits (B L, 159) contiguous, optional (null = forward only; loss and clip_out are the same bits either way):
+ *   (w_chord / count) (dCE + dA_3 + dA_5) + w_emotion dBCE;  an auxiliary row with a_k > 0 gives
+ *   dz_j = (w_k / n_valid) p_j (g_j - sum_i g_i p_i),  g_j = [j in top-k] / k - [j = t].
+ * ws: amt_chord_loss_aux_ws_floats(B, L) floats, 16-byte aligned, this call's alone until it has finished (the ticket counter, five
+ * sums per workgroup and two (B L, 159) gradient pieces).  Two launches on `stream`: the loss kernel (the grid and summation order of
+ * amt_chord_loss_fwd_bwd) and, with dlogits, an elementwise one that reads count from loss[6]; nothing waits on the host.  No
+ * floating-point atomic: the same inputs give the same bits.  159 B L <= 2^24. */
+#define AMT_CHORD_AUX_ROWS 0
+#define AMT_CHORD_AUX_VIEW 1
+int64_t amt_chord_loss_aux_ws_floats(int32_t B, int32_t L);
+int32_t amt_chord_loss_aux_fwd_bwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, int32_t B, int32_t L,
+                                   float w_chord, float w_emotion, float smoothing, int32_t layout, float* loss, float* clip_out,
+                                   float* dlogits, float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

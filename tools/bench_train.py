@@ -4,6 +4,7 @@ fused loss, backward, optimiser (not a test; run on the GPU box).
 
     python tools/bench_train.py --which ours            # the project's step alone
     python tools/bench_train.py --which both            # then, alternating with it, the comparison
+    python tools/bench_train.py --auxiliary_loss        # the step with the -auxiliary_loss chord loss, alternating with the plain one
     python tools/bench_train.py --music_gen_version 1.2.3 2.2      # the base model's step, then the named V1 / V2 models' in the same
                                                                    # session (chord_embed, the same shape and optimiser; --rms_norm)
 
@@ -52,6 +53,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--music_gen_version", nargs="*", default=[], help="also time these V1 / V2 versions (train_families.TRAINABLE)")
     ap.add_argument("--rms_norm", action="store_true", help="build the V1 versions with rms_norm=True")
+    ap.add_argument("--auxiliary_loss", action="store_true", help="also time the base model's step with the -auxiliary_loss chord loss "
+                    "(train_losses; profiles/train_losses_step.json)")
     ap.add_argument("--skip_base", action="store_true", help="with --music_gen_version: do not time the base model (kernel traces)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -81,6 +84,12 @@ def main():
         chord_train_loss(y, d["tgt"], d["emo_class"], C.LOSS_LAMBDA, 0.1).backward()
         opt.step()
 
+    def step_ours_aux():
+        opt.zero_grad()
+        y = ours(d["x"], d["x_root"], d["x_attr"], d["semantic"], d["key"], d["scene_offset"], d["motion"], d["emotion"])
+        chord_train_loss(y, d["tgt"], d["emo_class"], C.LOSS_LAMBDA, 0.1, auxiliary=True, layout="view").backward()
+        opt.step()
+
     def family_step(version):
         """One training step of the V1 / V2 model `version` (chord_embed, synthetic weights) on the same batch."""
         from video2music_amd.model import video_music_transformer as M
@@ -106,6 +115,8 @@ def main():
     if families:
         res["family_ms"] = {v: [] for v in families}
         res["rms_norm"] = bool(a.rms_norm)
+    if a.auxiliary_loss:
+        res["ours_aux_ms"] = []
     if a.which == "both":
         P = {k: torch.from_numpy(v).to(dev).requires_grad_(True) for k, v in sd.items()}
         used = [p for k, p in P.items() if k not in T.UNUSED]
@@ -137,12 +148,16 @@ def main():
     for _ in range(a.rounds):
         if not (families and a.skip_base):
             res["ours_ms"].append(timed(step_ours, a.steps, a.warmup))
+        if a.auxiliary_loss:
+            res["ours_aux_ms"].append(timed(step_ours_aux, a.steps, a.warmup))
         for v, step in families.items():
             res["family_ms"][v].append(timed(step, a.steps, a.warmup))
         if a.which == "both":
             res["torch_ms"].append(timed(step_torch, a.steps, a.warmup))
     if res["ours_ms"]:
         res["ours_ms_best"] = min(res["ours_ms"])
+    if a.auxiliary_loss:
+        res["ours_aux_ms_best"] = min(res["ours_aux_ms"])
     if families:
         res["family_ms_best"] = {v: min(t) for v, t in res["family_ms"].items()}
     if res["torch_ms"]:

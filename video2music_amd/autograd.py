@@ -21,6 +21,7 @@ and the pieces of the chord model's training that do not depend on the model (lo
                                                                           amt_attn_train_fwd; backward: amt_attn_bwd
     LayerNormFn       LayerNorm(x (+ resid)); gradients of both addends   amt_layernorm_fwd; backward: amt_layernorm_bwd
     ChordLossFn       smoothed cross-entropy + BCE-with-logits            amt_chord_loss_fwd_bwd
+    ChordAuxLossFn    the same + the top-3 / top-5 auxiliary hinge terms   amt_chord_loss_aux_fwd_bwd
     EmbeddingFn       rows of a table; the table's gradient is a one-hot product on the GEMM (deterministic), not index_add_
 
 and what the V1 / V2 chord models add to those (model/vmt_v2.py, `_forward_train`):
@@ -551,6 +552,28 @@ class ChordLossFn(torch.autograd.Function):
         if ctx.width > d.shape[2]:                              # columns past the 159 classes take no part
             d = torch.nn.functional.pad(d, (0, ctx.width - d.shape[2]))
         return d, None, None, None, None
+
+
+class ChordAuxLossFn(torch.autograd.Function):
+    """apply(logits (B, L, >=159), tgt (B, L) int64, emo_class (B, L) int32, w_chord, w_emotion, smoothing, layout) -> the scalar
+    training loss with the top-k auxiliary terms (`ops.chord_loss_aux`).  The kernel's second launch has already divided the chord
+    gradient by the batch's count of live terms; the backward hands the result on, scaled by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, tgt, emo_class, w_chord, w_emotion, smoothing, layout):
+        loss, clip, dlogits = ops.chord_loss_aux(logits, tgt, emo_class, w_chord, w_emotion, smoothing, layout,
+                                                 backward=ctx.needs_input_grad[0])
+        ctx.save_for_backward(dlogits)
+        ctx.width = logits.shape[2]
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dlogits, = ctx.saved_tensors
+        d = dlogits * g
+        if ctx.width > d.shape[2]:                              # columns past the 159 classes take no part
+            d = torch.nn.functional.pad(d, (0, ctx.width - d.shape[2]))
+        return d, None, None, None, None, None, None
 
 
 class MoEFn(torch.autograd.Function):

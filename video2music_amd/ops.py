@@ -323,6 +323,34 @@ def chord_loss(logits, tgt, emo_class, lam, smoothing, backward=True):
     return loss, clip, dlogits
 
 
+CHORD_AUX_LOSS_FIELDS = ("total", "chord", "emotion", "ce", "aux3", "aux5", "count")
+CHORD_AUX_CLIP_FIELDS = CHORD_LOSS_CLIP_FIELDS + ("a3_sum", "a5_sum")
+CHORD_AUX_LAYOUTS = {"rows": 0, "view": 1}              # AMT_CHORD_AUX_ROWS / AMT_CHORD_AUX_VIEW
+CHORD_AUX_TERMS = ((3, 3.0), (5, 5.0))                  # (k, weight) of the reference's two TopKAuxiliaryLoss terms (train.py:227-228)
+
+
+def chord_loss_aux(logits, tgt, emo_class, w_chord, w_emotion, smoothing, layout="view", backward=True):
+    """amt_chord_loss_aux_fwd_bwd: `chord_loss` with the reference's two top-k auxiliary terms in the chord part and free weights.
+    layout "view": the auxiliary rows as the reference's train_epoch forms them (the (B, 159, L) permute reshaped to (B, L, 159));
+    "rows": the natural rows, as its eval_model does.  Returns loss (7,) in the order of CHORD_AUX_LOSS_FIELDS, clip (B, 6) in the order
+    of CHORD_AUX_CLIP_FIELDS and dlogits (B, L, 159) -- None with backward=False, which leaves loss and clip the same bits."""
+    if layout not in CHORD_AUX_LAYOUTS:
+        raise ValueError(f"layout {layout!r}: one of {sorted(CHORD_AUX_LAYOUTS)}")
+    B, L = tgt.shape
+    assert logits.dtype == torch.float32 and logits.shape[:2] == (B, L) and logits.stride(2) == 1
+    assert tgt.dtype == torch.int64 and emo_class.dtype == torch.int32 and emo_class.shape == (B, L)
+    ld = logits.stride(1) if L > 1 else max(logits.stride(0), logits.shape[2])
+    assert B == 1 or logits.stride(0) == L * ld, "rows of logits must be evenly strided"
+    dev = logits.device
+    loss = torch.empty(len(CHORD_AUX_LOSS_FIELDS), device=dev, dtype=torch.float32)
+    clip = torch.empty(B, len(CHORD_AUX_CLIP_FIELDS), device=dev, dtype=torch.float32)
+    dlogits = torch.empty(B, L, 159, device=dev, dtype=torch.float32) if backward else None
+    ws = torch.empty(_lib.call("amt_chord_loss_aux_ws_floats", B, L), device=dev, dtype=torch.float32)
+    _lib.call("amt_chord_loss_aux_fwd_bwd", C.c_void_p(logits.data_ptr()), ld, p(tgt), p(emo_class), B, L, float(w_chord), float(w_emotion),
+              float(smoothing), CHORD_AUX_LAYOUTS[layout], p(loss), p(clip), p(dlogits), p(ws), _st())
+    return loss, clip, dlogits
+
+
 def selective_scan(xc, draw, dt_bias, A_log, dbc, R, D, xz, B, L, version=1, reverse=False):
     """Selective scan + gate.  xc, draw (B*L, ED); dbc (B*L, R+2N) = x_proj output (B at column R, C at R+N);
     xz (B*L, 2*ED) = in_proj output (gate branch z at column ED)."""

@@ -19,12 +19,14 @@ Refused, with the reason: ``-music_gen_version`` 1.x / 2.x / 3.x, ``-is_video Fa
 ``main(argv, families=...)`` / ``refuse(args, families=...)`` admit the listed V1 / V2 versions as well (``train_families`` is that
 entry point): the class the reference's ``train.py:136-168`` builds, trained through ``VideoMusicTransformer_V2._forward_train`` with
 the same loop, files and schedule.  With the default empty ``families`` every answer is the one above.  ``train_v3`` adds the V3
-family and ``-balancing`` (``opt_in=True``: the model's ``enable_training()`` is called after it is built).
+family and ``-balancing`` (``opt_in=True``: the model's ``enable_training()`` is called after it is built).  ``train_losses`` adds
+``-auxiliary_loss`` and ``-drop_loss`` to that (``losses=True``); here and in the two entry points between, both stay refused.
 
     python -m video2music_amd.train -dataset_dir ./dataset/ -music_gen_version None -chord_embed "" -motion_type 1
 """
 import csv
 import os
+import random
 import sys
 
 import numpy as np
@@ -102,10 +104,11 @@ def refuse_family(args, families, balancing=False):
     return None
 
 
-def refuse(args, families=(), balancing=False):
+def refuse(args, families=(), balancing=False, losses=False):
     """The reason this build does not run `args`, or None.  families: the -music_gen_version strings the caller trains beside the base
     model (`train_families.TRAINABLE`); empty, the answers are the base entry point's.  balancing (default off; `train_v3` sets it):
-    -balancing is admitted for a family version."""
+    -balancing is admitted for a family version.  losses (default off; `train_losses` sets it): -auxiliary_loss and -drop_loss are
+    admitted."""
     family = bool(families) and args.music_gen_version is not None
     if args.force_cpu:
         return "--force_cpu: video2music_amd has no CPU path (the CPU oracle lives in oracle/ for tests only)"
@@ -124,9 +127,9 @@ def refuse(args, families=(), balancing=False):
         return "-scene_embed: training with the scene-offset embedding is not built"
     if IS_SEPERATED:
         return "IS_SEPERATED: training the separate root / attr heads is not built"
-    if args.auxiliary_loss:
+    if args.auxiliary_loss and not losses:
         return "-auxiliary_loss: the top-k auxiliary losses are not built"
-    if args.drop_loss:
+    if args.drop_loss and not losses:
         return "-drop_loss is not built: every step uses the weighted sum of both losses"
     if args.augmentation:
         return "-augmentation is not built: the clips are read as they are"
@@ -162,9 +165,30 @@ def forward(model, f, Tc, clips=False):
               f["semantic"], f["key"], f["scene_offset"], f["motion"], f["emotion"])
 
 
-def evaluate(model, data, batch_size, Tc, smoothing):
+def clip_chord_losses(clip, auxiliary=False):
+    """The chord loss of every clip as eval_model forms it (a loader of batch size 1 and the training loss function) from the loss
+    kernel's per-clip sums `clip` (n, >= 4) (ops.CHORD_LOSS_CLIP_FIELDS; with auxiliary (n, 6), ops.CHORD_AUX_CLIP_FIELDS, of the
+    "rows" layout): the smoothed cross-entropy over the clip's valid targets, or the reference's `CombinedLoss(type='avg')`,
+    (CE + A_3 + A_5) / count with the clip's own count of fp32 terms above 1e-10.  A clip without a valid target gives NaN."""
+    clip = np.asarray(clip, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ce = clip[:, 1] / clip[:, 0]
+        if not auxiliary:
+            return ce
+        terms = [ce] + [clip[:, 4 + i] / clip[:, 0] * w for i, (_, w) in enumerate(ops.CHORD_AUX_TERMS)]
+        count = sum((t.astype(np.float32) > np.float32(1e-10)).astype(np.float64) for t in terms)
+        return ((terms[0] + terms[1]) + terms[2]) / count
+
+
+def drop_loss_weights(p, lam=LOSS_LAMBDA):
+    """-drop_loss (utilities/run_model_vevo.py:110-117): the (chord, emotion) weights of a step from its draw p in [0, 1)."""
+    return (lam, 1 - lam) if p < 0.6 else (1.0, 0.0) if p < 0.8 else (0.0, 1.0)
+
+
+def evaluate(model, data, batch_size, Tc, smoothing, auxiliary=False):
     """eval_model's figures (utilities/run_model_vevo.py:198-452) with the training loss function, per clip, then averaged over the
-    clips: {avg_total_loss, avg_loss_chord, avg_loss_emotion, avg_h1, avg_h3, avg_h5}."""
+    clips: {avg_total_loss, avg_loss_chord, avg_loss_emotion, avg_h1, avg_h3, avg_h5}.  auxiliary: that function is the
+    -auxiliary_loss one, which eval_model calls on the natural rows (:427-430)."""
     model.eval()
     rows, ce = [], []
     with torch.set_grad_enabled(False):
@@ -172,14 +196,16 @@ def evaluate(model, data, batch_size, Tc, smoothing):
             f = {k: v[b0:b0 + batch_size] for k, v in data.items()}
             y = forward(model, f, Tc, clips=True)
             m = metrics.chord_metrics(y, f["tgt"], f["emo_class"], f["emo_prob"])
-            _, clip, _ = ops.chord_loss(y, f["tgt"].contiguous(), f["emo_class"].to(torch.int32).contiguous(), LOSS_LAMBDA, smoothing, backward=False)
+            tgt, emo = f["tgt"].contiguous(), f["emo_class"].to(torch.int32).contiguous()
+            if auxiliary:
+                _, clip, _ = ops.chord_loss_aux(y, tgt, emo, LOSS_LAMBDA, 1 - LOSS_LAMBDA, smoothing, layout="rows", backward=False)
+            else:
+                _, clip, _ = ops.chord_loss(y, tgt, emo, LOSS_LAMBDA, smoothing, backward=False)
             rows.append(torch.stack([m[k] for k in metrics.FIELDS], dim=1).cpu())
             ce.append(clip.cpu())
     per_clip = {k: torch.cat(rows)[:, i].numpy() for i, k in enumerate(metrics.FIELDS)}
     r = metrics.clip_ratios(per_clip)
-    clip = torch.cat(ce).numpy().astype(np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        chord = clip[:, 1] / clip[:, 0]                     # the smoothed cross-entropy over the clip's valid targets
+    chord = clip_chord_losses(torch.cat(ce).numpy(), auxiliary)
     total = LOSS_LAMBDA * chord + (1 - LOSS_LAMBDA) * r["loss_emotion"]
 
     def mean(a):
@@ -188,15 +214,22 @@ def evaluate(model, data, batch_size, Tc, smoothing):
             "avg_h1": mean(r["h1"]), "avg_h3": mean(r["h3"]), "avg_h5": mean(r["h5"])}
 
 
-def train_epoch(cur_epoch, model, data, order, batch_size, Tc, smoothing, opt, lr_scheduler=None, print_modulus=1):
-    """utilities/run_model_vevo.py:20-196 over the clips `order` of `data`."""
+def train_epoch(cur_epoch, model, data, order, batch_size, Tc, smoothing, opt, lr_scheduler=None, print_modulus=1, auxiliary=False,
+                drop_rng=None, weights_log=None):
+    """utilities/run_model_vevo.py:20-196 over the clips `order` of `data`.  auxiliary: the chord part is the -auxiliary_loss one, on
+    the rows train_epoch's own call gives it (layout "view").  drop_rng: -drop_loss, a `random.Random` that gives one draw per step;
+    the weights of every step are appended to `weights_log` when that is a list."""
     model.train()
     n_batches = (len(order) + batch_size - 1) // batch_size
     for batch_num in range(n_batches):
         idx = order[batch_num * batch_size:(batch_num + 1) * batch_size]
         f = {k: v[idx] for k, v in data.items()}
         opt.zero_grad()
-        loss = chord_train_loss(forward(model, f, Tc), f["tgt"], f["emo_class"], LOSS_LAMBDA, smoothing)
+        weights = None if drop_rng is None else drop_loss_weights(drop_rng.random())
+        if weights_log is not None:
+            weights_log.append(weights)
+        loss = chord_train_loss(forward(model, f, Tc), f["tgt"], f["emo_class"], LOSS_LAMBDA, smoothing, auxiliary=auxiliary, layout="view",
+                                weights=weights)
         loss.backward()
         opt.step()
         if lr_scheduler is not None:
@@ -238,10 +271,11 @@ def build_model(args, total_vf_dim):
     return VideoMusicTransformer_V2(balancing=bool(args.balancing), **fam)
 
 
-def main(argv=None, families=(), opt_in=False):
-    """opt_in (`train_v3`): -balancing is admitted and the model's `enable_training()` is called after building it."""
+def main(argv=None, families=(), opt_in=False, losses=False):
+    """opt_in (`train_v3`): -balancing is admitted and the model's `enable_training()` is called after building it.  losses
+    (`train_losses`): -auxiliary_loss and -drop_loss are admitted; with -drop_loss the result also holds every step's weights."""
     args = parse_args(argv)
-    why = refuse(args, families, balancing=opt_in)
+    why = refuse(args, families, balancing=opt_in, losses=losses)
     if why:
         raise SystemExit(why)
     device = get_device()
@@ -258,6 +292,10 @@ def main(argv=None, families=(), opt_in=False):
     train, val = load(args, train_names, device), load(args, val_names, device)
     Tc = args.max_sequence_chord
     smoothing = float(args.ce_smoothing or 0.0)
+    # train.py:216-229: without -ce_smoothing the reference builds the plain cross-entropy whatever -auxiliary_loss says
+    auxiliary = bool(losses and args.auxiliary_loss and args.ce_smoothing is not None)
+    drop_rng = random.Random(args.seed) if losses and args.drop_loss else None        # a private stream: runs from one seed repeat
+    weights_log = [] if drop_rng is not None else None
     from .generate import total_vf_dim_of
     torch.manual_seed(args.seed)
     model = build_model(args, total_vf_dim_of(args, sem_dim=train["semantic"].shape[-1]))
@@ -299,13 +337,13 @@ def main(argv=None, families=(), opt_in=False):
             print(SEPERATOR)
             print("")
             train_epoch(epoch + 1, model, train, torch.from_numpy(rng.permutation(len(train_names))).to(device), bs, Tc, smoothing, opt,
-                        lr_scheduler, args.print_modulus)
+                        lr_scheduler, args.print_modulus, auxiliary, drop_rng, weights_log)
             print(SEPERATOR)
             print("Evaluating:")
         else:
             print(SEPERATOR)
             print("Baseline model evaluation (Epoch 0):")
-        tr, ev = evaluate(model, train, bs, Tc, smoothing), evaluate(model, val, bs, Tc, smoothing)
+        tr, ev = evaluate(model, train, bs, Tc, smoothing, auxiliary), evaluate(model, val, bs, Tc, smoothing, auxiliary)
         lr = opt.param_groups[0]["lr"]
         print("Epoch:", epoch + 1)
         for split, figs in (("train", tr), ("val", ev)):
@@ -324,7 +362,10 @@ def main(argv=None, families=(), opt_in=False):
             torch.save(model.state_dict(), epoch_weights_path(weights_folder, epoch + 1))
         with open(results_file, "a", newline="") as fh:
             csv.writer(fh).writerow([epoch + 1, lr] + [tr[k] for k in FIGURE_KEYS] + [ev[k] for k in FIGURE_KEYS])
-    return {"best_epoch": best_eval_loss_epoch, "best_val_total_loss": best_eval_loss}
+    res = {"best_epoch": best_eval_loss_epoch, "best_val_total_loss": best_eval_loss}
+    if weights_log is not None:
+        res["loss_weights"] = weights_log
+    return res
 
 
 if __name__ == "__main__":
