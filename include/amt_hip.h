@@ -476,6 +476,29 @@ int32_t amt_rnn_seq_bwd(const float* dy, int32_t lddy, const float* reserve, int
                         const float* w_hh, float* dxproj, int32_t ldxp, float* dhn, int32_t lddhn, int32_t B, int32_t L,
                         int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, void* stream);
 
+/* ---- the same recurrences for hidden sizes beyond the register kernels (csrc/rnn_wide.hip) ------------------------------------
+ * d a multiple of 32, 32 <= d <= 512 (the lower end overlaps amt_rnn_seq_* on purpose); gates, reverse, n_dirs, B, L and every
+ * pointer, layout and leading dimension -- xproj, w_hh, b_hh, y, reserve, dy, dxproj, dhn -- mean what they mean in the three
+ * functions above, and the results agree with theirs to rounding (another summation order: the products run on the matrix pipe).
+ * One step kernel per time step and call, all on `stream` (L launches; the stream's order is the only synchronisation between
+ * steps: no workgroup waits for another); clips beyond 32 are further tiles of the grid.  No allocation, no host
+ * synchronisation, no atomics: the same inputs give the same bits; amt_rnn_wide_seq_train_fwd's y equals amt_rnn_wide_seq_fwd's
+ * bit for bit.  Columns beyond the used widths are neither read nor written.  Rows that are read back as float4 need 16-byte
+ * alignment: y and w_hh (ldy a multiple of 4) in the forwards, dxproj and dhn (ldxp, lddhn multiples of 4) in the backward.
+ * ws: amt_rnn_wide_ws_floats(B, d, gates, n_dirs) = B * n_dirs * d floats (-1 for arguments the calls refuse), required by all
+ * three, never read before it is written (it need not be zero), free again when the call's launches have run: the eval forward
+ * keeps the LSTM's c there, the backward the carried term (LSTM dc f, GRU dh z); the training forward takes c_{t-1} from
+ * reserve and leaves ws alone.  Calls that may overlap must not share a ws. */
+int64_t amt_rnn_wide_ws_floats(int32_t B, int32_t d, int32_t gates, int32_t n_dirs);
+int32_t amt_rnn_wide_seq_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
+                             int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, float* ws, void* stream);
+int32_t amt_rnn_wide_seq_train_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
+                                   float* reserve, int32_t ldr, int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse,
+                                   int32_t n_dirs, float* ws, void* stream);
+int32_t amt_rnn_wide_seq_bwd(const float* dy, int32_t lddy, const float* reserve, int32_t ldr, const float* y, int32_t ldy,
+                             const float* w_hh, float* dxproj, int32_t ldxp, float* dhn, int32_t lddhn, int32_t B, int32_t L,
+                             int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, float* ws, void* stream);
+
 /* The same step for B independent clips in lockstep (all at one position): projections are one launch over B rows (weights
  * read once per step, not once per clip), the caches carry a leading clip dimension (self K/V: B, H, max_seq, hd; cross K/V:
  * B, H, S, hd), a mixture layer evaluates all experts on all rows and combines each row's routed pair in expert-index

@@ -120,6 +120,10 @@ SIGNATURES = {
     "amt_reg_metrics_fwd": [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "amt_rnn_seq_train_fwd": [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "amt_rnn_seq_bwd": [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "amt_rnn_wide_ws_floats": [_I, _I, _I, _I],
+    "amt_rnn_wide_seq_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "amt_rnn_wide_seq_train_fwd": [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "amt_rnn_wide_seq_bwd": [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "amt_reg_loss_fwd_bwd": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     "amt_attn_train_fwd": [_P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _I, _F, _P, _I, _P, _F, _P, _P],
     "amt_attn_bwd_ws_floats": [_I, _I, _I, _I, _I, _I],
@@ -161,7 +165,7 @@ _RESTYPES = {"amt_last_error": C.c_char_p, "amt_decode_step_bytes": C.c_int64, "
              "amt_chord_loss_ws_floats": C.c_int64, "amt_attn_bwd_ws_floats": C.c_int64, "amt_selective_scan_bwd_ws_floats": C.c_int64,
              "amt_dwconv1d_silu_bwd_ws_floats": C.c_int64, "amt_moe_train_scratch_floats": C.c_int64, "amt_moe_bwd_ws_floats": C.c_int64,
              "amt_glu_train_scratch_floats": C.c_int64, "amt_glu_bwd_ws_floats": C.c_int64,
-             "amt_selective_scan_wide_bwd_ws_floats": C.c_int64, "amt_chord_loss_aux_ws_floats": C.c_int64}
+             "amt_selective_scan_wide_bwd_ws_floats": C.c_int64, "amt_chord_loss_aux_ws_floats": C.c_int64, "amt_rnn_wide_ws_floats": C.c_int64}
 _NO_STATUS = set(_RESTYPES) | {"amt_abi_version", "amt_v2_last_step_launches", "amt_gemm_route", "amt_attn_route", "amt_decode_gemm_ex_lean", "amt_moe_wgrad_splits",
                                   "amt_rmsnorm_bwd_blocks", "amt_diff_subln_bwd_blocks", "amt_selective_scan_wide_ckpt_steps"}
 

@@ -6,7 +6,7 @@ module's own parameters.
     SigmoidHeadFn     the classifier head; hands out a second, empty-storage output that stands for its logits, so that the
                       fused loss can send its logit gradient straight to the head's GEMMs (losses.regression_train_loss)
     RnnLayerFn        one nn.LSTM / nn.GRU layer, all its directions    amt_linear_ex_fwd + amt_rnn_seq_train_fwd;
-                      backward: amt_rnn_seq_bwd + GEMMs
+                      backward: amt_rnn_seq_bwd + GEMMs (hidden sizes above 128: the amt_rnn_wide_seq_* pair)
     MambaBlockFn      one MambaBlock (+ the layer's residual)           amt_linear_ex_fwd, amt_dwconv1d_silu_fwd,
                       amt_selective_scan_train_fwd; backward: amt_selective_scan_bwd, amt_dwconv1d_silu_bwd + GEMMs
                       (more than 16 states per channel: amt_selective_scan_wide_train_fwd / amt_selective_scan_wide_bwd)
@@ -150,7 +150,8 @@ class RnnLayerFn(torch.autograd.Function):
         xproj = mm_nt(x, wi, bi)
         y = torch.empty(M, n_dirs * d, device=x.device, dtype=torch.float32)
         reserve = torch.empty(M, n_dirs * ops.rnn_reserve_cols(gates) * d, device=x.device, dtype=torch.float32)
-        ops.rnn_seq_train(xproj, wh, bh, y, 0, reserve, B, L, d, gates, reverse=reverse, n_dirs=n_dirs)
+        seq_train = ops.rnn_wide_seq_train if d > ops.RNN_NARROW_MAX else ops.rnn_seq_train      # same layouts; the width picks the kernel
+        seq_train(xproj, wh, bh, y, 0, reserve, B, L, d, gates, reverse=reverse, n_dirs=n_dirs)
         ctx.dims = (B, L, d, gates, bool(reverse), n_dirs)
         ctx.save_for_backward(x, y, reserve, wi, wh)
         return y
@@ -163,7 +164,8 @@ class RnnLayerFn(torch.autograd.Function):
         dy = dy.contiguous()
         dxp = torch.empty(M, n_dirs * R, device=x.device, dtype=torch.float32)
         dhn = torch.empty(M, n_dirs * d, device=x.device, dtype=torch.float32) if gates == 3 else None
-        ops.rnn_seq_bwd(dy, 0, reserve, y, 0, wh, dxp, dhn, B, L, d, gates, reverse=reverse, n_dirs=n_dirs)
+        seq_bwd = ops.rnn_wide_seq_bwd if d > ops.RNN_NARROW_MAX else ops.rnn_seq_bwd
+        seq_bwd(dy, 0, reserve, y, 0, wh, dxp, dhn, B, L, d, gates, reverse=reverse, n_dirs=n_dirs)
         dx = mm_nt(dxp, wi.t()) if ctx.needs_input_grad[0] else None
         dwi = mm_tn(dxp, x, ones=True)                                   # (n_dirs*R, in + 1): dW_ih | db_ih
         y3 = y.view(B, L, n_dirs * d)

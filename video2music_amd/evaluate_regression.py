@@ -35,7 +35,7 @@ def build_model(args, sem_dim):
     """evaluate_regression.py:68-87: total_vf_dim = semantic width + 6 or 5 emotion classes."""
     return VideoRegression(n_layers=args.n_layers, d_model=args.d_model, d_hidden=args.dim_feedforward, use_KAN=args.use_KAN,
                            max_sequence_video=args.max_sequence_video, total_vf_dim=sem_dim + (6 if args.emo_model.startswith("6c") else 5),
-                           regModel=args.regModel)
+                           regModel=args.regModel, wide_recurrent=True)
 
 
 def load_model(args, sem_dim, device):

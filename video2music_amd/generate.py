@@ -48,7 +48,7 @@ def regression_levels(args, f, device):
     from .model.video_regression import VideoRegression
     reg = VideoRegression(n_layers=args.n_layers_reg, d_model=args.d_model_reg, d_hidden=args.dim_feedforward_reg,
                           max_sequence_video=args.max_sequence_video, total_vf_dim=f["semantic"].shape[-1] + f["emotion"].shape[-1],
-                          regModel=args.regModel).eval()
+                          regModel=args.regModel, wide_recurrent=True).eval()
     if args.synthetic or args.synthetic_weights:
         shapes = [(k, tuple(v.shape)) for k, v in reg.state_dict().items()]
         reg.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic.synthetic_state_dict(shapes, seed=1).items()})

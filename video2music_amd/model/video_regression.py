@@ -14,7 +14,8 @@ library's kernels; no torch arithmetic runs in `forward`:
     Conv1d + SiLU             amt_dwconv1d_silu_fwd
     softplus, scan, gate      amt_selective_scan_fwd
     LayerNorms                amt_layernorm_post_fwd (residual in, `x_f + x_b` out)
-    LSTM / GRU recurrence     amt_rnn_seq_fwd (both directions of a layer in one launch)
+    LSTM / GRU recurrence     amt_rnn_seq_fwd (both directions of a layer in one launch); d_model above 128, accepted with
+                              `wide_recurrent=True` (multiples of 32 up to 512): amt_rnn_wide_seq_fwd, one launch per time step
 
 The backward Mamba block runs with `reverse=1` instead of `torch.flip` before and after (bimamba.py:171-185).
 
@@ -139,7 +140,7 @@ class _BiMambaEncoderParams(nn.Module):
 
 class VideoRegression(HasDerived, nn.Module):
     def __init__(self, n_layers=2, d_model=64, d_hidden=1024, dropout=0.1, use_KAN=False, max_sequence_video=300,
-                 total_vf_dim=0, regModel="bilstm", scene_embed=False, chord_embed=False):
+                 total_vf_dim=0, regModel="bilstm", scene_embed=False, chord_embed=False, *, wide_recurrent=False):
         super().__init__()
         if regModel not in ("bimamba+", "bimamba", "mamba", "mamba+", "moe_bimamba+", "sharedmoe_bimamba+", "lstm", "bilstm", "gru", "bigru",
                             "cnngru", "cnnbigru", "moemamba"):
@@ -154,6 +155,10 @@ class VideoRegression(HasDerived, nn.Module):
             moe = cls(GLUExpert(d_model, d_model * 2 + 1), d_model, n_experts=6, n_experts_per_token=2, dropout=dropout)
         if use_KAN or scene_embed or chord_embed:
             raise NotImplementedError("use_KAN / scene_embed / chord_embed are outside this path")
+        recurrent = regModel in ("lstm", "bilstm", "gru", "bigru", "cnngru", "cnnbigru")
+        if wide_recurrent and recurrent and d_model > ops.RNN_NARROW_MAX and (d_model % 32 != 0 or d_model > 512):
+            raise ValueError("wide_recurrent: above 128 the recurrent heads stream W_hh onto the matrix pipe (csrc/rnn_wide.hip): d_model must be "
+                             f"a multiple of 32, at most 512 (got {d_model})")
         if d_model % 32 != 0 or (d_hidden % 32 != 0 and regModel != "moemamba"):       # 'moemamba': d_hidden is d_state, no GEMM's K
             raise ValueError("d_model and d_hidden must be multiples of 32 (GEMM K step)")
         if d_model > 512 and regModel not in ("lstm", "bilstm", "gru", "bigru", "cnngru", "cnnbigru"):
@@ -161,10 +166,10 @@ class VideoRegression(HasDerived, nn.Module):
                              "dt projection reads")
         self.n_layers, self.d_model, self.d_hidden = n_layers, d_model, d_hidden
         self.max_seq_video, self.total_vf_dim, self.regModel = max_sequence_video, total_vf_dim, regModel
-        self._rnn = regModel in ("lstm", "bilstm", "gru", "bigru", "cnngru", "cnnbigru")
+        self._rnn = recurrent
         if self._rnn:
             # torch's own modules as parameter containers (same keys: weight_ih_l0, ..., *_reverse); their forward is never called
-            if d_model > 128 or d_model % 8:
+            if (d_model > 128 and not wide_recurrent) or d_model % 8:
                 raise ValueError("the recurrent heads keep W_hh in registers: d_model must be a multiple of 8, at most 128")
             cls = nn.LSTM if "lstm" in regModel else nn.GRU
             self._dirs = 2 if "bi" in regModel else 1
@@ -435,7 +440,8 @@ class VideoRegression(HasDerived, nn.Module):
             for l in range(self.n_layers):               # both directions: one input GEMM, one recurrence launch
                 wi, bi, wh, bh = self._rnn_layer(l)
                 out = torch.empty(B * S, self._dirs * d, device=dev, dtype=torch.float32)
-                ops.rnn_seq(ops.linear_ex(x, wi, bi), wh, bh, out, 0, B, S, d, gates, n_dirs=self._dirs)
+                seq = ops.rnn_wide_seq if d > ops.RNN_NARROW_MAX else ops.rnn_seq        # the width picks the kernel
+                seq(ops.linear_ex(x, wi, bi), wh, bh, out, 0, B, S, d, gates, n_dirs=self._dirs)
                 x = out
             return x.view(B, S, self._dirs * d)
         if not self._bidirectional:                     # Mamba.forward (mamba.py:73-78): x = mixer(norm(x)) + x per layer

@@ -253,7 +253,42 @@ def rnn_seq_bwd(dy, dy_col, reserve, y, y_col, w_hh, dxproj, dhn, B, L, d, gates
     return dxproj, dhn
 
 
-REG_LOSS_WS_FLOATS = 516        # AMT_REG_LOSS_WS_FLOATS of include/amt_hip.h
+RNN_NARROW_MAX = 128            # hidden sizes up to here run the register kernels (csrc/rnn.hip); beyond, csrc/rnn_wide.hip
+
+
+def rnn_wide_ws(B, d, gates, n_dirs, device):
+    """The scratch of one wide recurrence call (amt_rnn_wide_ws_floats); the kernels never read it before they wrote it."""
+    n = _lib.call("amt_rnn_wide_ws_floats", B, d, gates, n_dirs)          # -1: a shape the call itself refuses, with its reason
+    return torch.empty(max(n, 1), device=device, dtype=torch.float32)
+
+
+def rnn_wide_seq(xproj, w_hh, b_hh, y, col, B, L, d, gates, reverse=False, n_dirs=1):
+    """`rnn_seq` for hidden sizes 32 .. 512, a multiple of 32 (amt_rnn_wide_seq_fwd: one step launch per time step, W_hh streamed from
+    L2 onto the matrix pipe); same arguments, same layouts."""
+    ws = rnn_wide_ws(B, d, gates, n_dirs, y.device)
+    _lib.call("amt_rnn_wide_seq_fwd", p(xproj), xproj.shape[1], p(w_hh), p(b_hh), _off(y, col), y.shape[1], B, L, d, gates, int(reverse),
+              n_dirs, p(ws), _st())
+    return y
+
+
+def rnn_wide_seq_train(xproj, w_hh, b_hh, y, col, reserve, B, L, d, gates, reverse=False, n_dirs=1):
+    """`rnn_seq_train` for hidden sizes 32 .. 512 (amt_rnn_wide_seq_train_fwd): the reserve layout is `rnn_seq_train`'s, y is
+    `rnn_wide_seq`'s bits."""
+    ws = rnn_wide_ws(B, d, gates, n_dirs, y.device)
+    _lib.call("amt_rnn_wide_seq_train_fwd", p(xproj), xproj.shape[1], p(w_hh), p(b_hh), _off(y, col), y.shape[1], p(reserve), reserve.shape[1],
+              B, L, d, gates, int(reverse), n_dirs, p(ws), _st())
+    return y
+
+
+def rnn_wide_seq_bwd(dy, dy_col, reserve, y, y_col, w_hh, dxproj, dhn, B, L, d, gates, reverse=False, n_dirs=1):
+    """`rnn_seq_bwd` for hidden sizes 32 .. 512 (amt_rnn_wide_seq_bwd): same arguments, dxproj / dhn in the same layout."""
+    ws = rnn_wide_ws(B, d, gates, n_dirs, dy.device)
+    _lib.call("amt_rnn_wide_seq_bwd", _off(dy, dy_col), dy.shape[1], p(reserve), reserve.shape[1], _off(y, y_col), y.shape[1], p(w_hh),
+              p(dxproj), dxproj.shape[1], p(dhn), 0 if dhn is None else dhn.shape[1], B, L, d, gates, int(reverse), n_dirs, p(ws), _st())
+    return dxproj, dhn
+
+
+REG_LOSS_WS_FLOATS = 516       # AMT_REG_LOSS_WS_FLOATS of include/amt_hip.h
 
 
 def reg_loss(ln_nd, inst, note_density, loudness, instrument):

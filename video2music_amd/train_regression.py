@@ -189,7 +189,7 @@ def main(argv=None, trainable=TRAINABLE, opt_in=False):
     torch.manual_seed(args.seed)
     model = VideoRegression(n_layers=args.n_layers, d_model=args.d_model, d_hidden=args.dim_feedforward, dropout=args.dropout,
                             use_KAN=args.use_KAN, max_sequence_video=args.max_sequence_video,
-                            total_vf_dim=train["semantic"].shape[-1] + (6 if args.emo_model.startswith("6c") else 5), regModel=args.regModel)
+                            total_vf_dim=train["semantic"].shape[-1] + (6 if args.emo_model.startswith("6c") else 5), regModel=args.regModel, wide_recurrent=True)
     start_epoch = BASELINE_EPOCH
     if args.continue_weights is not None:
         model.load_state_dict(torch.load(args.continue_weights, map_location="cpu"))
