@@ -53,7 +53,8 @@
                                     amt_glu_bwd_ws_floats, amt_glu_bwd;
                                 13: amt_diff_subln_train_fwd, amt_diff_subln_bwd, amt_diff_subln_bwd_blocks, amt_moe_train_fwd_balanced;
                                 14: amt_selective_scan_wide_train_fwd, amt_selective_scan_wide_ckpt_steps, amt_selective_scan_wide_bwd,
-                                    amt_selective_scan_wide_bwd_ws_floats, amt_silu_bwd */
+                                    amt_selective_scan_wide_bwd_ws_floats, amt_silu_bwd;
+                                    (still 14) amt_rnn_wide_*, amt_chord_loss_aux_*, amt_optim_step, amt_optim_plan: additions only */
 
 #ifdef __cplusplus
 extern "C" {
@@ -843,6 +844,51 @@ int64_t amt_chord_loss_aux_ws_floats(int32_t B, int32_t L);
 int32_t amt_chord_loss_aux_fwd_bwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, int32_t B, int32_t L,
                                    float w_chord, float w_emotion, float smoothing, int32_t layout, float* loss, float* clip_out,
                                    float* dlogits, float* ws, void* stream);
+
+/* One fused multi-tensor optimiser step (csrc/optim.hip): torch's RAdam (coupled or decoupled weight decay) and the reference's
+ * RAdanW (model/RAdanW.py) in its foreach variant (:319-445, what the reference runs on a GPU) and its single-tensor variant
+ * (:223-317); the two are different optimisers and both are restated as written, the writes into the gradient included.
+ * One launch on `stream` updates n_tensors <= AMT_OPTIM_MAX_TENSORS tensors that share a step count; the pointer tables are read on
+ * the host during the call (they travel in the kernel arguments) and may be reused as soon as it returns.  Nothing waits on the host.
+ * Tensor t: p (parameter), g (gradient), m (exp_avg), v (exp_avg_sq), and for the RAdanW modes ed (exp_diff), eds (exp_diff_sq),
+ * npg (neg_prev_grad): numel[t] contiguous floats each, every pointer 16-byte aligned.  Written: p, m, v; under RAdanW also g, ed,
+ * eds, npg.  npg_from_grad != 0: npg is not read, -g stands in for it (the steps at which the reference re-initialises it).
+ * The scalars are the step's, formed by the caller in double exactly as the Python of torch / the reference forms them
+ * (video2music_amd/optim.py): decay = 1 - lr wd (1 where the mode has none), weight_decay the coupled one of AMT_OPTIM_RADAM (else 0),
+ * rectified = rho_t > 5, rect_step_size = -(sqrt(bias_correction2) lr rect / bias_correction1) and unrect_step_size =
+ * -(lr / bias_correction1) for the foreach forms; bias_correction1, bias_correction2_sqrt and rect for AMT_OPTIM_RADANW_SINGLE.
+ * Refused before any launch (status -1): an unknown mode, n_tensors outside 1..AMT_OPTIM_MAX_TENSORS, a null or misaligned pointer,
+ * numel <= 0.  The bits of every output depend on the element's inputs and the scalars alone: not on the grid, not on how the
+ * caller batches tensors into launches. */
+#define AMT_OPTIM_MAX_TENSORS 48
+#define AMT_OPTIM_RADAM 0
+#define AMT_OPTIM_RADAMW 1
+#define AMT_OPTIM_RADANW_FOREACH 2
+#define AMT_OPTIM_RADANW_SINGLE 3
+typedef struct amt_optim_args {
+    int32_t mode, n_tensors;
+    float* const* p;
+    float* const* g;
+    float* const* m;
+    float* const* v;
+    float* const* ed;
+    float* const* eds;
+    float* const* npg;
+    const int64_t* numel;
+    float lr, decay, weight_decay, one_minus_beta1, beta2, one_minus_beta2, eps;
+    float rect_step_size, unrect_step_size, bias_correction1, bias_correction2_sqrt, rect;
+    float beta3, one_minus_beta3, neg_one_minus_beta3, beta4, one_minus_beta4;
+    int32_t rectified, npg_from_grad;
+} amt_optim_args;
+int32_t amt_optim_step(const amt_optim_args* a, void* stream);
+/* The launcher's own constants, evaluated on the host (no device, no stream; a value, not a status; negative for an unknown query):
+ * tensors per launch, elements per chunk (a block's unit of work: tensors are cut into chunks, the chunks dealt to the blocks
+ * round-robin), the cap on the grid, and the block size. */
+#define AMT_OPTIM_PLAN_MAX_TENSORS 0
+#define AMT_OPTIM_PLAN_CHUNK 1
+#define AMT_OPTIM_PLAN_MAX_BLOCKS 2
+#define AMT_OPTIM_PLAN_THREADS 3
+int32_t amt_optim_plan(int32_t what);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,16 @@ class V2DecideArgs(C.Structure):             # amt_v2_decide_args
     _fields_ = [("tokens", _P), ("roots", _P), ("attrs", _P), ("T", _I), ("n_primer", _I), ("beam", _I), ("max_conseq_N", _I),
                 ("max_conseq_chord", _I), ("temperature", _F), ("uniforms", _P), ("chord_embed", _I)]
 
+OPTIM_MAX_TENSORS = 48                       # AMT_OPTIM_MAX_TENSORS
+
+
+class OptimArgs(C.Structure):                # amt_optim_args
+    _fields_ = ([("mode", _I), ("n_tensors", _I)] + [(k, _P) for k in ("p", "g", "m", "v", "ed", "eds", "npg", "numel")]
+                + [(k, _F) for k in ("lr", "decay", "weight_decay", "one_minus_beta1", "beta2", "one_minus_beta2", "eps", "rect_step_size",
+                                     "unrect_step_size", "bias_correction1", "bias_correction2_sqrt", "rect", "beta3", "one_minus_beta3",
+                                     "neg_one_minus_beta3", "beta4", "one_minus_beta4")]
+                + [("rectified", _I), ("npg_from_grad", _I)])
+
 # name -> argtypes (restype is int32 unless listed in _RESTYPES); mirrors include/amt_hip.h
 SIGNATURES = {
     "amt_last_error": [],
@@ -159,6 +169,8 @@ SIGNATURES = {
     "amt_silu_bwd": [_P, _P, _P, C.c_int64, _P],
     "amt_chord_loss_aux_ws_floats": [_I, _I],
     "amt_chord_loss_aux_fwd_bwd": [_P, _I, _P, _P, _I, _I, _F, _F, _F, _I, _P, _P, _P, _P, _P],
+    "amt_optim_step": [C.POINTER(OptimArgs), _P],
+    "amt_optim_plan": [_I],
 }
 _RESTYPES = {"amt_last_error": C.c_char_p, "amt_decode_step_bytes": C.c_int64, "amt_moe_scratch_floats": C.c_int64, "amt_moe_topk_scratch_floats": C.c_int64,
              "amt_v2_step_ws_floats": C.c_int64, "amt_v2_step_batch_ws_floats": C.c_int64, "amt_moe_ep_expert_scratch_floats": C.c_int64,
@@ -167,7 +179,7 @@ _RESTYPES = {"amt_last_error": C.c_char_p, "amt_decode_step_bytes": C.c_int64, "
              "amt_glu_train_scratch_floats": C.c_int64, "amt_glu_bwd_ws_floats": C.c_int64,
              "amt_selective_scan_wide_bwd_ws_floats": C.c_int64, "amt_chord_loss_aux_ws_floats": C.c_int64, "amt_rnn_wide_ws_floats": C.c_int64}
 _NO_STATUS = set(_RESTYPES) | {"amt_abi_version", "amt_v2_last_step_launches", "amt_gemm_route", "amt_attn_route", "amt_decode_gemm_ex_lean", "amt_moe_wgrad_splits",
-                                  "amt_rmsnorm_bwd_blocks", "amt_diff_subln_bwd_blocks", "amt_selective_scan_wide_ckpt_steps"}
+                                  "amt_rmsnorm_bwd_blocks", "amt_diff_subln_bwd_blocks", "amt_selective_scan_wide_ckpt_steps", "amt_optim_plan"}
 
 ABI_VERSION = 14        # AMT_ABI_VERSION of include/amt_hip.h these prototypes were written against
 

@@ -649,3 +649,63 @@ def glu_bwd(dout, x, saved, tensors_t, mask_h, dff_raw):
     _lib.call("amt_glu_bwd", p(dout), p(x), p(saved), p(w1t), p(wgt), p(w2t), p(mask_h), p(dx), p(dw1), p(db1), p(dwg), p(dbg), p(dw2),
               p(db2), p(ws), n, d, dff, dff_raw, glu, _st())
     return dx, (dw1, db1, dwg, dbg, dw2, db2)
+
+
+OPTIM_MODES = {"radam": 0, "radamw": 1, "radanw_foreach": 2, "radanw_single": 3}      # AMT_OPTIM_* of include/amt_hip.h
+OPTIM_ADAN = ("radanw_foreach", "radanw_single")
+OPTIM_STREAMS = ("p", "g", "m", "v", "ed", "eds", "npg")
+# fp32 tensors a step reads / writes per element, the figure behind the bytes-per-second of tools/bench_optim.py
+OPTIM_TENSORS_MOVED = {"radam": (4, 3), "radamw": (4, 3), "radanw_foreach": (7, 7), "radanw_single": (7, 7)}
+
+
+def optim_plan():
+    """amt_optim_plan: the optimiser launcher's own constants (needs no GPU): {max_tensors, chunk, max_blocks, threads}."""
+    return {k: _lib.call("amt_optim_plan", i) for i, k in enumerate(("max_tensors", "chunk", "max_blocks", "threads"))}
+
+
+def optim_check(t, what, shape=None):
+    """The data pointer of `t` if `amt_optim_step` can take it (fp32, contiguous, 16-byte aligned, not empty, of `shape` when given);
+    AmtError otherwise.  On the optimiser's per-tensor path: nothing is formatted unless it fails."""
+    q = t.data_ptr()
+    if t.dtype is torch.float32 and q and not q & 15 and (shape is None or t.shape == shape) and t.is_contiguous():
+        return q
+    why = (f"is {t.dtype}: the kernel is built for float32" if t.dtype is not torch.float32 else "is not contiguous" if not t.is_contiguous()
+           else "has no elements" if t.numel() < 1 else "is not 16-byte aligned" if q & 15
+           else f"has shape {tuple(t.shape)}, its parameter {tuple(shape)}")
+    raise _lib.AmtError(f"optim_step: {what} {why}")
+
+
+def optim_launch(mode, ptrs, numels, scalars):
+    """amt_optim_step on the current stream over checked tensors: `ptrs` {stream: [data pointers]} under OPTIM_STREAMS (the first four
+    for the RAdam modes), `numels` their element counts; ceil(n / max_tensors) launches, returns that count.  The library checks
+    alignment, null pointers and counts again before each launch; dtype and contiguity are the caller's (`optim_check`)."""
+    keys = OPTIM_STREAMS if mode in OPTIM_ADAN else OPTIM_STREAMS[:4]
+    n, cap = len(numels), _lib.OPTIM_MAX_TENSORS
+    args = _lib.OptimArgs(mode=OPTIM_MODES[mode], **scalars)
+    st, launches = _st(), 0
+    for b0 in range(0, n, cap):
+        nb = min(cap, n - b0)
+        tables = [(C.c_void_p * nb)(*ptrs[k][b0:b0 + nb]) for k in keys]
+        numel = (C.c_int64 * nb)(*numels[b0:b0 + nb])
+        args.n_tensors = nb
+        for k, table in zip(keys, tables):
+            setattr(args, k, C.cast(table, C.c_void_p))
+        args.numel = C.cast(numel, C.c_void_p)
+        _lib.call("amt_optim_step", C.byref(args), st)
+        launches += 1
+    return launches
+
+
+def optim_step(mode, tensors, scalars):
+    """One fused update of every tensor in `tensors`, a dict of equally long lists under OPTIM_STREAMS ('ed', 'eds', 'npg' for the RAdanW
+    modes only), all of one step count.  `scalars`: the step's coefficients by the field names of `amt_optim_args`
+    (`optim.step_scalars` forms them).  Every tensor is checked before the first launch (`optim_check`), then `optim_launch`."""
+    keys = OPTIM_STREAMS if mode in OPTIM_ADAN else OPTIM_STREAMS[:4]
+    n = len(tensors["p"])
+    if n < 1:
+        raise _lib.AmtError("optim_step: no tensor")
+    for k in keys:
+        if len(tensors[k]) != n:
+            raise _lib.AmtError(f"optim_step: {len(tensors[k])} tensors under '{k}', {n} parameters")
+    ptrs = {k: [optim_check(t, f"tensor {i} of '{k}'", tensors["p"][i].shape) for i, t in enumerate(tensors[k])] for k in keys}
+    return optim_launch(mode, ptrs, [t.numel() for t in tensors["p"]], scalars)

@@ -21,6 +21,7 @@ entry point): the class the reference's ``train.py:136-168`` builds, trained thr
 the same loop, files and schedule.  With the default empty ``families`` every answer is the one above.  ``train_v3`` adds the V3
 family and ``-balancing`` (``opt_in=True``: the model's ``enable_training()`` is called after it is built).  ``train_losses`` adds
 ``-auxiliary_loss`` and ``-drop_loss`` to that (``losses=True``); here and in the two entry points between, both stay refused.
+``train_optim`` adds ``-optimizer RAdam / RAdamW / RAdanW`` to that (``optimizers=True``, ``video2music_amd/optim.py``).
 
     python -m video2music_amd.train -dataset_dir ./dataset/ -music_gen_version None -chord_embed "" -motion_type 1
 """
@@ -36,8 +37,8 @@ from . import metrics, ops
 from .dataset import vevo_features as VF
 from .losses import chord_train_loss
 from .model.video_music_transformer import VideoMusicTransformer
-from .train_regression import (BASELINE_EPOCH, LR_DEFAULT_START, PREPEND_ZEROS_WIDTH, SCHEDULER_WARMUP_STEPS, SEPERATOR, LrStepTracker,
-                               make_optimizer, names_of)
+from .train_regression import (ADAM_BETA_1, ADAM_BETA_2, ADAM_EPSILON, BASELINE_EPOCH, LR_DEFAULT_START, PREPEND_ZEROS_WIDTH,
+                               SCHEDULER_WARMUP_STEPS, SEPERATOR, LrStepTracker, make_optimizer, names_of)
 from .utilities.argument_funcs import parse_train_args
 from .utilities.constants import IS_SEPERATED, LOSS_LAMBDA, VERSION
 from .utilities.device import get_device
@@ -104,11 +105,14 @@ def refuse_family(args, families, balancing=False):
     return None
 
 
-def refuse(args, families=(), balancing=False, losses=False):
+CHORD_OPTIMIZERS = ("Adam", "AdamW", "RAdam", "RAdamW", "RAdanW")     # what `optimizers=True` admits (reference train.py:237-250 less Lion)
+
+
+def refuse(args, families=(), balancing=False, losses=False, optimizers=False):
     """The reason this build does not run `args`, or None.  families: the -music_gen_version strings the caller trains beside the base
     model (`train_families.TRAINABLE`); empty, the answers are the base entry point's.  balancing (default off; `train_v3` sets it):
     -balancing is admitted for a family version.  losses (default off; `train_losses` sets it): -auxiliary_loss and -drop_loss are
-    admitted."""
+    admitted.  optimizers (default off; `train_optim` sets it): -optimizer RAdam, RAdamW and RAdanW are admitted."""
     family = bool(families) and args.music_gen_version is not None
     if args.force_cpu:
         return "--force_cpu: video2music_amd has no CPU path (the CPU oracle lives in oracle/ for tests only)"
@@ -135,7 +139,11 @@ def refuse(args, families=(), balancing=False, losses=False):
         return "-augmentation is not built: the clips are read as they are"
     if not args.no_tensorboard:
         return "--no_tensorboard False: tensorboard reporting is not built (results.csv holds the same figures)"
-    if args.optimizer not in (None, "Adam", "AdamW"):
+    if optimizers and args.optimizer == "Lion":
+        return "-optimizer Lion: lion_pytorch is a package the reference does not vendor, and it is not installed"
+    if optimizers and args.optimizer not in (None,) + CHORD_OPTIMIZERS:
+        return f"-optimizer {args.optimizer}: {', '.join(CHORD_OPTIMIZERS)}"
+    if not optimizers and args.optimizer not in (None, "Adam", "AdamW"):
         return f"-optimizer {args.optimizer}: Adam or AdamW (RAdam, RAdamW, RAdanW and Lion are not ported)"
     if (args.continue_weights is None) != (args.continue_epoch is None):
         return "-continue_weights and -continue_epoch go together"
@@ -271,11 +279,26 @@ def build_model(args, total_vf_dim):
     return VideoMusicTransformer_V2(balancing=bool(args.balancing), **fam)
 
 
-def main(argv=None, families=(), opt_in=False, losses=False):
-    """opt_in (`train_v3`): -balancing is admitted and the model's `enable_training()` is called after building it.  losses
+def make_chord_optimizer(args, params, lr):
+    """-optimizer with the reference's settings (train.py:237-250): RAdam without decay, RAdamW with weight_decay 0.01 decoupled,
+    RAdanW with betas (ADAM_BETA_1, ADAM_BETA_2, 0.92, 0.99) and weight_decay 0.01 in the variant the reference runs on a GPU; Adam /
+    AdamW are `make_optimizer`'s."""
+    from . import optim
+    if args.optimizer == "RAdam":
+        return optim.RAdam(params, lr=lr, betas=(ADAM_BETA_1, ADAM_BETA_2), eps=ADAM_EPSILON)
+    if args.optimizer == "RAdamW":
+        return optim.RAdam(params, lr=lr, betas=(ADAM_BETA_1, ADAM_BETA_2), eps=ADAM_EPSILON, weight_decay=0.01, decoupled_weight_decay=True)
+    if args.optimizer == "RAdanW":
+        return optim.RAdanW(params, lr=lr, betas=(ADAM_BETA_1, ADAM_BETA_2, 0.92, 0.99), eps=ADAM_EPSILON, weight_decay=0.01, variant="foreach")
+    return make_optimizer(args, params, lr)
+
+
+def main(argv=None, families=(), opt_in=False, losses=False, optimizers=False):
+    """optimizers (`train_optim`): -optimizer RAdam / RAdamW / RAdanW are admitted and run on `video2music_amd.optim`.  opt_in (`train_v3`): -balancing is admitted and the model's `enable_training()` is called after building it.  losses
     (`train_losses`): -auxiliary_loss and -drop_loss are admitted; with -drop_loss the result also holds every step's weights."""
     args = parse_args(argv)
-    why = refuse(args, families, balancing=opt_in, losses=losses)
+    why = refuse(args, families, balancing=opt_in, losses=losses, optimizers=optimizers)
+    make_opt = make_chord_optimizer if optimizers else make_optimizer
     if why:
         raise SystemExit(why)
     device = get_device()
@@ -320,10 +343,10 @@ def main(argv=None, families=(), opt_in=False, losses=False):
     n_batches = (len(train_names) + bs - 1) // bs
     if args.lr is None:
         init_step = 0 if args.continue_epoch is None else args.continue_epoch * n_batches
-        opt = make_optimizer(args, model.parameters(), LR_DEFAULT_START)
+        opt = make_opt(args, model.parameters(), LR_DEFAULT_START)
         lr_scheduler = torch.optim.lr_scheduler.LambdaLR(opt, LrStepTracker(args.d_model, SCHEDULER_WARMUP_STEPS, init_step).step)
     else:
-        opt, lr_scheduler = make_optimizer(args, model.parameters(), args.lr), None
+        opt, lr_scheduler = make_opt(args, model.parameters(), args.lr), None
 
     best_eval_loss, best_eval_loss_epoch = float("inf"), -1
     if not os.path.isfile(results_file):

@@ -15,6 +15,8 @@ order is shuffled per epoch from ``--seed``.
 
 Refused, with the reason: the regModels whose backward is not built (Mamba, mixture and CNN heads), ``-optimizer RAdam / RAdamW``
 (the reference's own optimiser file), ``--force_cpu``, ``-is_video False``, ``-use_KAN``, ``-augmentation``, tensorboard reporting.
+``python -m video2music_amd.train_regression_optim`` (``run(argv, ..., optimizers=True)``) admits ``-optimizer RAdam / RAdamW`` on
+``video2music_amd/optim.py``.
 
     python -m video2music_amd.train_regression -dataset_dir ./dataset/ -regModel bilstm -epochs 50
 """
@@ -72,9 +74,10 @@ UNBUILT = {"mamba": "the RMSNorm backward is not built" + _ALL, "mamba+": "the R
            "cnnbigru": "the backward of its convolution front is not built" + _ALL}
 
 
-def refuse(args, trainable=TRAINABLE):
+def refuse(args, trainable=TRAINABLE, optimizers=False):
     """The reason this build does not run `args`, or None.  `trainable`: the regModels the caller trains (the default: the
-    recurrent heads; train_regression_mamba adds 'bimamba+' and 'bimamba')."""
+    recurrent heads; train_regression_mamba adds 'bimamba+' and 'bimamba').  optimizers (default off; `train_regression_optim` sets
+    it): -optimizer RAdam and RAdamW are admitted."""
     if args.force_cpu:
         return "--force_cpu: video2music_amd has no CPU path (the CPU oracle lives in oracle/ for tests only)"
     if not args.is_video:
@@ -91,9 +94,13 @@ def refuse(args, trainable=TRAINABLE):
                     "mixture and CNN heads run inference here)")
         return (f"-regModel {args.regModel}: {UNBUILT.get(args.regModel, 'no such regression head')}; the backward pass is built for "
                 f"{', '.join(trainable)} (the other heads run inference here)")
-    if args.optimizer in ("RAdam", "RAdamW"):
+    if optimizers and args.optimizer in ("RAdanW", "Lion"):
+        return f"-optimizer {args.optimizer}: the reference's train_regression.py has no such branch; Adam, AdamW, RAdam or RAdamW"
+    if optimizers and args.optimizer not in (None, "Adam", "AdamW", "RAdam", "RAdamW"):
+        return f"-optimizer {args.optimizer}: Adam, AdamW, RAdam or RAdamW"
+    if not optimizers and args.optimizer in ("RAdam", "RAdamW"):
         return f"-optimizer {args.optimizer}: the reference's own RAdam file is not ported; use Adam or AdamW"
-    if args.optimizer not in (None, "Adam", "AdamW"):
+    if not optimizers and args.optimizer not in (None, "Adam", "AdamW"):
         return f"-optimizer {args.optimizer}: Adam or AdamW"
     if (args.continue_weights is None) != (args.continue_epoch is None):
         return "-continue_weights and -continue_epoch go together"
@@ -104,6 +111,17 @@ def make_optimizer(args, params, lr):
     if args.optimizer == "AdamW":
         return torch.optim.AdamW(params, lr=lr, betas=(ADAM_BETA_1, ADAM_BETA_2), eps=ADAM_EPSILON, weight_decay=1e-5)
     return torch.optim.Adam(params, lr=lr, betas=(ADAM_BETA_1, ADAM_BETA_2), eps=ADAM_EPSILON)
+
+
+def make_regression_optimizer(args, params, lr):
+    """-optimizer with the reference's settings (train_regression.py:145-154): RAdam without decay, RAdamW with weight_decay 1e-5
+    decoupled, both on `video2music_amd.optim`; Adam / AdamW are `make_optimizer`'s."""
+    if args.optimizer in ("RAdam", "RAdamW"):
+        from . import optim
+        w = args.optimizer == "RAdamW"
+        return optim.RAdam(params, lr=lr, betas=(ADAM_BETA_1, ADAM_BETA_2), eps=ADAM_EPSILON, weight_decay=1e-5 if w else 0.0,
+                           decoupled_weight_decay=w)
+    return make_optimizer(args, params, lr)
 
 
 def write_model_params(args, path):
@@ -166,10 +184,17 @@ def train_epoch(cur_epoch, model, data, order, batch_size, opt, lr_scheduler=Non
 
 def main(argv=None, trainable=TRAINABLE, opt_in=False):
     """opt_in: call the model's `enable_training()` (train_regression_all: the heads that build a graph only when asked to)."""
+    return run(argv, trainable, opt_in)
+
+
+def run(argv=None, trainable=TRAINABLE, opt_in=False, optimizers=False):
+    """`main`, with one more switch (`main`'s own signature is what the older entry points were written against).  optimizers
+    (`train_regression_optim`): -optimizer RAdam / RAdamW are admitted and run on `video2music_amd.optim`."""
     args = parse_train_args(argv)[0]
-    why = refuse(args, trainable)
+    why = refuse(args, trainable, optimizers)
     if why:
         raise SystemExit(why)
+    make_opt = make_regression_optimizer if optimizers else make_optimizer
     device = get_device()
     if device.type != "cuda":
         raise SystemExit("no GPU visible: video2music_amd runs on MI355X only")
@@ -202,10 +227,10 @@ def main(argv=None, trainable=TRAINABLE, opt_in=False):
     n_batches = (len(train_names) + bs - 1) // bs
     if args.lr is None:
         init_step = 0 if args.continue_epoch is None else args.continue_epoch * n_batches
-        opt = make_optimizer(args, model.parameters(), LR_DEFAULT_START)
+        opt = make_opt(args, model.parameters(), LR_DEFAULT_START)
         lr_scheduler = torch.optim.lr_scheduler.LambdaLR(opt, LrStepTracker(args.d_model, SCHEDULER_WARMUP_STEPS, init_step).step)
     else:
-        opt, lr_scheduler = make_optimizer(args, model.parameters(), args.lr), None
+        opt, lr_scheduler = make_opt(args, model.parameters(), args.lr), None
 
     best_eval_loss, best_eval_loss_epoch = float("inf"), -1
     if not os.path.isfile(results_file):
