@@ -15,8 +15,13 @@
  * of the reference would add.
  *
  * Conventions
- *   - every function returns int32: 0 = ok, < 0 = bad argument, > 0 = hipError_t;
- *     amt_last_error() returns a thread-local message for the last non-zero return.
+ *   - a function declared amt_status returns a status: 0 = ok, < 0 = bad argument, > 0 = hipError_t;
+ *     amt_last_error() returns a thread-local message for the last non-zero return.  Any other return type (int32_t, int64_t,
+ *     const char*) is a value, never a status.  amt_status is int32_t: the distinction is for the reader and for
+ *     video2music_amd/_lib.py, which reads its ctypes prototypes, struct layouts and constants from this file and raises on a
+ *     non-zero return exactly where amt_status is declared.  It reads declarations of the plain forms used below -- `type name(args);`,
+ *     `typedef struct name { fields } name;`, `#define AMT_X <integer>` -- over int32_t, int64_t, float, double, const char* and
+ *     pointers, and refuses anything else at import.
  *   - all tensor arguments are raw DEVICE pointers, fp32 (ids int64), row-major, 16-byte aligned;
  *     the caller owns inputs and outputs; weights are copied (and repacked) into library-owned
  *     memory by amt_load_weight, so caller storage may be freed afterwards.
@@ -61,6 +66,7 @@ extern "C" {
 #endif
 
 typedef struct amt_handle amt_handle;
+typedef int32_t amt_status;      /* 0 = ok, or an error with amt_last_error(): see the conventions above */
 
 /* Constructor arguments of VideoMusicTransformer (model/video_music_transformer.py:911-914) that
  * shape the computation, plus the batch capacity the reference does not have (it is batch-1). */
@@ -83,47 +89,47 @@ int32_t amt_abi_version(void);
  * 64 <= d_model <= 1024; head_dim = d_model / num_heads in {16, 32, 64, 128}; dim_feedforward a multiple of 32, <= 8192 (beyond d_model + dim_feedforward = 1536 the decode step runs without folded LayerNorms, beyond
  * dim_feedforward = 1536 its linear2 product runs in column ranges of 1024);
  * max_batch 1..256 clips per decode chain (larger batches are sliced by the caller, video2music_amd/model). */
-int32_t amt_create(const amt_config* cfg, amt_handle** out);
-int32_t amt_destroy(amt_handle* h);
+amt_status amt_create(const amt_config* cfg, amt_handle** out);
+amt_status amt_destroy(amt_handle* h);
 /* One state_dict entry (reference key names).  `data` may be a host or a
  * device pointer; `shape` has `ndim` entries.  Replaces nn.Module.load_state_dict (generate.py:216). */
-int32_t amt_load_weight(amt_handle* h, const char* name, const float* data, int32_t ndim, const int64_t* shape);
+amt_status amt_load_weight(amt_handle* h, const char* name, const float* data, int32_t ndim, const int64_t* shape);
 /* Validates that every tensor of the hot path is present with the right shape and builds the
  * derived layouts (MFMA-ordered decode weights, Linear_chord tables).  Synchronises the device. */
-int32_t amt_finalize(amt_handle* h);
+amt_status amt_finalize(amt_handle* h);
 
 /* ---- VideoMusicTransformer.forward pieces ------------------------------------------------ */
 /* Video stream + encoder + per-layer cross-attention K/V (video_music_transformer.py:1005-1033,
  * torch nn.TransformerEncoder).  sem (B,S,sem_dim), scene (B,S), motion (B,S,motion_dim) with
  * motion_dim=1 for the scalar form, emotion (B,S,emo_dim).  Optionally copies the encoder memory
  * (B,S,d) to memory_out.  The handle keeps memory / K / V for amt_prefill and amt_generate. */
-int32_t amt_encode(amt_handle* h, int32_t B, int32_t S,
-                   const float* sem, int32_t sem_dim, const float* scene,
-                   const float* motion, int32_t motion_dim, const float* emotion, int32_t emo_dim,
-                   float* memory_out, void* stream);
+amt_status amt_encode(amt_handle* h, int32_t B, int32_t S,
+                      const float* sem, int32_t sem_dim, const float* scene,
+                      const float* motion, int32_t motion_dim, const float* emotion, int32_t emo_dim,
+                      float* memory_out, void* stream);
 /* Teacher-forced decoder pass (video_music_transformer.py:984-1001,1027-1044; rpr.py:24-70) over
  * the clips of the last amt_encode: root/attr ids (B,L) int64, key (B) -> logits (B,L,159).
  * layer_out (optional) receives the output of decoder layer `layer_index` (B,L,d). */
-int32_t amt_prefill(amt_handle* h, int32_t B, int32_t L, const int64_t* root_ids, const int64_t* attr_ids,
-                    const float* key, float* logits_out, float* layer_out, int32_t layer_index, void* stream);
+amt_status amt_prefill(amt_handle* h, int32_t B, int32_t L, const int64_t* root_ids, const int64_t* attr_ids,
+                       const float* key, float* logits_out, float* layer_out, int32_t layer_index, void* stream);
 
 /* ---- VideoMusicTransformer.generate (video_music_transformer.py:1046-1132), batched ------ */
 /* Starts a generation over the B clips of the last amt_encode.  primer* are (B,P) int64 when
  * primer_per_clip != 0, else (P) shared by all clips.  beam: 0 = sampling branch, 1 = verbatim
  * top-1 branch.  Resets the KV cache and the device position counter. */
-int32_t amt_generate_begin(amt_handle* h, int32_t B, const int64_t* primer, const int64_t* primer_root,
-                           const int64_t* primer_attr, int32_t P, int32_t primer_per_clip, const float* key,
-                           int32_t T, int32_t beam, int32_t max_conseq_N, int32_t max_conseq_chord, void* stream);
+amt_status amt_generate_begin(amt_handle* h, int32_t B, const int64_t* primer, const int64_t* primer_root,
+                              const int64_t* primer_attr, int32_t P, int32_t primer_per_clip, const float* key,
+                              int32_t T, int32_t beam, int32_t max_conseq_N, int32_t max_conseq_chord, void* stream);
 /* Switches the sampling branch (beam=0) of the generation in progress from the arg-max decision to the
  * reference's Categorical draw (video_music_transformer.py:1104-1105), done on device by inverse CDF:
  * uniforms is (T,B) fp32 in [0,1), device memory, copied; the token decided from input position t of clip b
  * is the first id whose cumulative masked probability reaches uniforms[t*B+b] * sum.  null switches back.
  * amt_generate_begin resets to arg-max. */
-int32_t amt_generate_set_uniforms(amt_handle* h, const float* uniforms, void* stream);
+amt_status amt_generate_set_uniforms(amt_handle* h, const float* uniforms, void* stream);
 /* Runs `n_steps` decode steps with the arg-max sampler on device (hipGraph replay; oracle G2 for
  * beam=0, G1 for beam=1).  logits_out (optional) is (T,B,159): row t = logits computed from input
  * position t.  n_steps < 0 runs to the end (T-1 steps in total). */
-int32_t amt_generate_run(amt_handle* h, int32_t n_steps, float* logits_out, void* stream);
+amt_status amt_generate_run(amt_handle* h, int32_t n_steps, float* logits_out, void* stream);
 /* Same steps as amt_generate_run, issued eagerly with a HIP event pair recorded on `stream` around
  * every kernel launch (synchronises once per step).  Accumulates, per kernel class
  * {0: self-attention decode, 1: cross-attention decode, 2: skinny GEMMs, 3: sampling head,
@@ -160,103 +166,103 @@ int32_t amt_generate_run(amt_handle* h, int32_t n_steps, float* logits_out, void
  *   "profile_skip" = 1 | 2 | 3 (any time; results become meaningless): measurement hook of bench.py, leaves the self-attention
  *   (bit 0) and / or cross-attention (bit 1) launches out of the captured decode step, so that what a kernel costs the step is
  *   the difference between two timed generates.  0 restores the real step. */
-int32_t amt_set_option(amt_handle* h, const char* name, int32_t value);
+amt_status amt_set_option(amt_handle* h, const char* name, int32_t value);
 /* amt_encode with rows [B*S][d] added to Linear_vis's output before the encoder: reference scene_embed=True
  * (:1016-1027: the scene offset is left out of the feature columns and scene_embedding(offset.int()) is added instead).  The
  * caller keeps the scene column in the features and uploads Linear_vis.weight with a zero column at its position. */
-int32_t amt_encode_resid(amt_handle* h, int32_t B, int32_t S, const float* sem, int32_t sem_dim, const float* scene,
-                         const float* motion, int32_t motion_dim, const float* emotion, int32_t emo_dim,
-                         const float* vis_resid, float* memory_out, void* stream);
-int32_t amt_generate_profile(amt_handle* h, int32_t n_steps, double* ms_by_class, int64_t* launches_by_class,
-                             int64_t* attn_bytes_by_class, void* stream);
+amt_status amt_encode_resid(amt_handle* h, int32_t B, int32_t S, const float* sem, int32_t sem_dim, const float* scene,
+                            const float* motion, int32_t motion_dim, const float* emotion, int32_t emo_dim,
+                            const float* vis_resid, float* memory_out, void* stream);
+amt_status amt_generate_profile(amt_handle* h, int32_t n_steps, double* ms_by_class, int64_t* launches_by_class,
+                                int64_t* attn_bytes_by_class, void* stream);
 /* One decode step that stops before the decision: writes the decision distribution
  * softmax(logits)[:157] with the suppressions applied, (B,157), for a host-side sampler
  * (torch.multinomial = the reference's Categorical.sample), then amt_generate_commit feeds the
  * chosen ids (B) int64 back. */
-int32_t amt_generate_step_probs(amt_handle* h, float* probs_out, void* stream);
-int32_t amt_generate_commit(amt_handle* h, const int64_t* chosen, void* stream);
+amt_status amt_generate_step_probs(amt_handle* h, float* probs_out, void* stream);
+amt_status amt_generate_commit(amt_handle* h, const int64_t* chosen, void* stream);
 /* Between the steps of a host-driven generation (amt_generate_step_probs / amt_generate_commit): the branch of the following
  * steps, 0 = sampling branch (suppressions applied to the distribution, the committed id feeds back as root / attr), 1 = top-k
  * branch (plain softmax[:157], root / attr of the committed position stay PAD).  This is the per-step choice
  * `random.uniform(0,1) <= beam_chance` of model/video_music_transformer.py:1074-1084; the host keeps the `beam` rows. */
-int32_t amt_generate_set_branch(amt_handle* h, int32_t beam);
+amt_status amt_generate_set_branch(amt_handle* h, int32_t beam);
 /* Test access to the self-attention K/V cache, fp32 [2 (K, V)][n_layers][max_batch][H][rows][hd] with rows = max_sequence_chord plus
  * the padding rows of DESIGN.md §4: dims_out (optional, 6 values) receives the shape; buf (optional, n_floats = their product, device
  * memory) receives the cache (write = 0) or replaces it (write = 1). */
-int32_t amt_kv_cache_io(amt_handle* h, float* buf, int64_t n_floats, int32_t write, int64_t* dims_out, void* stream);
+amt_status amt_kv_cache_io(amt_handle* h, float* buf, int64_t n_floats, int32_t write, int64_t* dims_out, void* stream);
 /* Copies the (B,T) int64 token matrix (PAD=158 beyond the generated length) to tokens_out. */
-int32_t amt_generate_end(amt_handle* h, int64_t* tokens_out, void* stream);
+amt_status amt_generate_end(amt_handle* h, int64_t* tokens_out, void* stream);
 /* begin + run(-1) + end. */
-int32_t amt_generate(amt_handle* h, int32_t B, const int64_t* primer, const int64_t* primer_root,
-                     const int64_t* primer_attr, int32_t P, int32_t primer_per_clip, const float* key,
-                     int32_t T, int32_t beam, int32_t max_conseq_N, int32_t max_conseq_chord,
-                     int64_t* tokens_out, float* logits_out, void* stream);
+amt_status amt_generate(amt_handle* h, int32_t B, const int64_t* primer, const int64_t* primer_root,
+                        const int64_t* primer_attr, int32_t P, int32_t primer_per_clip, const float* key,
+                        int32_t T, int32_t beam, int32_t max_conseq_N, int32_t max_conseq_chord,
+                        int64_t* tokens_out, float* logits_out, void* stream);
 /* Timing/roofline introspection for bench.py: algorithmic HBM bytes of the decode-attention
  * launches of one step at key count n_keys (self) — see DESIGN.md. */
 int64_t amt_decode_step_bytes(const amt_handle* h, int32_t B, int32_t n_self_keys, int32_t S);
 
 /* ---- stateless operator entry points (used by the parity tests and standalone modules) --- */
 /* y[M,N] = x[M,K] . w[N,K]^T + bias (+ resid) ; optional ReLU.  torch.nn.functional.linear. K % 32 == 0. */
-int32_t amt_linear_fwd(const float* x, const float* w, const float* bias, const float* resid, float* y,
-                       int32_t M, int32_t N, int32_t K, int32_t relu, void* stream);
+amt_status amt_linear_fwd(const float* x, const float* w, const float* bias, const float* resid, float* y,
+                          int32_t M, int32_t N, int32_t K, int32_t relu, void* stream);
 /* y = LayerNorm(x (+ resid)) (torch.nn.LayerNorm; rpr.py:59-69). */
-int32_t amt_layernorm_fwd(const float* x, const float* resid, const float* w, const float* b, float* y,
-                          int32_t rows, int32_t dim, float eps, void* stream);
+amt_status amt_layernorm_fwd(const float* x, const float* resid, const float* w, const float* b, float* y,
+                             int32_t rows, int32_t dim, float eps, void* stream);
 /* RMSNorm.forward (custom_transformer.py:38-45); w may be null. */
-int32_t amt_rmsnorm_fwd(const float* x, const float* w, float* y, int32_t rows, int32_t dim, float eps, void* stream);
+amt_status amt_rmsnorm_fwd(const float* x, const float* w, float* y, int32_t rows, int32_t dim, float eps, void* stream);
 /* Tail of DifferentialMultiheadAttention (custom_transformer.py:818-826; VideoMusicTransformer_V3): with o1 / o2 the
  * attention outputs of the even / odd heads of a pair over the same values, y = RMSNorm_hd(o1 - lambda_full * o2) * w *
  * out_scale (out_scale = 1 - lambda_init), rows of hd <= 128 values. */
-int32_t amt_diff_subln_fwd(const float* o1, const float* o2, const float* w, float* y, int32_t rows, int32_t hd,
-                           float lambda_full, float out_scale, float eps, void* stream);
+amt_status amt_diff_subln_fwd(const float* o1, const float* o2, const float* w, float* y, int32_t rows, int32_t hd,
+                              float lambda_full, float out_scale, float eps, void* stream);
 /* y = a + b over n floats (n % 4 == 0): the residual add of the pre-norm layers (custom_transformer.py:1241-1249). */
-int32_t amt_add_fwd(const float* a, const float* b, float* y, int64_t n, void* stream);
+amt_status amt_add_fwd(const float* a, const float* b, float* y, int64_t n, void* stream);
 /* y[r][:] = x[r][:] * row_scale[r] (+ add[r][:] when add != null): the video rows dropped by dropTokenRate in the V1 / V2 / V3
  * classes (model/video_music_transformer.py:193-197, 488-492, 798-802: vf * (rand(B,S) > rate), also in eval mode), with the
  * positional rows that follow (:208) as `add`.  dim a multiple of 4. */
-int32_t amt_row_scale_add_fwd(const float* x, const float* row_scale, const float* add, float* y, int32_t rows, int32_t dim,
-                              void* stream);
+amt_status amt_row_scale_add_fwd(const float* x, const float* row_scale, const float* add, float* y, int32_t rows, int32_t dim,
+                                 void* stream);
 /* RMSNorm(x + resid): the post-norm residual form of the custom layers (custom_transformer.py:1233-1240); resid may be null. */
-int32_t amt_rmsnorm_resid_fwd(const float* x, const float* resid, const float* w, float* y, int32_t rows, int32_t dim,
-                              float eps, void* stream);
+amt_status amt_rmsnorm_resid_fwd(const float* x, const float* resid, const float* w, float* y, int32_t rows, int32_t dim,
+                                 float eps, void* stream);
 /* RotaryPositionalEmbeddings.forward (rotate_operation.py:111-165), input_pos=None: x is
  * (n0, seq, n2, hd); cache is the module's (max_seq, cache_half, 2) buffer. */
-int32_t amt_rope_fwd(const float* x, const float* cache, float* y, int32_t n0, int32_t seq, int32_t n2, int32_t hd,
-                     int32_t cache_half, void* stream);
+amt_status amt_rope_fwd(const float* x, const float* cache, float* y, int32_t n0, int32_t seq, int32_t n2, int32_t hd,
+                        int32_t cache_half, void* stream);
 /* Core of multi_head_attention_forward_rpr (rpr.py:387-414) after the projections: q (already
  * scaled), k, v are (B,L,H*hd) row-major; Er (er_len,hd); causal.  o (B,L,H*hd). */
-int32_t amt_rpr_attn_fwd(const float* q, const float* k, const float* v, const float* Er, float* o,
-                         int32_t B, int32_t H, int32_t L, int32_t hd, int32_t er_len, void* stream);
+amt_status amt_rpr_attn_fwd(const float* q, const float* k, const float* v, const float* Er, float* o,
+                            int32_t B, int32_t H, int32_t L, int32_t hd, int32_t er_len, void* stream);
 /* Core of torch MultiheadAttention as used at rpr.py:62-63 / the video encoder: q (B,Lq,H*hd)
  * scaled, k,v (B,Lk,H*hd); no mask (causal=0) or causal. */
 /* The same attention without the causal mask (forward(mask=False), model/video_music_transformer.py:978-982): every key is
  * visible; the relative term stays zero for keys j > i, which is what model/rpr.py:439-455 (_skew) produces. */
-int32_t amt_rpr_attn_nomask_fwd(const float* q, const float* k, const float* v, const float* Er, float* o,
-                                int32_t B, int32_t H, int32_t L, int32_t hd, int32_t er_len, void* stream);
-int32_t amt_cross_attn_fwd(const float* q, const float* k, const float* v, float* o,
-                           int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t causal, void* stream);
+amt_status amt_rpr_attn_nomask_fwd(const float* q, const float* k, const float* v, const float* Er, float* o,
+                                   int32_t B, int32_t H, int32_t L, int32_t hd, int32_t er_len, void* stream);
+amt_status amt_cross_attn_fwd(const float* q, const float* k, const float* v, float* o,
+                              int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t causal, void* stream);
 /* General strided form of the same kernel (used by the V2 stack and MultiheadGQA): tensor[b][h][l][c] lives at
  * base + b*bs + h*hs + l*ls + c with strides = {q_bs,q_hs,q_ls, k_bs,k_hs,k_ls, v_bs,v_hs,v_ls, o_bs,o_hs,o_ls} in
  * elements; q_scale multiplies q (torch MHA: hd^-0.5; 0 = 1); query head h reads kv head h / kv_group. */
-int32_t amt_attn_fwd(const float* q, const float* k, const float* v, float* o, const int64_t* strides,
-                     int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t causal, int32_t kv_group,
-                     float q_scale, void* stream);
+amt_status amt_attn_fwd(const float* q, const float* k, const float* v, float* o, const int64_t* strides,
+                        int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t causal, int32_t kv_group,
+                        float q_scale, void* stream);
 /* Input stage pieces of forward (video_music_transformer.py:984-1030): out[row][0:ld_out] = [sem | scene | motion |
  * emotion | 0-pad]; xf[b*L+l] = PR[root] + PA[attr] + key[b]*wkey + bias + pe[l] with PR = E_root.Wc[:, :d]^T etc. */
-int32_t amt_concat_features_fwd(const float* sem, int32_t sem_dim, const float* scene, const float* motion, int32_t motion_dim,
-                                const float* emotion, int32_t emo_dim, float* out, int32_t rows, int32_t ld_out, void* stream);
-int32_t amt_chord_embed_fwd(const int64_t* root, const int64_t* attr, const float* key, const float* PR, const float* PA,
-                            const float* wkey, const float* bias, const float* pe, float* out,
-                            int32_t B, int32_t L, int32_t d, void* stream);
+amt_status amt_concat_features_fwd(const float* sem, int32_t sem_dim, const float* scene, const float* motion, int32_t motion_dim,
+                                   const float* emotion, int32_t emo_dim, float* out, int32_t rows, int32_t ld_out, void* stream);
+amt_status amt_chord_embed_fwd(const int64_t* root, const int64_t* attr, const float* key, const float* PR, const float* PA,
+                               const float* wkey, const float* bias, const float* pe, float* out,
+                               int32_t B, int32_t L, int32_t d, void* stream);
 /* Decode-step forms: q (B,H*hd) for the token at position pos (host value), K/V caches
  * (B,H,cap,hd); keys 0..pos.  Er may be null (cross-attention: pass pos = S-1). */
-int32_t amt_attn_decode_fwd(const float* q, const float* kcache, const float* vcache, const float* Er, float* o,
-                            int32_t B, int32_t H, int32_t hd, int32_t cap, int32_t pos, int32_t er_len, void* stream);
+amt_status amt_attn_decode_fwd(const float* q, const float* kcache, const float* vcache, const float* Er, float* o,
+                               int32_t B, int32_t H, int32_t hd, int32_t cap, int32_t pos, int32_t er_len, void* stream);
 /* Decode-step projection: y[B,N] = LN?(x)[B,K] . w[N,K]^T + bias (+resid)(relu); packs w on the fly
  * into `w_packed_scratch` (N_pad16*K floats).  ln_w/ln_b may be null.  B <= 32, K % 64 == 0. */
-int32_t amt_decode_linear_fwd(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b,
-                              const float* resid, float* y, float* xn_out, float* w_packed_scratch,
-                              int32_t B, int32_t N, int32_t K, int32_t relu, float eps, void* stream);
+amt_status amt_decode_linear_fwd(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b,
+                                 const float* resid, float* y, float* xn_out, float* w_packed_scratch,
+                                 int32_t B, int32_t N, int32_t K, int32_t relu, float eps, void* stream);
 /* The two kernels of the decode step in the form the handle uses them, with a LayerNorm folded through the projection
  * (reference rpr.py:59-69 computes LayerNorm(u) then the projection):
  * amt_attn_decode_fold_fwd: raw (B, ldq) = u . (W o gamma)^T, columns [0,d) query (and [d,2d) key, [2d,3d) value of the new
@@ -271,11 +277,11 @@ int32_t amt_decode_linear_fwd(const float* x, const float* w, const float* bias,
  *   first K1 columns (all K when x2 is null), y_high (B, n_high) = [x|x2] . w_high^T + b_high.  pro = 1: the staged row is
  *   [relu((x - mu*fold_g)*rstd + fold_c) | LayerNorm(x2)] (statistics of x2's row) and LayerNorm(x2) is y_low's residual.
  *   Weights are given in nn.Linear layout and packed into the scratch buffers (ceil(n/16)*16*K floats each). */
-int32_t amt_attn_decode_fold_fwd(const float* raw, int32_t ldq, float* kcache, float* vcache, const float* Er,
-                                 const float* u, const float* fold_g, const float* fold_c, const float* ln_w,
-                                 const float* ln_b, float* xn_out, float* o, int32_t B, int32_t H, int32_t hd,
-                                 int32_t cap, const int32_t* pos_dev, int32_t n_keys, int32_t er_len, int32_t new_kv,
-                                 float eps, float q_scale, void* stream);
+amt_status amt_attn_decode_fold_fwd(const float* raw, int32_t ldq, float* kcache, float* vcache, const float* Er,
+                                    const float* u, const float* fold_g, const float* fold_c, const float* ln_w,
+                                    const float* ln_b, float* xn_out, float* o, int32_t B, int32_t H, int32_t hd,
+                                    int32_t cap, const int32_t* pos_dev, int32_t n_keys, int32_t er_len, int32_t new_kv,
+                                    float eps, float q_scale, void* stream);
 /* Bit of amt_decode_gemm_args.pro: run the kernel's serial tile loop (LDS read, fix, four MFMAs per k-tile, one after the other) instead
  * of the pipelined one (next tile's reads and fix under this tile's MFMAs).  Same arithmetic in the same order: y_low / y_high are
  * bit-identical either way. */
@@ -297,41 +303,41 @@ typedef struct amt_decode_gemm_args {
     float* scratch_low; float* scratch_high;   /* packed copies of the weights, ceil(n/16)*16*K floats each */
     int32_t B; float eps;
 } amt_decode_gemm_args;
-int32_t amt_decode_gemm_ex_fwd(const amt_decode_gemm_args* a, void* stream);
+amt_status amt_decode_gemm_ex_fwd(const amt_decode_gemm_args* a, void* stream);
 /* Whether amt_decode_gemm_ex_fwd would run this argument block on the kernel's lean front: 1 yes, 0 the generic front (a shape or
  * option outside the lean front's range, or one of the two bits above), negative for a block amt_decode_gemm_ex_fwd refuses.  The
  * launcher's own rule, evaluated on the host: no device, no stream, nothing is read through the pointers; a code, not a status. */
 int32_t amt_decode_gemm_ex_lean(const amt_decode_gemm_args* a);
 /* MultiheadGQA.forward (grouped_query_attention.py:286-358) without RoPE: query/key/value are the
  * caller's (L,B,E) buffers, weights in nn.Linear layout; scratch >= 4*L*B*E floats. */
-int32_t amt_gqa_fwd(const float* query, const float* key, const float* value,
-                    const float* wq, const float* bq, const float* wk, const float* bk, const float* wv, const float* bv,
-                    const float* ln_w, const float* ln_b, const float* wo, const float* bo,
-                    float* out, float* scratch, int32_t L, int32_t S, int32_t B, int32_t E, int32_t query_heads,
-                    int32_t kv_heads, int32_t is_causal, float ln_eps, void* stream);
+amt_status amt_gqa_fwd(const float* query, const float* key, const float* value,
+                       const float* wq, const float* bq, const float* wk, const float* bk, const float* wv, const float* bv,
+                       const float* ln_w, const float* ln_b, const float* wo, const float* bo,
+                       float* out, float* scratch, int32_t L, int32_t S, int32_t B, int32_t E, int32_t query_heads,
+                       int32_t kv_heads, int32_t is_causal, float ln_eps, void* stream);
 /* The same with MultiheadGQA(RoPE=...) (grouped_query_attention.py:316-322): the projected q and k are rotated through the raw
  * (heads, len, B, head_dim) view with the module's cos/sin cache (cache_rows, cache_half, 2) -- cache_half = dim/2 of the
  * RotaryPositionalEmbeddings the caller built, head_dim/2 or a multiple that the view folds (rotate_operation.py:148-149). */
-int32_t amt_gqa_rope_fwd(const float* query, const float* key, const float* value,
-                         const float* wq, const float* bq, const float* wk, const float* bk, const float* wv, const float* bv,
-                         const float* ln_w, const float* ln_b, const float* wo, const float* bo,
-                         float* out, float* scratch, int32_t L, int32_t S, int32_t B, int32_t E, int32_t query_heads,
-                         int32_t kv_heads, int32_t is_causal, float ln_eps, const float* rope_cache, int32_t cache_rows,
-                         int32_t cache_half, void* stream);
+amt_status amt_gqa_rope_fwd(const float* query, const float* key, const float* value,
+                            const float* wq, const float* bq, const float* wk, const float* bk, const float* wv, const float* bv,
+                            const float* ln_w, const float* ln_b, const float* wo, const float* bo,
+                            float* out, float* scratch, int32_t L, int32_t S, int32_t B, int32_t E, int32_t query_heads,
+                            int32_t kv_heads, int32_t is_causal, float ln_eps, const float* rope_cache, int32_t cache_rows,
+                            int32_t cache_half, void* stream);
 /* MoELayer.forward / SharedMoELayer.forward, eval mode (moe.py:167-200,231-302): x (n_tok,d);
  * gate (n_exp,d)+(n_exp); experts' linear1/gate (n_exp,dff,d)+(n_exp,dff), linear2 (n_exp,d,dff)+(n_exp,d);
  * shared_* may be null.  top-k = 2.  idx_out/w_out (optional) receive the routing (n_tok,2).
  * scratch: see amt_moe_scratch_floats. */
 int64_t amt_moe_scratch_floats(int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp);
-int32_t amt_moe_fwd(const float* x, const float* gate_w, const float* gate_b,
-                    const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
-                    const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
-                    float* out, int32_t* idx_out, float* w_out, float* scratch,
-                    int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp, void* stream);
+amt_status amt_moe_fwd(const float* x, const float* gate_w, const float* gate_b,
+                       const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
+                       const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
+                       float* out, int32_t* idx_out, float* w_out, float* scratch,
+                       int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp, void* stream);
 /* The same layer with n_experts_per_token = k, 1 <= k <= 8 (MoELayer / SharedMoELayer constructor argument, moe.py:150-160,202-215; every
  * reference model passes 2): idx_out / w_out are (n_tok, k), the shared expert enters with 1/k; scratch from amt_moe_topk_scratch_floats. */
 int64_t amt_moe_topk_scratch_floats(int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp, int32_t k);
-int32_t amt_moe_topk_fwd(const float* x, const float* gate_w, const float* gate_b,
+amt_status amt_moe_topk_fwd(const float* x, const float* gate_w, const float* gate_b,
                     const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
                     const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
                     float* out, int32_t* idx_out, float* w_out, float* scratch,
@@ -353,21 +359,21 @@ int32_t amt_moe_topk_fwd(const float* x, const float* gate_w, const float* gate_
  * (sw1t, swgt (d, dff), sw2t (dff, d) the shared expert's), prepared by the caller.  An expert without rows gets exact zeros.  No
  * floating-point atomics and a fixed order of every sum: the same inputs give the same bits.  ws: amt_moe_bwd_ws_floats. */
 int64_t amt_moe_train_scratch_floats(int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp, int32_t k, int32_t glu);
-int32_t amt_moe_train_fwd(const float* x, const float* gate_w, const float* gate_b,
+amt_status amt_moe_train_fwd(const float* x, const float* gate_w, const float* gate_b,
                     const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
                     const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
                     const float* mask_h, const float* mask_y, const float* mask_hs,
                     float* out, int32_t* idx_out, float* w_out, float* saved,
                     int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, void* stream);
 int64_t amt_moe_bwd_ws_floats(int32_t n_tok, int32_t d, int32_t dff, int32_t n_exp, int32_t k);
-int32_t amt_moe_bwd(const float* dout, const float* x, const float* gate_w, const float* saved,
-                    const float* w1t, const float* wgt, const float* w2t, const float* sw1t, const float* swgt, const float* sw2t,
-                    const float* mask_h, const float* mask_y, const float* mask_hs,
-                    float* dx, float* dgate_w, float* dgate_b,
-                    float* dw1, float* db1, float* dwg, float* dbg, float* dw2, float* db2,
-                    float* dsw1, float* dsb1, float* dswg, float* dsbg, float* dsw2, float* dsb2,
-                    float* ws, int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, int32_t glu,
-                    int32_t has_shared, float temperature, void* stream);
+amt_status amt_moe_bwd(const float* dout, const float* x, const float* gate_w, const float* saved,
+                       const float* w1t, const float* wgt, const float* w2t, const float* sw1t, const float* swgt, const float* sw2t,
+                       const float* mask_h, const float* mask_y, const float* mask_hs,
+                       float* dx, float* dgate_w, float* dgate_b,
+                       float* dw1, float* db1, float* dwg, float* dbg, float* dw2, float* db2,
+                       float* dsw1, float* dsb1, float* dswg, float* dsbg, float* dsw2, float* dsb2,
+                       float* ws, int32_t n_tok, int32_t d, int32_t dff, int32_t dff_raw, int32_t n_exp, int32_t k, int32_t glu,
+                       int32_t has_shared, float temperature, void* stream);
 /* amt_moe_train_fwd for SharedMoELayer(balancing=True) in training mode (moe.py:257-279): amt_moe_train_fwd's arguments, then
  * sel_bias (n_exp), update_rate and bias_delta (n_exp).  The k experts of a token are those with the largest logit + sel_bias[e],
  * largest first and the lower expert id first among equals; idx keeps that order; wts is the softmax over the RAW logits of those k,
@@ -375,7 +381,7 @@ int32_t amt_moe_bwd(const float* dout, const float* x, const float* gate_w, cons
  * is: the bias has no gradient.  bias_delta[e] = update_rate (mean(c) - c[e]) with c the plan's integer rows per expert as fp32 and
  * mean(c) = (sum c) / n_exp in fp32: what the caller adds to its bias buffer (the library keeps no state).  With sel_bias all zero
  * out / idx_out / w_out / saved are the bits of amt_moe_train_fwd. */
-int32_t amt_moe_train_fwd_balanced(const float* x, const float* gate_w, const float* gate_b,
+amt_status amt_moe_train_fwd_balanced(const float* x, const float* gate_w, const float* gate_b,
                     const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
                     const float* sw1, const float* sb1, const float* swg, const float* sbg, const float* sw2, const float* sb2,
                     const float* mask_h, const float* mask_y, const float* mask_hs,
@@ -392,13 +398,13 @@ int32_t amt_moe_wgrad_splits(int32_t n_tok, int32_t d, int32_t dff, int32_t n_ex
  * travel by all_to_all between amt_moe_route_fwd and amt_moe_combine_fwd, see video2music_amd/model/moe.py):
  * router (moe.py:180-190), one GLUExpert on n rows (moe.py:44-49; scratch >= 2*n*dff floats), and the
  * weighted sum out[t] = w0*y[slot_pos[t,0]] + w1*y[slot_pos[t,1]] in expert-index order (+ shared_scale*shared). */
-int32_t amt_moe_route_fwd(const float* x, const float* gate_w, const float* gate_b, int32_t* idx_out, float* w_out,
-                          int32_t n_tok, int32_t d, int32_t n_exp, void* stream);
-int32_t amt_glu_expert_fwd(const float* x, const float* w1, const float* b1, const float* wg, const float* bg,
-                           const float* w2, const float* b2, float* out, float* scratch,
-                           int32_t n, int32_t d, int32_t dff, void* stream);
-int32_t amt_moe_combine_fwd(const float* y_rows, const int32_t* slot_pos, const int32_t* idx, const float* wts,
-                            const float* shared, float shared_scale, float* out, int32_t n_tok, int32_t d, void* stream);
+amt_status amt_moe_route_fwd(const float* x, const float* gate_w, const float* gate_b, int32_t* idx_out, float* w_out,
+                             int32_t n_tok, int32_t d, int32_t n_exp, void* stream);
+amt_status amt_glu_expert_fwd(const float* x, const float* w1, const float* b1, const float* wg, const float* bg,
+                              const float* w2, const float* b2, float* out, float* scratch,
+                              int32_t n, int32_t d, int32_t dff, void* stream);
+amt_status amt_moe_combine_fwd(const float* y_rows, const int32_t* slot_pos, const int32_t* idx, const float* wts,
+                               const float* shared, float shared_scale, float* out, int32_t n_tok, int32_t d, void* stream);
 /* Expert-parallel execution with the plans on the DEVICE (video2music_amd/model/moe.py:expert_parallel_moe):
  * amt_moe_ep_dispatch_plan_fwd: from one rank's routing idx[2*n_tok] the rows per expert counts_out[n_exp], the send-buffer order
  *   perm[2*n_tok] (send row -> token; ordered by expert, exact packing, so the rows of one destination rank are contiguous) and
@@ -408,13 +414,13 @@ int32_t amt_moe_combine_fwd(const float* y_rows, const int32_t* slot_pos, const 
  * amt_moe_ep_expert_fwd: the rank's e_local experts (stacked tensors as amt_moe_fwd takes them) on the n_recv rows the all_to_all
  *   delivered, grouped by (source rank, local expert) with the segment sizes in DEVICE memory recv_counts[world][e_local]; results
  *   y_out[n_recv][d] in arrival order.  One grouped GEMM launch per projection; scratch: amt_moe_ep_expert_scratch_floats. */
-int32_t amt_moe_ep_dispatch_plan_fwd(const int32_t* idx, int32_t n_tok, int32_t n_exp, int32_t* counts_out, int32_t* perm,
-                                     int32_t* slot_pos, int32_t* ints, void* stream);
-int32_t amt_gather_rows_fwd(const float* src, const int32_t* index, float* dst, int32_t n_rows, int32_t d, void* stream);
+amt_status amt_moe_ep_dispatch_plan_fwd(const int32_t* idx, int32_t n_tok, int32_t n_exp, int32_t* counts_out, int32_t* perm,
+                                        int32_t* slot_pos, int32_t* ints, void* stream);
+amt_status amt_gather_rows_fwd(const float* src, const int32_t* index, float* dst, int32_t n_rows, int32_t d, void* stream);
 int64_t amt_moe_ep_expert_scratch_floats(int32_t n_recv, int32_t d, int32_t dff, int32_t e_local);
-int32_t amt_moe_ep_expert_fwd(const float* rows, const int32_t* recv_counts, int32_t world, int32_t e_local, int32_t n_recv,
-                              const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
-                              float* y_out, float* scratch, int32_t d, int32_t dff, void* stream);
+amt_status amt_moe_ep_expert_fwd(const float* rows, const int32_t* recv_counts, int32_t world, int32_t e_local, int32_t n_recv,
+                                 const float* w1, const float* b1, const float* wg, const float* bg, const float* w2, const float* b2,
+                                 float* y_out, float* scratch, int32_t d, int32_t dff, void* stream);
 
 /* ---- VideoMusicTransformer_V2 '2.2': one KV-cached decode step of one clip ------------------------
  * Issues, from one call, the launch sequence of the decoder restricted to position t (reference
@@ -445,11 +451,11 @@ int32_t amt_moe_ep_expert_fwd(const float* rows, const int32_t* recv_counts, int
  * ws: amt_v2_step_ws_floats(E, dff, n_exp) floats.  E, dff multiples of 64, at most 1536.
  * state_dev (optional): int32 {position, root, attr} in device memory; when given, t / root / attr are read there and the
  * position is incremented at the end of the step, so that one captured graph of the step can be replayed for every token. */
-int32_t amt_pack_weight_fwd(const float* w, float* out, int32_t N, int32_t K, void* stream);
+amt_status amt_pack_weight_fwd(const float* w, float* out, int32_t N, int32_t K, void* stream);
 int64_t amt_v2_step_ws_floats(int32_t E, int32_t dff, int32_t n_exp);
-int32_t amt_v2_step(const void* const* tab, int32_t n_layers, int32_t H, int32_t E, int32_t dff, int32_t n_exp,
-                    int32_t S, int32_t max_seq, int32_t t, int32_t root, int32_t attr, float key, const int32_t* state_dev,
-                    float* logits_out, float* ws, void* stream);
+amt_status amt_v2_step(const void* const* tab, int32_t n_layers, int32_t H, int32_t E, int32_t dff, int32_t n_exp,
+                       int32_t S, int32_t max_seq, int32_t t, int32_t root, int32_t attr, float key, const int32_t* state_dev,
+                       float* logits_out, float* ws, void* stream);
 /* ---- regression head, recurrent variants (video_regression.py:124-135: torch.nn.LSTM / nn.GRU, batch_first) -------------
  * The recurrence of one layer and direction over projected inputs xproj (B, L, ldxp) whose columns [0, gates*d) hold
  * W_ih x + b_ih (gate order of torch: LSTM i,f,g,o; GRU r,z,n): gates = 4 LSTM, 3 GRU; w_hh (gates*d, d), b_hh (gates*d);
@@ -457,15 +463,15 @@ int32_t amt_v2_step(const void* const* tab, int32_t n_layers, int32_t H, int32_t
  * bidirectional layer); reverse = 1 walks t = L-1 .. 0 and writes h at t.  d a multiple of 8, at most 128.
  * n_dirs = 2 runs both directions of a bidirectional layer in one launch: xproj then holds [forward | reverse] projections
  * side by side (2*gates*d columns), w_hh / b_hh the two directions stacked, y gets [h_forward | h_reverse] (2*d columns). */
-int32_t amt_rnn_seq_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
-                        int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, void* stream);
+amt_status amt_rnn_seq_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
+                           int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, void* stream);
 
 /* amt_rnn_seq_fwd that also keeps what the backward needs: y is computed by the same arithmetic, bit for bit.
  * reserve (B*L, ldr), ldr >= n_dirs * C * d, row b*L + t, direction dir at columns [dir*C*d, (dir+1)*C*d), in blocks of d:
  *   LSTM (C = 5): i, f, g, o (activated), c_t            GRU (C = 4): r, z, n (activated), W_hn h_{t-1} + b_hn */
-int32_t amt_rnn_seq_train_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
-                              float* reserve, int32_t ldr, int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse,
-                              int32_t n_dirs, void* stream);
+amt_status amt_rnn_seq_train_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
+                                 float* reserve, int32_t ldr, int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse,
+                                 int32_t n_dirs, void* stream);
 /* Backpropagation through time of one layer (one workgroup per clip and direction, W_hh^T in registers, no atomics: the same
  * inputs give the same bits).  dy (B*L, lddy): gradient of y, this layer's n_dirs*d columns; reserve / y as amt_rnn_seq_train_fwd
  * left them; w_hh as there.  dxproj (B*L, ldxp), n_dirs*gates*d columns laid out like xproj: the gradient with respect to the
@@ -473,9 +479,9 @@ int32_t amt_rnn_seq_train_fwd(const float* xproj, int32_t ldxp, const float* w_h
  * LSTM: the hidden side sees the same values (dW_hh = dxproj^T h_prev, db_hh = db_ih); dhn is not used (may be null).
  * GRU: the hidden side's n block is r * (the input side's); it goes to dhn (B*L, lddhn), n_dirs*d columns, required.
  * h_prev is y shifted by one step in the direction's order, zero at its start.  Shapes and caps as amt_rnn_seq_fwd. */
-int32_t amt_rnn_seq_bwd(const float* dy, int32_t lddy, const float* reserve, int32_t ldr, const float* y, int32_t ldy,
-                        const float* w_hh, float* dxproj, int32_t ldxp, float* dhn, int32_t lddhn, int32_t B, int32_t L,
-                        int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, void* stream);
+amt_status amt_rnn_seq_bwd(const float* dy, int32_t lddy, const float* reserve, int32_t ldr, const float* y, int32_t ldy,
+                           const float* w_hh, float* dxproj, int32_t ldxp, float* dhn, int32_t lddhn, int32_t B, int32_t L,
+                           int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, void* stream);
 
 /* ---- the same recurrences for hidden sizes beyond the register kernels (csrc/rnn_wide.hip) ------------------------------------
  * d a multiple of 32, 32 <= d <= 512 (the lower end overlaps amt_rnn_seq_* on purpose); gates, reverse, n_dirs, B, L and every
@@ -491,14 +497,14 @@ int32_t amt_rnn_seq_bwd(const float* dy, int32_t lddy, const float* reserve, int
  * keeps the LSTM's c there, the backward the carried term (LSTM dc f, GRU dh z); the training forward takes c_{t-1} from
  * reserve and leaves ws alone.  Calls that may overlap must not share a ws. */
 int64_t amt_rnn_wide_ws_floats(int32_t B, int32_t d, int32_t gates, int32_t n_dirs);
-int32_t amt_rnn_wide_seq_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
-                             int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, float* ws, void* stream);
-int32_t amt_rnn_wide_seq_train_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
-                                   float* reserve, int32_t ldr, int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse,
-                                   int32_t n_dirs, float* ws, void* stream);
-int32_t amt_rnn_wide_seq_bwd(const float* dy, int32_t lddy, const float* reserve, int32_t ldr, const float* y, int32_t ldy,
-                             const float* w_hh, float* dxproj, int32_t ldxp, float* dhn, int32_t lddhn, int32_t B, int32_t L,
-                             int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, float* ws, void* stream);
+amt_status amt_rnn_wide_seq_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
+                                int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, float* ws, void* stream);
+amt_status amt_rnn_wide_seq_train_fwd(const float* xproj, int32_t ldxp, const float* w_hh, const float* b_hh, float* y, int32_t ldy,
+                                      float* reserve, int32_t ldr, int32_t B, int32_t L, int32_t d, int32_t gates, int32_t reverse,
+                                      int32_t n_dirs, float* ws, void* stream);
+amt_status amt_rnn_wide_seq_bwd(const float* dy, int32_t lddy, const float* reserve, int32_t ldr, const float* y, int32_t ldy,
+                                const float* w_hh, float* dxproj, int32_t ldxp, float* dhn, int32_t lddhn, int32_t B, int32_t L,
+                                int32_t d, int32_t gates, int32_t reverse, int32_t n_dirs, float* ws, void* stream);
 
 /* The same step for B independent clips in lockstep (all at one position): projections are one launch over B rows (weights
  * read once per step, not once per clip), the caches carry a leading clip dimension (self K/V: B, H, max_seq, hd; cross K/V:
@@ -506,9 +512,9 @@ int32_t amt_rnn_wide_seq_bwd(const float* dy, int32_t lddy, const float* reserve
  * order.  Same pointer table.  keys_dev: B floats; state_dev: int32 {position, root[B], attr[B]} in device memory, the
  * position is incremented at the end; logits_out (B, 159); ws: amt_v2_step_batch_ws_floats(E, dff, n_exp, B) floats. */
 int64_t amt_v2_step_batch_ws_floats(int32_t E, int32_t dff, int32_t n_exp, int32_t B);
-int32_t amt_v2_step_batch(const void* const* tab, int32_t n_layers, int32_t H, int32_t E, int32_t dff, int32_t n_exp,
-                          int32_t S, int32_t max_seq, int32_t B, const float* keys_dev, int32_t* state_dev,
-                          float* logits_out, float* ws, void* stream);
+amt_status amt_v2_step_batch(const void* const* tab, int32_t n_layers, int32_t H, int32_t E, int32_t dff, int32_t n_exp,
+                             int32_t S, int32_t max_seq, int32_t B, const float* keys_dev, int32_t* state_dev,
+                             float* logits_out, float* ws, void* stream);
 
 /* Per-clip decision of the lockstep step, on the device (reference model/video_music_transformer.py:547-600: temperature
  * softmax[:157], N / repeat suppression, top-1 / arg-max / Categorical draw by inverse CDF at uniforms[(pos)*B + b], id ->
@@ -516,9 +522,9 @@ int32_t amt_v2_step_batch(const void* const* tab, int32_t n_layers, int32_t H, i
  * reads the position from state_dev[0], which that call has advanced): stores tokens[b][pos] (and roots / attrs, all
  * [B][T] int64, primer positions pre-filled) and leaves the position's (root, attr) in state_dev for the next step.
  * No host round trip: the pair (step, decide) is captured once and replayed T-1 times. */
-int32_t amt_v2_decide_batch(const float* logits, int32_t ld_logits, int32_t* state_dev, int64_t* tokens, int64_t* roots,
-                            int64_t* attrs, int32_t B, int32_t T, int32_t n_primer, int32_t beam, int32_t max_conseq_N,
-                            int32_t max_conseq_chord, float temperature, const float* uniforms, int32_t chord_embed, void* stream);
+amt_status amt_v2_decide_batch(const float* logits, int32_t ld_logits, int32_t* state_dev, int64_t* tokens, int64_t* roots,
+                               int64_t* attrs, int32_t B, int32_t T, int32_t n_primer, int32_t beam, int32_t max_conseq_N,
+                               int32_t max_conseq_chord, float temperature, const float* uniforms, int32_t chord_embed, void* stream);
 /* amt_v2_step_batch and the decision as ONE launch chain (what the lockstep generate replays T-2 times from a captured graph):
  * the step for the position in state_dev[0] WITHOUT its trailing position increment, then one kernel that decides position
  * state_dev[0] + 1 exactly like amt_v2_decide_batch, writes that position's chord-stream row into ws (the input of the next call,
@@ -540,7 +546,7 @@ typedef struct amt_v2_decide_args {        /* the decision: see amt_v2_decide_ba
 } amt_v2_decide_args;
 /* The caller issues at most T - 1 - n_done calls per generation (positions 0 .. T-2); the position counter in state_dev never
  * advances past T - 1, so a call too many recomputes the last position instead of leaving the caches (T <= max_seq required). */
-int32_t amt_v2_step_decide_batch(const amt_v2_step_args* step, const amt_v2_decide_args* decide, int32_t first, void* stream);
+amt_status amt_v2_step_decide_batch(const amt_v2_step_args* step, const amt_v2_decide_args* decide, int32_t first, void* stream);
 /* Introspection for bench.py: kernel launches issued by the calling thread's last amt_v2_step_batch / amt_v2_step_decide_batch
  * call (a count, not a status). */
 int32_t amt_v2_last_step_launches(void);
@@ -549,26 +555,26 @@ int32_t amt_v2_last_step_launches(void);
 /* Depthwise causal Conv1d(kernel K, padding K-1)[..., :L] + SiLU of MambaBlock.forward (mamba.py:172-175,268-272):
  * x (B,L,C) with row stride ldx, w (C,K) = conv1d.weight (C,1,K), y (B,L,C).  reverse = 1 evaluates the block of the
  * time-flipped sequence and returns it un-flipped (the backward branch of bimamba.py:171-185 without the two flips). */
-int32_t amt_dwconv1d_silu_fwd(const float* x, int32_t ldx, const float* w, const float* bias, float* y,
-                              int32_t B, int32_t L, int32_t C, int32_t K, int32_t reverse, void* stream);
+amt_status amt_dwconv1d_silu_fwd(const float* x, int32_t ldx, const float* w, const float* bias, float* y,
+                                 int32_t B, int32_t L, int32_t C, int32_t K, int32_t reverse, void* stream);
 /* MambaBlock.ssm + gate (mamba.py:291-354, 281-287): delta = softplus(delta_raw + dt_bias), A = -exp(A_log) (ED,N),
  * h_t = exp(delta A) h_{t-1} + delta B_t x_t, y_t = h_t . C_t + D x_t, out = y*silu(z) [+ x*(1 - sigmoid(silu(z))) for
  * version 1 = "Mamba+"].  x / delta_raw / z / y are (B*L, ED) with their own row strides, Bm / Cm (B*L, N) with stride
  * ld_bc (slices of the x_proj output).  N = 16.  reverse as above. */
-int32_t amt_selective_scan_fwd(const float* x, int32_t ldx, const float* delta_raw, int32_t ld_delta, const float* dt_bias,
-                               const float* A_log, const float* Bm, const float* Cm, int32_t ld_bc, const float* D,
-                               const float* z, int32_t ldz, float* y, int32_t ldy, int32_t B, int32_t L, int32_t ED,
-                               int32_t N, int32_t version, int32_t reverse, void* stream);
+amt_status amt_selective_scan_fwd(const float* x, int32_t ldx, const float* delta_raw, int32_t ld_delta, const float* dt_bias,
+                                  const float* A_log, const float* Bm, const float* Cm, int32_t ld_bc, const float* D,
+                                  const float* z, int32_t ldz, float* y, int32_t ldy, int32_t B, int32_t L, int32_t ED,
+                                  int32_t N, int32_t version, int32_t reverse, void* stream);
 /* ---- training the Mamba heads ('bimamba+', 'bimamba'): the two kernels above with what their backward needs, and the backward.
  * d_state N = 16 only (other values are refused with the reason).  No floating-point atomics: the same inputs give the same bits. ---- */
 /* amt_selective_scan_fwd (y: the same bits) that also writes y_pre (B*L, ld_ypre), the un-gated y_t = h_t . C_t + D x_t, and
  * h_chunks [B][ceil(L / 32)][ED][N], the state at the start of every 32-step chunk in the order the scan walks them (reverse = 1:
  * from the last position). */
-int32_t amt_selective_scan_train_fwd(const float* x, int32_t ldx, const float* delta_raw, int32_t ld_delta, const float* dt_bias,
-                                     const float* A_log, const float* Bm, const float* Cm, int32_t ld_bc, const float* D,
-                                     const float* z, int32_t ldz, float* y, int32_t ldy, float* y_pre, int32_t ld_ypre,
-                                     float* h_chunks, int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse,
-                                     void* stream);
+amt_status amt_selective_scan_train_fwd(const float* x, int32_t ldx, const float* delta_raw, int32_t ld_delta, const float* dt_bias,
+                                        const float* A_log, const float* Bm, const float* Cm, int32_t ld_bc, const float* D,
+                                        const float* z, int32_t ldz, float* y, int32_t ldy, float* y_pre, int32_t ld_ypre,
+                                        float* h_chunks, int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse,
+                                        void* stream);
 /* Backward of the scan and its gate from dout (B*L, ld_dout), the forward's inputs, y_pre and h_chunks: the states inside a chunk
  * are recomputed from its checkpoint, the chunks walked from the last to the first.  Writes dx, ddraw (the gradient of delta_raw;
  * its column sums are the gradient of dt_bias), dz (each B*L x ED with its own row stride), dBm / dCm (B*L x N, row stride ld_dbc:
@@ -576,61 +582,61 @@ int32_t amt_selective_scan_train_fwd(const float* x, int32_t ldx, const float* d
  * ceil(ED / 16) per-block copies of dB | dC (B*L x 2N each) and per-clip partials of dA and dD, summed in index order by a second
  * launch. */
 int64_t amt_selective_scan_bwd_ws_floats(int32_t B, int32_t L, int32_t ED, int32_t N);
-int32_t amt_selective_scan_bwd(const float* dout, int32_t ld_dout, const float* x, int32_t ldx, const float* delta_raw,
-                               int32_t ld_delta, const float* dt_bias, const float* A_log, const float* Bm, const float* Cm,
-                               int32_t ld_bc, const float* D, const float* z, int32_t ldz, const float* y_pre, int32_t ld_ypre,
-                               const float* h_chunks, float* dx, int32_t lddx, float* ddraw, int32_t ld_ddraw, float* dz,
-                               int32_t lddz, float* dBm, float* dCm, int32_t ld_dbc, float* dA_log, float* dD, float* ws,
-                               int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse, void* stream);
+amt_status amt_selective_scan_bwd(const float* dout, int32_t ld_dout, const float* x, int32_t ldx, const float* delta_raw,
+                                  int32_t ld_delta, const float* dt_bias, const float* A_log, const float* Bm, const float* Cm,
+                                  int32_t ld_bc, const float* D, const float* z, int32_t ldz, const float* y_pre, int32_t ld_ypre,
+                                  const float* h_chunks, float* dx, int32_t lddx, float* ddraw, int32_t ld_ddraw, float* dz,
+                                  int32_t lddz, float* dBm, float* dCm, int32_t ld_dbc, float* dA_log, float* dD, float* ws,
+                                  int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse, void* stream);
 /* Backward of amt_dwconv1d_silu_fwd from dy (B*L, lddy) and the forward's inputs (the pre-activation is formed again): dx (B*L, C
  * columns, row stride lddx), dw (C, K), dbias (C; null exactly when bias is).  K <= 8.  ws: amt_dwconv1d_silu_bwd_ws_floats floats
  * (the pre-activation's gradient and per-64-row partials of dw | dbias, summed in index order). */
 int64_t amt_dwconv1d_silu_bwd_ws_floats(int32_t B, int32_t L, int32_t C, int32_t K);
-int32_t amt_dwconv1d_silu_bwd(const float* dy, int32_t lddy, const float* x, int32_t ldx, const float* w, const float* bias,
-                              float* dx, int32_t lddx, float* dw, float* dbias, float* ws, int32_t B, int32_t L, int32_t C,
-                              int32_t K, int32_t reverse, void* stream);
+amt_status amt_dwconv1d_silu_bwd(const float* dy, int32_t lddy, const float* x, int32_t ldx, const float* w, const float* bias,
+                                 float* dx, int32_t lddx, float* dw, float* dbias, float* ws, int32_t B, int32_t L, int32_t C,
+                                 int32_t K, int32_t reverse, void* stream);
 /* ---- training the wide-state heads ('moemamba': d_state = d_hidden): N = 32, 64, 128 or 256; N = 16 is refused with a pointer to
  * the calls above.  Same rules: accurate expf / log1pf, no floating-point atomics, the same inputs give the same bits. ---- */
 /* amt_selective_scan_fwd at that N (y: the same bits) that also writes y_pre (B*L, ld_ypre) and h_chunks [B][ceil(L / I)][ED][N], the
  * state at the start of every I-step chunk in walking order, I = amt_selective_scan_wide_ckpt_steps(N) = 32 (two of the kernel's
  * 16-step passes; 0 for an N the call refuses). */
 int32_t amt_selective_scan_wide_ckpt_steps(int32_t N);
-int32_t amt_selective_scan_wide_train_fwd(const float* x, int32_t ldx, const float* delta_raw, int32_t ld_delta, const float* dt_bias,
-                                          const float* A_log, const float* Bm, const float* Cm, int32_t ld_bc, const float* D,
-                                          const float* z, int32_t ldz, float* y, int32_t ldy, float* y_pre, int32_t ld_ypre,
-                                          float* h_chunks, int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse,
-                                          void* stream);
+amt_status amt_selective_scan_wide_train_fwd(const float* x, int32_t ldx, const float* delta_raw, int32_t ld_delta, const float* dt_bias,
+                                             const float* A_log, const float* Bm, const float* Cm, int32_t ld_bc, const float* D,
+                                             const float* z, int32_t ldz, float* y, int32_t ldy, float* y_pre, int32_t ld_ypre,
+                                             float* h_chunks, int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse,
+                                             void* stream);
 /* amt_selective_scan_bwd's outputs at that N.  One workgroup per (16 channels, clip, 16 states).  ws:
  * amt_selective_scan_wide_bwd_ws_floats(B, L, ED, N) floats = ceil(ED / 16) per-block copies of dB | dC (B*L x 2N each), per-clip
  * partials of dA (ED x N) and dD (ED), and N / 16 per-slice partials (B*L x ED each) of d delta and of the scan's part of dx; a second
  * launch adds each in index order and does the element-wise part (softplus', dz, the D x and Mamba+ terms of dx) once. */
 int64_t amt_selective_scan_wide_bwd_ws_floats(int32_t B, int32_t L, int32_t ED, int32_t N);
-int32_t amt_selective_scan_wide_bwd(const float* dout, int32_t ld_dout, const float* x, int32_t ldx, const float* delta_raw,
-                                    int32_t ld_delta, const float* dt_bias, const float* A_log, const float* Bm, const float* Cm,
-                                    int32_t ld_bc, const float* D, const float* z, int32_t ldz, const float* y_pre, int32_t ld_ypre,
-                                    const float* h_chunks, float* dx, int32_t lddx, float* ddraw, int32_t ld_ddraw, float* dz,
-                                    int32_t lddz, float* dBm, float* dCm, int32_t ld_dbc, float* dA_log, float* dD, float* ws,
-                                    int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse, void* stream);
+amt_status amt_selective_scan_wide_bwd(const float* dout, int32_t ld_dout, const float* x, int32_t ldx, const float* delta_raw,
+                                       int32_t ld_delta, const float* dt_bias, const float* A_log, const float* Bm, const float* Cm,
+                                       int32_t ld_bc, const float* D, const float* z, int32_t ldz, const float* y_pre, int32_t ld_ypre,
+                                       const float* h_chunks, float* dx, int32_t lddx, float* ddraw, int32_t ld_ddraw, float* dz,
+                                       int32_t lddz, float* dBm, float* dCm, int32_t ld_dbc, float* dA_log, float* dD, float* ws,
+                                       int32_t B, int32_t L, int32_t ED, int32_t N, int32_t version, int32_t reverse, void* stream);
 /* da[i] = dy[i] s (1 + a[i] (1 - s)), s = sigmoid(a[i]) with the accurate expf: the SiLU's derivative at the pre-activation a, the one
  * launch the backward of CNN_GRU's Conv1d + SiLU front (autograd.ConvSiluFn) adds to the GEMMs. */
-int32_t amt_silu_bwd(const float* dy, const float* a, float* da, int64_t n, void* stream);
+amt_status amt_silu_bwd(const float* dy, const float* a, float* da, int64_t n, void* stream);
 /* out[row] = [a[row][0:da] | b[row][0:db] | 0 ...] (ld_out columns): cat(semantic, emotion) of get_feature
  * (video_regression.py:199-216), zero-padded to the GEMM's K step. */
-int32_t amt_concat2_fwd(const float* a, int32_t da, const float* b, int32_t db, float* out, int32_t rows, int32_t ld_out,
-                        void* stream);
+amt_status amt_concat2_fwd(const float* a, int32_t da, const float* b, int32_t db, float* out, int32_t rows, int32_t ld_out,
+                           void* stream);
 /* amt_linear_fwd with leading dimensions and an activation: y = act(x[M,K](ldx) . w[N,K](ldw)^T + bias (+ resid(ldr)));
  * act 0 none, 1 ReLU, 2 sigmoid (the classifier head, video_regression.py:188-197), 3 SiLU (CNN_GRU's convolution, :88-91).
  * K % 32 == 0. */
-int32_t amt_linear_ex_fwd(const float* x, int32_t ldx, const float* w, int32_t ldw, const float* bias, const float* resid,
-                          int32_t ldr, float* y, int32_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
+amt_status amt_linear_ex_fwd(const float* x, int32_t ldx, const float* w, int32_t ldw, const float* bias, const float* resid,
+                             int32_t ldr, float* y, int32_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, void* stream);
 /* Which kernel the dense GEMM launcher takes for y (M, N) = act(x (M, K) w (N, K)^T ...): 0 the skinny GEMM, 1 the 64x64-tile kernel,
  * 2 the 128x128-tile kernel; negative for a shape or act amt_linear_ex_fwd refuses.  act as amt_linear_ex_fwd's; other_forms != 0
  * stands for the operand and epilogue forms only the library's own callers set (head-split store, row addend, silu-multiply,
  * grouped or gathered rows).  The launcher's own rule, evaluated on the host: no device, no stream; a code, not a status. */
 int32_t amt_gemm_route(int32_t M, int32_t N, int32_t K, int32_t act, int32_t other_forms);
 /* y = LayerNorm(x (+ resid)) + post : the "norm2(x_b + x) then x_f + x_b" step of bimamba.py:183-188 in one pass. */
-int32_t amt_layernorm_post_fwd(const float* x, const float* resid, const float* w, const float* b, const float* post,
-                               float* y, int32_t rows, int32_t dim, float eps, void* stream);
+amt_status amt_layernorm_post_fwd(const float* x, const float* resid, const float* w, const float* b, const float* post,
+                                  float* y, int32_t rows, int32_t dim, float eps, void* stream);
 
 /* ---- evaluation: the test-split metrics of evaluate.py (utilities/run_model_vevo.py:198-452) from teacher-forced logits ---- */
 /* Replaces compute_vevo_accuracy / compute_hits_k / compute_vevo_correspondence (dataset/vevo_dataset.py:653-701,747-810) and the two
@@ -650,9 +656,9 @@ int32_t amt_layernorm_post_fwd(const float* x, const float* resid, const float* 
  * n_hit1, n_hit3, n_hit5, ce_sum over valid rows, bce_sum over all L rows, n_counted, n_right, L}.  Counts are exact (L <= 2^24).
  * The sums are deterministic: a wave tree inside a row, then the rows of a clip added in row order; one launch, no atomics on
  * floats.  pred_out / rank_out / ce_out: (B*L) each, optional (null = not written); ce_out is 0 on ignored rows. */
-int32_t amt_chord_metrics_fwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, const float* emo_prob,
-                              float emo_threshold, int32_t B, int32_t L, float* clip_out,
-                              int32_t* pred_out, int32_t* rank_out, float* ce_out, void* stream);
+amt_status amt_chord_metrics_fwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, const float* emo_prob,
+                                 float emo_threshold, int32_t B, int32_t L, float* clip_out,
+                                 int32_t* pred_out, int32_t* rank_out, float* ce_out, void* stream);
 
 /* Test-split sums of the regression head (reference utilities/run_model_regression.py:70-125): both heads of VideoRegression applied
  * to the encoder output and reduced against the targets, one launch, nothing synchronised.
@@ -668,9 +674,9 @@ int32_t amt_chord_metrics_fwd(const float* logits, int32_t ld, const int64_t* tg
  * count, as the reference averages over max_sequence_video rows).  Deterministic: a fixed 40-term tree inside a row, then the rows of a clip
  * added in row order; no atomics on floats; the optional outputs do not change the sums.
  * ln_nd_out (B*S, 2) = {nd, ld} and inst_out (B*S, 40) = p: optional (null = not written). */
-int32_t amt_reg_metrics_fwd(const float* feat, int32_t ld, int32_t W, const float* w_heads, const float* note_density,
-                            const float* loudness, const float* instrument, int32_t B, int32_t S, float* clip_out,
-                            float* ln_nd_out, float* inst_out, void* stream);
+amt_status amt_reg_metrics_fwd(const float* feat, int32_t ld, int32_t W, const float* w_heads, const float* note_density,
+                               const float* loudness, const float* instrument, int32_t B, int32_t S, float* clip_out,
+                               float* ln_nd_out, float* inst_out, void* stream);
 
 /* Training loss of the regression head (reference utilities/run_model_regression.py:33-39) and its gradient, one launch:
  *   SmoothL1Loss()(ln_nd, [note_density | loudness]) + binary_cross_entropy(inst, instrument)
@@ -682,9 +688,9 @@ int32_t amt_reg_metrics_fwd(const float* feat, int32_t ld, int32_t W, const floa
  * threads; the order of every addition is a function of `rows` alone and no floating-point atomic is used: the same inputs give the
  * same bits. */
 #define AMT_REG_LOSS_WS_FLOATS 516
-int32_t amt_reg_loss_fwd_bwd(const float* ln_nd, const float* inst, const float* note_density, const float* loudness,
-                             const float* instrument, int32_t rows, float* loss, float* d_ln_nd, float* d_logit, float* ws,
-                             void* stream);
+amt_status amt_reg_loss_fwd_bwd(const float* ln_nd, const float* inst, const float* note_density, const float* loudness,
+                                const float* instrument, int32_t rows, float* loss, float* d_ln_nd, float* d_logit, float* ws,
+                                void* stream);
 
 /* ---- training of the chord model (reference train.py, utilities/run_model_vevo.py:73-119) ---- */
 /* amt_attn_fwd that keeps what a backward needs.  Arguments as amt_attn_fwd, plus
@@ -696,10 +702,10 @@ int32_t amt_reg_loss_fwd_bwd(const float* ln_nd, const float* inst, const float*
  * The TRAIN instantiations of the prefill kernels, chosen by shape exactly as the inference calls choose theirs: with keep null, O
  * equals amt_rpr_attn_fwd / amt_cross_attn_fwd / amt_attn_fwd bit for bit.  Head dims 32, 64, 128 (16 is refused: the backward
  * has no instantiation for it). */
-int32_t amt_attn_train_fwd(const float* q, const float* k, const float* v, float* o, const int64_t* strides,
-                           int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t causal, int32_t kv_group,
-                           float q_scale, const float* Er, int32_t er_len, const uint8_t* keep, float keep_scale, float* lse,
-                           void* stream);
+amt_status amt_attn_train_fwd(const float* q, const float* k, const float* v, float* o, const int64_t* strides,
+                              int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t causal, int32_t kv_group,
+                              float q_scale, const float* Er, int32_t er_len, const uint8_t* keep, float keep_scale, float* lse,
+                              void* stream);
 /* Backward of amt_attn_train_fwd: from dO (o's strides) and the forward's q, k, v, o, lse, Er, keep the gradients with respect to
  * the tensors as passed: dq (q's strides; includes q_scale), dk, dv (k's / v's strides; with kv_group > 1 the sum over the group's
  * query heads, in head order), dEr (er_len, hd) contiguous, optional.  With D_i = sum_d dO_id O_id:
@@ -718,10 +724,10 @@ int32_t amt_attn_train_fwd(const float* q, const float* k, const float* v, float
  * relative position table.  The launcher's own rule, evaluated on the host: no device, no stream; a code, not a status. */
 int32_t amt_attn_route(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t has_er);
 int64_t amt_attn_bwd_ws_floats(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t rpr);
-int32_t amt_attn_bwd(const float* dO, const float* q, const float* k, const float* v, const float* o, const float* lse,
-                     const float* Er, int32_t er_len, const uint8_t* keep, float keep_scale, float* dq, float* dk, float* dv,
-                     float* dEr, const int64_t* strides, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd,
-                     int32_t causal, int32_t kv_group, float q_scale, float* ws, void* stream);
+amt_status amt_attn_bwd(const float* dO, const float* q, const float* k, const float* v, const float* o, const float* lse,
+                        const float* Er, int32_t er_len, const uint8_t* keep, float keep_scale, float* dq, float* dk, float* dv,
+                        float* dEr, const int64_t* strides, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd,
+                        int32_t causal, int32_t kv_group, float q_scale, float* ws, void* stream);
 
 /* Backward of y = LayerNorm(x (+ resid)) * w + b (amt_layernorm_fwd; torch.nn.LayerNorm).  dy, x, resid (null = none), dx: (rows, dim);
  * w, dw, db: (dim).  x / resid are the forward's inputs: the row statistics are formed again from them as the forward formed them.
@@ -734,8 +740,8 @@ int32_t amt_attn_bwd(const float* dO, const float* q, const float* k, const floa
  * workgroup order: the order of every addition is a function of (rows, dim) alone and no floating-point atomic is used, so the same
  * inputs give the same bits. */
 #define AMT_LAYERNORM_BWD_WS_FLOATS(dim) (4 + 256 * (dim))
-int32_t amt_layernorm_bwd(const float* dy, const float* x, const float* resid, const float* w, float* dx, float* dw, float* db,
-                          float* ws, int32_t rows, int32_t dim, float eps, void* stream);
+amt_status amt_layernorm_bwd(const float* dy, const float* x, const float* resid, const float* w, float* dx, float* dw, float* db,
+                             float* ws, int32_t rows, int32_t dim, float eps, void* stream);
 
 /* What the training of the V1 / V2 chord models adds to the above (csrc/family_train.hip; amt_rmsnorm_bwd: csrc/norm_bwd.hip).  All
  * three are fp32 and stateless, use no floating-point atomic and fix the order of every addition by the shapes alone: the same inputs give the same bits.
@@ -743,8 +749,8 @@ int32_t amt_layernorm_bwd(const float* dy, const float* x, const float* resid, c
  * amt_rope_bwd: the adjoint of amt_rope_fwd under the same index rule and the same shape checks (both cache layouts: the broadcast
  * slab 2 cache_half == hd, and the [seq][cache_half][2] cache read as [n0][seq][hd/2][2]); each pair of dy is rotated by the transpose
  * of the forward's rotation: dx0 = dy0 cos + dy1 sin, dx1 = dy1 cos - dy0 sin.  dx may be dy.  dy / dx 8-byte aligned. */
-int32_t amt_rope_bwd(const float* dy, const float* cache, float* dx, int32_t n0, int32_t seq, int32_t n2, int32_t hd,
-                     int32_t cache_half, void* stream);
+amt_status amt_rope_bwd(const float* dy, const float* cache, float* dx, int32_t n0, int32_t seq, int32_t n2, int32_t hd,
+                        int32_t cache_half, void* stream);
 /* Backward of y = RMSNorm(x (+ resid)) * w (amt_rmsnorm_resid_fwd) from the forward's own inputs.  dy, x, resid (null = none), dx:
  * (rows, dim); w, dw: (dim).  With u = x (+ resid), r = rsqrt(mean(u^2) + eps), xh = u r, g = dy w:
  *   dx = r (g - xh mean(g xh))      (the gradient of x and of resid alike),   dw = sum over rows of dy xh
@@ -755,8 +761,8 @@ int32_t amt_rope_bwd(const float* dy, const float* cache, float* dx, int32_t n0,
  * without the mean and db, and its two-stage sum. */
 #define AMT_RMSNORM_BWD_WS_FLOATS(dim) (4 + 128 * (dim))
 int32_t amt_rmsnorm_bwd_blocks(int32_t rows);
-int32_t amt_rmsnorm_bwd(const float* dy, const float* x, const float* resid, const float* w, float* dx, float* dw, float* ws,
-                        int32_t rows, int32_t dim, float eps, void* stream);
+amt_status amt_rmsnorm_bwd(const float* dy, const float* x, const float* resid, const float* w, float* dx, float* dw, float* ws,
+                           int32_t rows, int32_t dim, float eps, void* stream);
 /* Training of one GLUExpert on n rows (amt_glu_expert_fwd's layer): y = W2((W1 x + b1) * silu(Wg x + bg) * mask_h) + b2, or with
  * w1 == NULL the Linear -> SiLU -> Dropout -> Linear expert y = W2(silu(Wg x + bg) * mask_h) + b2 (amt_moe_train_fwd's convention).
  * x, out (n, d); w1 / wg (dff, d), b1 / bg (dff), w2 (d, dff), b2 (d) at the padded width dff (a multiple of 32, as d); mask_h
@@ -767,13 +773,13 @@ int32_t amt_rmsnorm_bwd(const float* dy, const float* x, const float* resid, con
  * padding's rows / columns come out zero).  w1t / wgt (d, dff) and w2t (dff, d) are the TRANSPOSED weights, prepared by the caller.
  * ws: amt_glu_bwd_ws_floats(n, d, dff) floats, 16-byte aligned. */
 int64_t amt_glu_train_scratch_floats(int32_t n, int32_t dff, int32_t glu);
-int32_t amt_glu_train_fwd(const float* x, const float* w1, const float* b1, const float* wg, const float* bg, const float* w2,
-                          const float* b2, const float* mask_h, float* out, float* saved, int32_t n, int32_t d, int32_t dff,
-                          int32_t dff_raw, void* stream);
+amt_status amt_glu_train_fwd(const float* x, const float* w1, const float* b1, const float* wg, const float* bg, const float* w2,
+                             const float* b2, const float* mask_h, float* out, float* saved, int32_t n, int32_t d, int32_t dff,
+                             int32_t dff_raw, void* stream);
 int64_t amt_glu_bwd_ws_floats(int32_t n, int32_t d, int32_t dff);
-int32_t amt_glu_bwd(const float* dout, const float* x, const float* saved, const float* w1t, const float* wgt, const float* w2t,
-                    const float* mask_h, float* dx, float* dw1, float* db1, float* dwg, float* dbg, float* dw2, float* db2,
-                    float* ws, int32_t n, int32_t d, int32_t dff, int32_t dff_raw, int32_t glu, void* stream);
+amt_status amt_glu_bwd(const float* dout, const float* x, const float* saved, const float* w1t, const float* wgt, const float* w2t,
+                       const float* mask_h, float* dx, float* dw1, float* db1, float* dwg, float* dbg, float* dw2, float* db2,
+                       float* ws, int32_t n, int32_t d, int32_t dff, int32_t dff_raw, int32_t glu, void* stream);
 
 /* Training of the differential-attention tail of the V3 chord models (csrc/diff_subln_train.hip).  Both are fp32 and stateless, use no
  * floating-point atomic and fix the order of every addition by the shapes alone: the same inputs give the same bits.
@@ -793,12 +799,12 @@ int32_t amt_glu_bwd(const float* dout, const float* x, const float* saved, const
  * 256 / hd))), evaluated on the host: a count, not a status; negative for rows <= 0 or another hd), workgroup b taking rows
  * [b per, (b + 1) per) with per = ceil(rows / blocks), wave w of it the groups of 256 / hd rows w, w + 4, ... of that range. */
 #define AMT_DIFF_SUBLN_BWD_WS_FLOATS(hd) (4 + 128 * ((hd) + 4))
-int32_t amt_diff_subln_train_fwd(const float* o1, const float* o2, const float* w, const float* lambda_dev, float* y, int32_t rows,
-                                 int32_t hd, float out_scale, float eps, void* stream);
+amt_status amt_diff_subln_train_fwd(const float* o1, const float* o2, const float* w, const float* lambda_dev, float* y, int32_t rows,
+                                    int32_t hd, float out_scale, float eps, void* stream);
 int32_t amt_diff_subln_bwd_blocks(int32_t rows, int32_t hd);
-int32_t amt_diff_subln_bwd(const float* dy, const float* o1, const float* o2, const float* w, const float* lambda_dev, float* d_o1,
-                           float* d_o2, float* dw, float* dlambda, float* ws, int32_t rows, int32_t hd, float out_scale, float eps,
-                           void* stream);
+amt_status amt_diff_subln_bwd(const float* dy, const float* o1, const float* o2, const float* w, const float* lambda_dev, float* d_o1,
+                              float* d_o2, float* dw, float* dlambda, float* ws, int32_t rows, int32_t hd, float out_scale, float eps,
+                              void* stream);
 
 /* Training loss of the chord model (reference utilities/run_model_vevo.py:101-119) and its gradient, one launch:
  *   total = lambda CrossEntropyLoss(ignore_index=CHORD_PAD, label_smoothing=smoothing)(y, tgt)
@@ -818,8 +824,8 @@ int32_t amt_diff_subln_bwd(const float* dy, const float* o1, const float* o2, co
  * inside a row, the rows of a workgroup added in row order, the workgroups of a clip in order, the clips in order; no floating-point
  * atomic, so the same inputs give the same bits.  159 B L <= 2^24. */
 int64_t amt_chord_loss_ws_floats(int32_t B, int32_t L);
-int32_t amt_chord_loss_fwd_bwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, int32_t B, int32_t L,
-                               float lambda, float smoothing, float* loss, float* clip_out, float* dlogits, float* ws, void* stream);
+amt_status amt_chord_loss_fwd_bwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, int32_t B, int32_t L,
+                                  float lambda, float smoothing, float* loss, float* clip_out, float* dlogits, float* ws, void* stream);
 
 /* The same loss with the reference's -auxiliary_loss (train.py:221-229, model/loss.py:85-141) and free weights:
  *   chord = (CE + A_3 + A_5) / count,  total = w_chord chord + w_emotion emotion
@@ -841,9 +847,9 @@ int32_t amt_chord_loss_fwd_bwd(const float* logits, int32_t ld, const int64_t* t
 #define AMT_CHORD_AUX_ROWS 0
 #define AMT_CHORD_AUX_VIEW 1
 int64_t amt_chord_loss_aux_ws_floats(int32_t B, int32_t L);
-int32_t amt_chord_loss_aux_fwd_bwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, int32_t B, int32_t L,
-                                   float w_chord, float w_emotion, float smoothing, int32_t layout, float* loss, float* clip_out,
-                                   float* dlogits, float* ws, void* stream);
+amt_status amt_chord_loss_aux_fwd_bwd(const float* logits, int32_t ld, const int64_t* tgt, const int32_t* emo_class, int32_t B, int32_t L,
+                                      float w_chord, float w_emotion, float smoothing, int32_t layout, float* loss, float* clip_out,
+                                      float* dlogits, float* ws, void* stream);
 
 /* One fused multi-tensor optimiser step (csrc/optim.hip): torch's RAdam (coupled or decoupled weight decay) and the reference's
  * RAdanW (model/RAdanW.py) in its foreach variant (:319-445, what the reference runs on a GPU) and its single-tensor variant
@@ -880,7 +886,7 @@ typedef struct amt_optim_args {
     float beta3, one_minus_beta3, neg_one_minus_beta3, beta4, one_minus_beta4;
     int32_t rectified, npg_from_grad;
 } amt_optim_args;
-int32_t amt_optim_step(const amt_optim_args* a, void* stream);
+amt_status amt_optim_step(const amt_optim_args* a, void* stream);
 /* The launcher's own constants, evaluated on the host (no device, no stream; a value, not a status; negative for an unknown query):
  * tensors per launch, elements per chunk (a block's unit of work: tensors are cut into chunks, the chunks dealt to the blocks
  * round-robin), the cap on the grid, and the block size. */

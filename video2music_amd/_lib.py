@@ -1,4 +1,5 @@
-"""ctypes binding of ``libamt_hip.so`` (C ABI declared in ``include/amt_hip.h``).
+"""ctypes binding of ``libamt_hip.so``.  The C ABI is declared once, in ``include/amt_hip.h``: prototypes, argument structs and
+constants are read from that file at import (``parse_header``), so a new entry point needs no edit here.
 
 There is deliberately no CPU fallback: if the shared library is missing, or a call returns a
 non-zero status, this module raises.  Build the library with ``python -c "import __graft_entry__ as
@@ -6,6 +7,7 @@ g; g.build()"`` or ``video2music_amd/csrc/build.sh``.
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # AMT_LIB: an alternate build of the same library (tools/ab_build.sh: A/B kernel experiments on one box); default = the in-tree build
@@ -16,172 +18,91 @@ class AmtError(RuntimeError):
     pass
 
 
-class AmtConfig(C.Structure):
-    _fields_ = [("n_layers", C.c_int32), ("num_heads", C.c_int32), ("d_model", C.c_int32),
-                ("dim_feedforward", C.c_int32), ("max_sequence_video", C.c_int32),
-                ("max_sequence_chord", C.c_int32), ("total_vf_dim", C.c_int32), ("max_batch", C.c_int32)]
+# ---- the header is the one declaration of the ABI: prototypes, argument structs and constants are read from it ---------------------
+_SCALARS = {"int32_t": C.c_int32, "amt_status": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
 
 
-_P = C.c_void_p
-_I = C.c_int32
-_F = C.c_float
+def _ctype(ctype, structs, where):
+    """ctypes type of a C type of the header.  `structs`: the argument structs a pointer may name ({} inside a struct: every pointer
+    field is a c_void_p).  Any other pointer is a c_void_p on purpose: one `const int64_t*` takes a device tensor (`ptr(t)`) in one
+    call and a host array (`(c_int64 * n)(...)`, `byref(...)`) in another, and c_void_p accepts all of these."""
+    t = re.sub(r"\s*\*\s*", "*", " ".join(ctype.split()))
+    if t == "const char*":
+        return C.c_char_p
+    if t.endswith("*"):
+        pointee = t.removeprefix("const ")[:-1]
+        return C.POINTER(structs[pointee]) if pointee in structs else C.c_void_p
+    if t.removeprefix("const ") not in _SCALARS:
+        raise AmtError(f"{where}: no ctypes mapping for the type {t!r} (known: {', '.join(_SCALARS)}, const char*, pointers)")
+    return _SCALARS[t.removeprefix("const ")]
 
 
-class DecodeGemmArgs(C.Structure):           # amt_decode_gemm_args
-    _fields_ = [("x", _P), ("ldx", _I), ("x2", _P), ("ldx2", _I), ("K1", _I), ("K", _I),
-                ("w_low", _P), ("bias_low", _P), ("resid", _P), ("relu", _I), ("w_high", _P), ("bias_high", _P),
-                ("n_low", _I), ("n_high", _I), ("pro", _I), ("fold_g", _P), ("fold_c", _P), ("ln_w", _P), ("ln_b", _P),
-                ("y_low", _P), ("y_high", _P), ("scratch_low", _P), ("scratch_high", _P), ("B", _I), ("eps", _F)]
+def _named(decl, where):
+    """(type, name) of a `type name` parameter or field; anything else is refused."""
+    found = re.fullmatch(r"(.*[\s*])(\w+)", decl.strip(), re.S)
+    if not found or not found.group(1).strip() or re.search(r"[\[(]|\.\.\.", decl):
+        raise AmtError(f"{where}: cannot bind {decl.strip()!r} (an array, function pointer, variadic or unnamed declaration?)")
+    return found.groups()
 
 
-class V2StepArgs(C.Structure):               # amt_v2_step_args
-    _fields_ = [("tab", _P), ("n_layers", _I), ("H", _I), ("E", _I), ("dff", _I), ("n_exp", _I), ("S", _I), ("max_seq", _I), ("B", _I),
-                ("keys_dev", _P), ("state_dev", _P), ("logits_out", _P), ("ws", _P)]
+def parse_header(text):
+    """The ABI `text` (include/amt_hip.h) declares: ({function: (restype, argtypes, returns a status)}, {struct: ctypes.Structure
+    class}, {AMT_X: int} for the object-like integer macros).  It reads `type name(args);` and `typedef struct name { ... } name;` and
+    raises AmtError, naming the declaration, on anything it cannot map: a binding with a missing type would hand a kernel garbage."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(AMT_\w+)[ \t]+(\S+)[ \t]*$", text, re.M):
+        try:
+            consts[name] = int(value, 0)
+        except ValueError:
+            pass                                    # not an integer literal: not a constant of the bindings
+    text = re.sub(r'^[ \t]*#[^\n]*$|extern\s+"C"\s*\{', " ", text, flags=re.M)
+    structs = {}
+
+    def struct(found):
+        name, fields = found.group(1), []
+        for stmt in filter(None, map(str.strip, found.group(2).split(";"))):
+            first, *more = stmt.split(",")          # `int32_t mode, n_tensors;` declares several names
+            ctype, field = _named(first, f"struct {name}")
+            names = [field] + [m.strip() for m in more]
+            if not all(re.fullmatch(r"\w+", n) for n in names):
+                raise AmtError(f"struct {name}: cannot bind {stmt!r}")
+            fields += [(n, _ctype(ctype, {}, f"struct {name}")) for n in names]
+        structs[name] = type(name, (C.Structure,), {"_fields_": fields})
+        return " "
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", struct, text, flags=re.S)
+    protos = {}
+    for stmt in map(str.strip, text.split(";")):
+        if stmt in ("", "}") or re.fullmatch(r"typedef\s+struct\s+(\w+)\s+\1", stmt):      # "}" closes extern "C"; an opaque handle type
+            continue
+        alias = re.fullmatch(r"typedef\s+(\w+)\s+(\w+)", stmt)
+        found = re.fullmatch(r"(.*?)\b(amt_\w+)\s*\((.*)\)", stmt, re.S)
+        if alias:                                   # typedef int32_t amt_status: must agree with _SCALARS
+            if alias.group(2) not in _SCALARS or _SCALARS[alias.group(2)] is not _SCALARS.get(alias.group(1)):
+                raise AmtError(f"{stmt!r}: a typedef the bindings' type table does not know")
+        elif found:
+            ret, name, args = found.groups()
+            args = [] if args.strip() == "void" else [_ctype(_named(a, name)[0], structs, name) for a in args.split(",")]
+            protos[name] = (_ctype(ret, structs, name), args, ret.strip() == "amt_status")
+        else:
+            raise AmtError(f"cannot read the declaration {' '.join(stmt.split())[:120]!r}")
+    unread = set(re.findall(r"\b(amt_\w+)\s*\(", text)) - set(protos)
+    if unread:
+        raise AmtError(f"declared but not read as prototypes: {sorted(unread)}")
+    return protos, structs, consts
 
 
-class V2DecideArgs(C.Structure):             # amt_v2_decide_args
-    _fields_ = [("tokens", _P), ("roots", _P), ("attrs", _P), ("T", _I), ("n_primer", _I), ("beam", _I), ("max_conseq_N", _I),
-                ("max_conseq_chord", _I), ("temperature", _F), ("uniforms", _P), ("chord_embed", _I)]
-
-OPTIM_MAX_TENSORS = 48                       # AMT_OPTIM_MAX_TENSORS
-
-
-class OptimArgs(C.Structure):                # amt_optim_args
-    _fields_ = ([("mode", _I), ("n_tensors", _I)] + [(k, _P) for k in ("p", "g", "m", "v", "ed", "eds", "npg", "numel")]
-                + [(k, _F) for k in ("lr", "decay", "weight_decay", "one_minus_beta1", "beta2", "one_minus_beta2", "eps", "rect_step_size",
-                                     "unrect_step_size", "bias_correction1", "bias_correction2_sqrt", "rect", "beta3", "one_minus_beta3",
-                                     "neg_one_minus_beta3", "beta4", "one_minus_beta4")]
-                + [("rectified", _I), ("npg_from_grad", _I)])
-
-# name -> argtypes (restype is int32 unless listed in _RESTYPES); mirrors include/amt_hip.h
-SIGNATURES = {
-    "amt_last_error": [],
-    "amt_abi_version": [],
-    "amt_create": [C.POINTER(AmtConfig), C.POINTER(_P)],
-    "amt_destroy": [_P],
-    "amt_load_weight": [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64)],
-    "amt_finalize": [_P],
-    "amt_encode": [_P, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P],
-    "amt_encode_resid": [_P, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P],
-    "amt_set_option": [_P, C.c_char_p, _I],
-    "amt_prefill": [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
-    "amt_generate_begin": [_P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P],
-    "amt_generate_set_uniforms": [_P, _P, _P],
-    "amt_generate_run": [_P, _I, _P, _P],
-    "amt_generate_profile": [_P, _I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P],
-    "amt_generate_step_probs": [_P, _P, _P],
-    "amt_generate_commit": [_P, _P, _P],
-    "amt_generate_set_branch": [_P, _I],
-    "amt_generate_end": [_P, _P, _P],
-    "amt_kv_cache_io": [_P, _P, C.c_int64, _I, C.POINTER(C.c_int64), _P],
-    "amt_generate": [_P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P],
-    "amt_v2_decide_batch": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _I, _P],
-    "amt_v2_step_decide_batch": [C.POINTER(V2StepArgs), C.POINTER(V2DecideArgs), _I, _P],
-    "amt_decode_step_bytes": [_P, _I, _I, _I],
-    "amt_linear_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "amt_layernorm_fwd": [_P, _P, _P, _P, _P, _I, _I, _F, _P],
-    "amt_rmsnorm_fwd": [_P, _P, _P, _I, _I, _F, _P],
-    "amt_rmsnorm_resid_fwd": [_P, _P, _P, _P, _I, _I, _F, _P],
-    "amt_diff_subln_fwd": [_P, _P, _P, _P, _I, _I, _F, _F, _F, _P],
-    "amt_add_fwd": [_P, _P, _P, C.c_int64, _P],
-    "amt_row_scale_add_fwd": [_P, _P, _P, _P, _I, _I, _P],
-    "amt_rope_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "amt_rpr_attn_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "amt_rpr_attn_nomask_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "amt_cross_attn_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "amt_attn_fwd": [_P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _I, _F, _P],
-    "amt_concat_features_fwd": [_P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P],
-    "amt_chord_embed_fwd": [_P] * 9 + [_I, _I, _I, _P],
-    "amt_attn_decode_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "amt_decode_linear_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "amt_attn_decode_fold_fwd": [_P, _I] + [_P] * 10 + [_I, _I, _I, _I, _P, _I, _I, _I, _F, _F, _P],
-    "amt_decode_gemm_ex_fwd": [C.POINTER(DecodeGemmArgs), _P],
-    "amt_decode_gemm_ex_lean": [C.POINTER(DecodeGemmArgs)],
-    "amt_gqa_fwd": [_P] * 15 + [_I] * 7 + [_F, _P],
-    "amt_gqa_rope_fwd": [_P] * 15 + [_I] * 7 + [_F, _P, _I, _I, _P],
-    "amt_moe_scratch_floats": [_I, _I, _I, _I],
-    "amt_moe_fwd": [_P] * 19 + [_I] * 4 + [_P],
-    "amt_moe_topk_scratch_floats": [_I, _I, _I, _I, _I],
-    "amt_moe_topk_fwd": [_P] * 19 + [_I] * 5 + [_P],
-    "amt_moe_train_scratch_floats": [_I, _I, _I, _I, _I, _I],
-    "amt_moe_train_fwd": [_P] * 22 + [_I] * 6 + [_P],
-    "amt_moe_bwd_ws_floats": [_I, _I, _I, _I, _I],
-    "amt_moe_bwd": [_P] * 29 + [_I] * 8 + [_F, _P],
-    "amt_moe_route_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "amt_glu_expert_fwd": [_P] * 9 + [_I, _I, _I, _P],
-    "amt_moe_combine_fwd": [_P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
-    "amt_moe_ep_dispatch_plan_fwd": [_P, _I, _I, _P, _P, _P, _P, _P],
-    "amt_gather_rows_fwd": [_P, _P, _P, _I, _I, _P],
-    "amt_moe_ep_expert_scratch_floats": [_I, _I, _I, _I],
-    "amt_moe_ep_expert_fwd": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
-    "amt_dwconv1d_silu_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "amt_selective_scan_fwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "amt_concat2_fwd": [_P, _I, _P, _I, _P, _I, _I, _P],
-    "amt_linear_ex_fwd": [_P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
-    "amt_layernorm_post_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
-    "amt_v2_step_ws_floats": [_I, _I, _I],
-    "amt_pack_weight_fwd": [_P, _P, _I, _I, _P],
-    "amt_v2_step": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P],
-    "amt_rnn_seq_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "amt_v2_step_batch_ws_floats": [_I, _I, _I, _I],
-    "amt_v2_last_step_launches": [],
-    "amt_v2_step_batch": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "amt_chord_metrics_fwd": [_P, _I, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P],
-    "amt_reg_metrics_fwd": [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
-    "amt_rnn_seq_train_fwd": [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "amt_rnn_seq_bwd": [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "amt_rnn_wide_ws_floats": [_I, _I, _I, _I],
-    "amt_rnn_wide_seq_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "amt_rnn_wide_seq_train_fwd": [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "amt_rnn_wide_seq_bwd": [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "amt_reg_loss_fwd_bwd": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
-    "amt_attn_train_fwd": [_P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _I, _F, _P, _I, _P, _F, _P, _P],
-    "amt_attn_bwd_ws_floats": [_I, _I, _I, _I, _I, _I],
-    "amt_attn_bwd": [_P] * 7 + [_I, _P, _F, _P, _P, _P, _P, C.POINTER(C.c_int64), _I, _I, _I, _I, _I, _I, _I, _F, _P, _P],
-    "amt_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
-    "amt_chord_loss_ws_floats": [_I, _I],
-    "amt_chord_loss_fwd_bwd": [_P, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P],
-    "amt_selective_scan_train_fwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
-    "amt_selective_scan_bwd_ws_floats": [_I, _I, _I, _I],
-    "amt_selective_scan_bwd": [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P,
-                               _P, _I, _I, _I, _I, _I, _I, _P],
-    "amt_dwconv1d_silu_bwd_ws_floats": [_I, _I, _I, _I],
-    "amt_dwconv1d_silu_bwd": [_P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "amt_gemm_route": [_I, _I, _I, _I, _I],
-    "amt_attn_route": [_I, _I, _I, _I, _I, _I],
-    "amt_moe_wgrad_splits": [_I, _I, _I, _I, _I, _I],
-    "amt_rope_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "amt_rmsnorm_bwd_blocks": [_I],
-    "amt_rmsnorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
-    "amt_glu_train_scratch_floats": [_I, _I, _I],
-    "amt_glu_train_fwd": [_P] * 10 + [_I, _I, _I, _I, _P],
-    "amt_glu_bwd_ws_floats": [_I, _I, _I],
-    "amt_glu_bwd": [_P] * 15 + [_I, _I, _I, _I, _I, _P],
-    "amt_diff_subln_train_fwd": [_P, _P, _P, _P, _P, _I, _I, _F, _F, _P],
-    "amt_diff_subln_bwd_blocks": [_I, _I],
-    "amt_diff_subln_bwd": [_P] * 10 + [_I, _I, _F, _F, _P],
-    "amt_moe_train_fwd_balanced": [_P] * 22 + [_I] * 6 + [_P, _P, _F, _P],
-    "amt_selective_scan_wide_ckpt_steps": [_I],
-    "amt_selective_scan_wide_train_fwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
-    "amt_selective_scan_wide_bwd_ws_floats": [_I, _I, _I, _I],
-    "amt_selective_scan_wide_bwd": [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P,
-                                    _P, _I, _I, _I, _I, _I, _I, _P],
-    "amt_silu_bwd": [_P, _P, _P, C.c_int64, _P],
-    "amt_chord_loss_aux_ws_floats": [_I, _I],
-    "amt_chord_loss_aux_fwd_bwd": [_P, _I, _P, _P, _I, _I, _F, _F, _F, _I, _P, _P, _P, _P, _P],
-    "amt_optim_step": [C.POINTER(OptimArgs), _P],
-    "amt_optim_plan": [_I],
-}
-_RESTYPES = {"amt_last_error": C.c_char_p, "amt_decode_step_bytes": C.c_int64, "amt_moe_scratch_floats": C.c_int64, "amt_moe_topk_scratch_floats": C.c_int64,
-             "amt_v2_step_ws_floats": C.c_int64, "amt_v2_step_batch_ws_floats": C.c_int64, "amt_moe_ep_expert_scratch_floats": C.c_int64,
-             "amt_chord_loss_ws_floats": C.c_int64, "amt_attn_bwd_ws_floats": C.c_int64, "amt_selective_scan_bwd_ws_floats": C.c_int64,
-             "amt_dwconv1d_silu_bwd_ws_floats": C.c_int64, "amt_moe_train_scratch_floats": C.c_int64, "amt_moe_bwd_ws_floats": C.c_int64,
-             "amt_glu_train_scratch_floats": C.c_int64, "amt_glu_bwd_ws_floats": C.c_int64,
-             "amt_selective_scan_wide_bwd_ws_floats": C.c_int64, "amt_chord_loss_aux_ws_floats": C.c_int64, "amt_rnn_wide_ws_floats": C.c_int64}
-_NO_STATUS = set(_RESTYPES) | {"amt_abi_version", "amt_v2_last_step_launches", "amt_gemm_route", "amt_attn_route", "amt_decode_gemm_ex_lean", "amt_moe_wgrad_splits",
-                                  "amt_rmsnorm_bwd_blocks", "amt_diff_subln_bwd_blocks", "amt_selective_scan_wide_ckpt_steps", "amt_optim_plan"}
-
-ABI_VERSION = 14        # AMT_ABI_VERSION of include/amt_hip.h these prototypes were written against
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "amt_hip.h")
+if not os.path.exists(HEADER_PATH):
+    raise AmtError(f"{HEADER_PATH} is missing: the bindings are read from the C header")
+with open(HEADER_PATH) as _f:
+    _PROTOS, _STRUCTS, CONST = parse_header(_f.read())
+SIGNATURES = {name: argtypes for name, (_, argtypes, _) in _PROTOS.items()}       # name -> argtypes
+_STATUS = frozenset(name for name, proto in _PROTOS.items() if proto[2])           # declared amt_status: call() raises on non-zero
+AmtConfig, DecodeGemmArgs, V2StepArgs, V2DecideArgs, OptimArgs = (
+    _STRUCTS[k] for k in ("amt_config", "amt_decode_gemm_args", "amt_v2_step_args", "amt_v2_decide_args", "amt_optim_args"))
+ABI_VERSION = CONST["AMT_ABI_VERSION"]              # load() refuses a library that answers another
+OPTIM_MAX_TENSORS = CONST["AMT_OPTIM_MAX_TENSORS"]
 
 _lib = None
 
@@ -206,16 +127,17 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, C.c_int32)
+        fn.restype = _PROTOS[name][0]
     _lib = lib
     return lib
 
 
 def call(name, *args):
-    """Calls an entry point and raises AmtError with the library's message on a non-zero status."""
+    """Calls an entry point and raises AmtError with the library's message on a non-zero status (a return the header declares as
+    `amt_status`; any other return is a value and is handed back as it is)."""
     lib = load()
     rc = getattr(lib, name)(*args)
-    if name not in _NO_STATUS and rc != 0:
+    if rc != 0 and name in _STATUS:
         msg = lib.amt_last_error()
         raise AmtError(f"{name} failed (status {rc}): {msg.decode() if msg else '?'}")
     return rc

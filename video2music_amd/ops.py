@@ -288,7 +288,7 @@ def rnn_wide_seq_bwd(dy, dy_col, reserve, y, y_col, w_hh, dxproj, dhn, B, L, d, 
     return dxproj, dhn
 
 
-REG_LOSS_WS_FLOATS = 516       # AMT_REG_LOSS_WS_FLOATS of include/amt_hip.h
+REG_LOSS_WS_FLOATS = _lib.CONST["AMT_REG_LOSS_WS_FLOATS"]
 
 
 def reg_loss(ln_nd, inst, note_density, loudness, instrument):
@@ -360,7 +360,7 @@ def chord_loss(logits, tgt, emo_class, lam, smoothing, backward=True):
 
 CHORD_AUX_LOSS_FIELDS = ("total", "chord", "emotion", "ce", "aux3", "aux5", "count")
 CHORD_AUX_CLIP_FIELDS = CHORD_LOSS_CLIP_FIELDS + ("a3_sum", "a5_sum")
-CHORD_AUX_LAYOUTS = {"rows": 0, "view": 1}              # AMT_CHORD_AUX_ROWS / AMT_CHORD_AUX_VIEW
+CHORD_AUX_LAYOUTS = {k: _lib.CONST["AMT_CHORD_AUX_" + k.upper()] for k in ("rows", "view")}
 CHORD_AUX_TERMS = ((3, 3.0), (5, 5.0))                  # (k, weight) of the reference's two TopKAuxiliaryLoss terms (train.py:227-228)
 
 
@@ -651,7 +651,7 @@ def glu_bwd(dout, x, saved, tensors_t, mask_h, dff_raw):
     return dx, (dw1, db1, dwg, dbg, dw2, db2)
 
 
-OPTIM_MODES = {"radam": 0, "radamw": 1, "radanw_foreach": 2, "radanw_single": 3}      # AMT_OPTIM_* of include/amt_hip.h
+OPTIM_MODES = {k: _lib.CONST["AMT_OPTIM_" + k.upper()] for k in ("radam", "radamw", "radanw_foreach", "radanw_single")}
 OPTIM_ADAN = ("radanw_foreach", "radanw_single")
 OPTIM_STREAMS = ("p", "g", "m", "v", "ed", "eds", "npg")
 # fp32 tensors a step reads / writes per element, the figure behind the bytes-per-second of tools/bench_optim.py
@@ -660,7 +660,8 @@ OPTIM_TENSORS_MOVED = {"radam": (4, 3), "radamw": (4, 3), "radanw_foreach": (7, 
 
 def optim_plan():
     """amt_optim_plan: the optimiser launcher's own constants (needs no GPU): {max_tensors, chunk, max_blocks, threads}."""
-    return {k: _lib.call("amt_optim_plan", i) for i, k in enumerate(("max_tensors", "chunk", "max_blocks", "threads"))}
+    return {k: _lib.call("amt_optim_plan", _lib.CONST["AMT_OPTIM_PLAN_" + k.upper()])
+            for k in ("max_tensors", "chunk", "max_blocks", "threads")}
 
 
 def optim_check(t, what, shape=None):

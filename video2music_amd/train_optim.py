@@ -7,7 +7,7 @@
                   (``model/RAdanW.py``) in the foreach variant it runs on a GPU
 
 The last three run on the fused multi-tensor kernel ``amt_optim_step`` (``video2music_amd/optim.py``, ``csrc/optim.hip``): one launch
-per 48 tensors of a step, no host synchronisation.  ``Lion`` is refused: ``lion_pytorch`` is a package the reference does not vendor,
+per ``_lib.OPTIM_MAX_TENSORS`` tensors of a step, no host synchronisation.  ``Lion`` is refused: ``lion_pytorch`` is a package the reference does not vendor,
 and it is not installed.  Everything ``train_losses`` refuses stays refused; ``train``, ``train_families``, ``train_v3`` and
 ``train_losses`` still take Adam / AdamW alone.
 
