@@ -344,6 +344,84 @@ def chord_refs(treatment, smoothing):
     return tuple(chord_split(torch_cpu(y, tgt, emo, smoothing, dt)) for dt in (torch.float64, torch.float32))
 
 
+# ---- the auxiliary chord loss (csrc/chord_aux_loss.hip): a second softmax per row, five selected maxima, two hinges, `count` ----
+AUX_W = (0.4, 0.6)              # the weighting of tests/test_chord_aux_loss_gpu.py
+# the treatments above at helpers_chord_aux.REGIME_SHAPE and three recipes of the auxiliary terms' own.  ties_inside: in every auxiliary
+# row the two largest logits are equal and so are the 4th and 5th (the top-3 and top-5 means do not depend on the order among equals;
+# the 3rd / 4th and 5th / 6th gaps are `make_case`'s or wider).  count_flip_guard2 / 1: `regime_case(2)` / `(1)` with + 1000 on every
+# logit -- an inactive hinge must stay exactly inactive, or `count` and with it every chord gradient changes by a factor
+AUX_RECIPES = LOGIT_TREATMENTS + ("ties_inside", "count_flip_guard2", "count_flip_guard1")
+AUX_LOSSES = ("total", "chord", "emotion", "ce", "aux3", "aux5")
+AUX_CLIP = ("n_valid", "ce", "bce", "L", "a3", "a5")
+
+
+@functools.lru_cache(maxsize=None)
+def chord_aux_case(recipe, layout):
+    """-> y (B, L, 159) fp32, tgt, emo at REGIME_SHAPE.  The recipes of the auxiliary terms' own are built on the auxiliary rows and,
+    for "view", carried to y by `unview`; a treatment's y is the same for both layouts."""
+    from tests import helpers_chord_aux as HA
+    B, L = HA.REGIME_SHAPE
+    if recipe in LOGIT_TREATMENTS:
+        return chord_logits(recipe, B, L)[:3]
+    if recipe == "ties_inside":
+        y, tgt, emo = HA.make_case(B, L)
+        z = np.ascontiguousarray(HA.aux_rows(y, layout)).copy()
+        order = np.argsort(-z, axis=-1, kind="stable")
+        for dst, src in ((1, 0), (4, 3)):                   # the 2nd takes the 1st's value, the 5th the 4th's
+            np.put_along_axis(z, order[..., dst:dst + 1], np.take_along_axis(z, order[..., src:src + 1], -1), -1)
+        return np.ascontiguousarray(z if layout == "rows" else HA.unview(z), dtype=np.float32), tgt, emo
+    y, tgt, emo = HA.regime_case({"count_flip_guard2": 2, "count_flip_guard1": 1}[recipe], layout)
+    return y + np.float32(1000.0), tgt, emo
+
+
+def chord_aux_split(res):
+    """The outputs of `helpers_chord_aux.chord_aux` (and of the kernel) as tensors of one scale each."""
+    out = {"loss_" + k: res["loss"][i:i + 1] for i, k in enumerate(AUX_LOSSES)}
+    out["count"] = res["loss"][6:7]
+    out.update({"clip_" + k: res["clip"][:, i] for i, k in enumerate(AUX_CLIP)})
+    out["dlogits"] = res["dlogits"]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def chord_aux_refs(recipe, layout, smoothing):
+    from tests import helpers_chord_aux as HA
+    y, tgt, emo = chord_aux_case(recipe, layout)
+    return tuple(chord_aux_split(HA.chord_aux(y, tgt, emo, smoothing, AUX_W, layout, dt)) for dt in (torch.float64, torch.float32))
+
+
+def chord_aux_n(B, L):
+    """The sums of tests/test_chord_aux_loss_gpu.py's bounds: a 159-term tree inside a row and a sum over the clip's L rows for a
+    per-clip sum (`helpers_eval.loss_bound`); for a loss those carried through the B clips, and 4 for the quotients and the
+    combination; 159 for dlogits."""
+    return lambda k: 159 + L + B + 4 if k.startswith("loss") else 159 + L if k.startswith("clip") else 159
+
+
+def chord_aux_floors(y):
+    """(gap, margin) a case must keep from the two places where the gradient jumps, from the fp32 spacing s at the logits' magnitude
+    (6e-5 at 1000).  The logits are fp32 numbers, so two of them that differ differ by s or more: a top-k border is decided by
+    a comparison of inputs and any gap of 2 s is unambiguous.  z - m is rounded to s / 2, so a probability carries up to s of relative
+    error on top of the 159-term sum's; a hinge 4 (s + 159 U) from its kink cannot change sides.  Never under helpers_chord_aux's own."""
+    from tests import helpers_chord_aux as HA
+    s = float(np.spacing(np.float32(np.abs(y).max())))
+    return max(2 * s, HA.MIN_GAP), max(4 * (s + HA.NC * U), HA.MIN_MARGIN)
+
+
+def aux_hinge_sum_f32(z, t, k, variant="ok"):
+    """sum over the rows of relu(mean(top-k of softmax(z)) - softmax(z)_t) in fp32 numpy as the kernel's header states it: the k
+    largest are chosen on the logits, p = exp(z - m) / se with results below the smallest normal number flushed.  z (rows, 159), t (rows).
+    variant: "no_max" (the softmax without its maximum) | "topk_of_p" (the k largest chosen on the rounded p, lowest index first)."""
+    f = np.float32
+    z = z.astype(f)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        e = np.exp(z if variant == "no_max" else z - z.max(-1, keepdims=True), dtype=f)
+        e = np.where(e < FLT_MIN, f(0), e)
+        p = e / e.sum(-1, keepdims=True, dtype=f)
+        order = np.argsort(-(p if variant == "topk_of_p" else z), axis=-1, kind="stable")[:, :k]
+        top = np.take_along_axis(p, order, -1).sum(-1, dtype=f) / f(k)
+        return np.maximum(top - np.take_along_axis(p, t[:, None], -1)[:, 0], f(0)).sum(dtype=f)
+
+
 # =====================================================================================================================
 # B. selective scan
 # =====================================================================================================================
@@ -351,6 +429,10 @@ SCAN_RECIPES = ("slow_decay", "fast_decay", "threshold", "tiny_delta", "gate_sat
 SCAN_SHAPES = [(2, 33, 24), (1, 70, 40)]
 SOFTPLUS_GRID = (19.0, 19.999, 20.0, 20.001, 21.0, 40.0, 88.0)
 SCAN_CHUNK = 32
+# amt_selective_scan_wide_train_fwd / _bwd (csrc/mamba.hip, csrc/mamba_bwd.hip): the narrowest and the widest state, every recipe, both
+# shapes; the backward recomputes from checkpoints every 32 steps and adds the partial state sums of N / 16 slices in a second launch
+SCAN_WIDE_N = (32, 256)
+SCAN_SLICE = 16
 
 
 @functools.lru_cache(maxsize=None)
@@ -422,7 +504,9 @@ def scan_split(recipe, res):
 
 
 def scan_n(B, L, N):
-    return lambda k: B * L if k.split("[")[0] in ("dA_log", "dD", "d_dt_bias") else L * N
+    """B L for a parameter's gradient, L N for a value at the end of a state chain (tests/test_scan_wide_bwd_gpu.py) -- but never more
+    than CAP / U: at (L, N) = (70, 256) L N U is 1.07e-3, and the case is held to the cap instead of being left out."""
+    return lambda k: B * L if k.split("[")[0] in ("dA_log", "dD", "d_dt_bias") else min(L * N, int(CAP / U))
 
 
 @functools.lru_cache(maxsize=None)
@@ -440,9 +524,11 @@ def softplus_f32(v, variant="ok"):
     return soft if variant != "ok" else np.where(v > 20, v, soft)
 
 
-def scan_state_np(c, B, L, ED, N, dtype, carry="ok", softplus="ok"):
+def scan_state_np(c, B, L, ED, N, dtype, carry="ok", softplus="ok", slices_left_out=0):
     """The un-gated scan output y_t = h_t . C_t + D x_t, forward in time, in numpy at `dtype`, walking in chunks of SCAN_CHUNK steps as
-    the training kernels do.  carry: "ok" | "zero" (a chunk starts from h = 0) | "neighbour" (from the state of channel n + 1)."""
+    the training kernels do.  carry: "ok" | "zero" (a chunk starts from h = 0) | "neighbour" (from the state of channel n + 1).
+    slices_left_out: the state sum of y runs over the first N - 16 slices_left_out states only (the wide kernels sum N / 16 slices of
+    16 states each and add the partials afterwards)."""
     R = c["R"]
     f = lambda t: t.numpy().astype(dtype)
     x, v = f(c["xc"]).reshape(B, L, ED), (f(c["draw"]) + f(c["dt_bias"])).reshape(B, L, ED)
@@ -456,7 +542,7 @@ def scan_state_np(c, B, L, ED, N, dtype, carry="ok", softplus="ok"):
             h = np.zeros_like(h) if carry == "zero" else np.roll(h, -1, axis=2)
         with np.errstate(under="ignore"):
             h = np.exp(delta[:, t, :, None] * A) * h + (delta[:, t, :, None] * Bm[:, t, None, :]) * x[:, t, :, None]
-        y[:, t] = (h * Cm[:, t, None, :]).sum(-1) + f(c["D"]) * x[:, t]
+        y[:, t] = (h * Cm[:, t, None, :])[..., :N - SCAN_SLICE * slices_left_out].sum(-1) + f(c["D"]) * x[:, t]
     return y.reshape(B * L, ED)
 
 
@@ -532,9 +618,15 @@ def rnn_run(G, n_dirs, d, xproj, w_hh, b_hh, dy, dtype):
 
 
 @functools.lru_cache(maxsize=None)
-def rnn_refs(recipe, G, n_dirs):
-    a = rnn_recipe(recipe, G, n_dirs)
-    return rnn_run(G, n_dirs, RNN_SHAPE[2], *a, torch.float64), rnn_run(G, n_dirs, RNN_SHAPE[2], *a, torch.float32)
+def rnn_refs(recipe, G, n_dirs, d=RNN_SHAPE[2]):
+    a = rnn_recipe(recipe, G, n_dirs, RNN_SHAPE[0], d)
+    return rnn_run(G, n_dirs, d, *a, torch.float64), rnn_run(G, n_dirs, d, *a, torch.float32)
+
+
+# csrc/rnn_wide.hip (amt_rnn_wide_seq_fwd / _train_fwd / _bwd: its own sigm and tanhf, W_hh h on fp32 MFMA tiles): every case at
+# d = 160 (five 32-column tiles, an odd count) and the bidirectional ones at 256, the first width the CLI uses.  whh2 puts up to
+# 2 d = 512 behind a gate; its bound at 256 is the largest of the suite and still under the cap (the host test holds it there)
+RNN_WIDE_CASES = [(r, G, n, 160) for r, G, n in RNN_CASES] + [(r, G, n, 256) for r, G, n in RNN_CASES if n == 2]
 
 
 def rnn_n(recipe, G, B=RNN_SHAPE[0], d=RNN_SHAPE[2]):
@@ -679,11 +771,46 @@ def subln_inputs(recipe, rows, hd):
     return a["x"], (-a["resid"] / np.float32(SUBLN_LAM)).astype(np.float32), a["w"]
 
 
-def subln_run(o1, o2, w, dtype, eps=1e-5):
-    t = lambda v: torch.from_numpy(v).to(dtype)
-    u = t(o1) - torch.tensor(SUBLN_LAM, dtype=dtype) * t(o2)
-    y = u * torch.rsqrt((u * u).mean(-1, keepdim=True) + eps) * t(w) * torch.tensor(SUBLN_SCALE, dtype=dtype)
-    return {"y": y.numpy().astype(np.float64)}
+def subln_run(o1, o2, w, dtype, eps=1e-5, grads=False, dy=None, stats_of_o1_alone=False):
+    """grads: torch's autograd of y against `dy` with lambda a leaf -> y, d_o1, d_o2, dw, dlambda (1,).  stats_of_o1_alone: the wrong
+    variant, the mean square taken of o1 instead of o1 - lam o2."""
+    t = lambda v: torch.from_numpy(v).to(dtype).requires_grad_(grads)
+    o1, o2, w = t(o1), t(o2), t(w)
+    lam = torch.tensor([SUBLN_LAM], dtype=dtype, requires_grad=grads)
+    u = o1 - lam * o2
+    s = o1 if stats_of_o1_alone else u
+    y = u * torch.rsqrt((s * s).mean(-1, keepdim=True) + eps) * w * torch.tensor(SUBLN_SCALE, dtype=dtype)
+    out = {"y": y.detach().numpy().astype(np.float64)}
+    if grads:
+        y.backward(torch.from_numpy(dy).to(dtype))
+        out.update({"d_o1": o1.grad, "d_o2": o2.grad, "dw": w.grad, "dlambda": lam.grad})
+        out = {k: np.asarray(v, dtype=np.float64) for k, v in out.items()}
+    return out
+
+
+# amt_diff_subln_train_fwd / amt_diff_subln_bwd (csrc/diff_subln_train.hip): the backward takes head_dim 32 / 64 / 128 only.  `huge12`
+# for `huge`, as `norm_recipes_for("rmsnorm")` and for its reason: at 1e15 torch's own fp32 autograd is 3 % to 11 % off fp64 in d_o1,
+# d_o2 and dlambda (the host test shows it)
+SUBLN_BWD_SHAPES = [(37, 128), (70, 32), (5, 64)]
+SUBLN_BWD_RECIPES = tuple("huge12" if r == "huge" else r for r in SUBLN_RECIPES)
+
+
+@functools.lru_cache(maxsize=None)
+def subln_bwd_inputs(recipe, rows, hd):
+    """`subln_inputs` and the recipe's dy."""
+    return subln_inputs(recipe, rows, hd) + (norm_recipe(recipe, rows, hd, True)["dy"],)
+
+
+@functools.lru_cache(maxsize=None)
+def subln_bwd_refs(recipe, rows, hd):
+    o1, o2, w, dy = subln_bwd_inputs(recipe, rows, hd)
+    return tuple(subln_run(o1, o2, w, dt, grads=True, dy=dy) for dt in (torch.float64, torch.float32))
+
+
+def subln_bwd_n(rows, hd):
+    """The longest sum behind a value: a row's mean square for y, d_o1 and d_o2 (hd, as `test_diff_subln`); for dw and
+    dlambda = -sum du o2 the sum over the rows on top of it (a row's share of dlambda is a sum of hd terms, the rows' shares are added)."""
+    return lambda k: rows + hd if k in ("dw", "dlambda") else hd
 
 
 # ---- the folded LayerNorm: y = (raw - mu g) rstd + c (csrc/fold.hip) ----
@@ -821,6 +948,50 @@ def moe_tensors(o):
 
 def moe_n(n_tok, d, raw, k):
     return lambda name: max(raw, d) + k if name in ("x", "out") else k if name == "weights" else max(n_tok, raw, d)      # tests/test_moe_bwd_gpu.py
+
+
+# amt_moe_train_fwd_balanced (csrc/moe.hip): the V3 selection bias on the saturated router -- the experts are chosen on logits + bias and
+# weighed by the softmax of their raw logits.  The bias is a permuted ramp (helpers_v3_train.BIAS_ORDER's analogue for 8 experts) of
+# the logits' own standard deviation, as `case_bias` of tests/test_v3_train_ops_gpu.py scales it
+MOE_BIAS_ORDER = (3, 0, 5, 1, 7, 4, 2, 6)
+
+
+def moe_biased_grads(x, dout, P, bias, n_exp, k, dtype, weights_biased=False):
+    """`helpers_moe_train.layer_grads` of the shared GLU layer with the routing of helpers_v3_train.forward_restated's `ff`: top-k of
+    logits + bias, softmax over the chosen experts' raw logits.  weights_biased: the wrong variant, the softmax over logits + bias.
+    Also: gap, the smallest k-th versus (k+1)-th selection value relative to the largest, and the share of rows whose expert set is not
+    the raw logits'."""
+    from tests import helpers_moe_train as TMoe
+    with torch.enable_grad():
+        t = lambda a: torch.as_tensor(np.asarray(a)).to(dtype)
+        Pt = {key: t(v).requires_grad_(True) for key, v in P.items()}
+        xt = t(x).requires_grad_(True)
+        logits = TMoe.gate_logits(Pt, "", xt)
+        sel = logits + t(bias)
+        idx = torch.topk(sel, k, dim=-1).indices
+        w = torch.softmax(torch.gather(sel if weights_biased else logits, -1, idx), dim=-1)
+        out = torch.zeros_like(xt)
+        for e in range(n_exp):
+            tok, j = torch.where(idx == e)
+            if tok.numel():
+                out = out.index_add(0, tok, w[tok, j].unsqueeze(1) * TMoe.expert(Pt, f"experts.{e}.", xt[tok]))
+        out = out + (1.0 / k) * TMoe.expert(Pt, "shared_expert.", xt)
+        (out * t(dout)).sum().backward()
+    g = {key: (torch.zeros_like(v) if v.grad is None else v.grad).numpy().astype(np.float64) for key, v in Pt.items()}
+    g["x"] = xt.grad.numpy().astype(np.float64)
+    plain = torch.topk(logits.detach(), k, dim=-1).indices.sort(-1).values
+    return {"out": out.detach().numpy().astype(np.float64), "grads": g, "idx": idx.numpy(), "weights": w.detach().numpy().astype(np.float64),
+            "gap": TMoe.gate_gap(sel, k), "flipped": float((idx.sort(-1).values != plain).any(-1).double().mean())}
+
+
+@functools.lru_cache(maxsize=None)
+def moe_biased_recipe(n_tok, d, raw, n_exp, k):
+    """`moe_recipe` and a selection bias -> x, dout, P, bias (n_exp,) fp32, fp64 and fp32 results of `moe_biased_grads`."""
+    x, dout, P, _, _ = moe_recipe(n_tok, d, raw, n_exp, k)
+    logits = x.astype(np.float64) @ P["gate.weight"].astype(np.float64).T + P["gate.bias"]
+    assert n_exp == len(MOE_BIAS_ORDER)
+    bias = (logits.std() * np.linspace(-1.0, 1.0, n_exp)[list(MOE_BIAS_ORDER)]).astype(np.float32)
+    return x, dout, P, bias, moe_biased_grads(x, dout, P, bias, n_exp, k, torch.float64), moe_biased_grads(x, dout, P, bias, n_exp, k, torch.float32)
 
 
 GLU_CASES = [(129, 32, 100, False), (129, 32, 100, True)]       # n, d, dff (padded to 128), SiLU expert

@@ -1,7 +1,9 @@
 """The softmax-shaped, scan, gate and row-statistics kernels against fp64 on the recipes of tests/helpers_numeric_range.py: inputs
 away from N(0,1), where the running-max rescale, `m + log l`, `__expf` at large arguments, softplus's threshold, a sigmoid past the
 exponential's overflow and the row statistics decide the answer.  tests/test_numeric_range_host.py shows on the CPU that every recipe
-reaches its regime, that its bound stays under 1e-3 and that the wrong variant it exists for misses it.
+reaches its regime, that its bound stays under 1e-3 and that the wrong variant it exists for misses it.  The families that came later
+run the same recipes: the auxiliary chord loss, the wide recurrence and wide-state scan kernels, the differential sub-norm's backward
+and the balanced router.
 
 Bound for every output: rel_err(got, ref64) <= max(8 e32, n U) (see the helper); every test prints err/bound per output."""
 import ctypes as C
@@ -128,6 +130,36 @@ def test_chord_loss_and_metrics(treatment, smoothing):
         assert np.array_equal(m[:, f["n_valid"]], host(clip)[:, 0]) and np.array_equal(pred.cpu().numpy(), y.argmax(-1))
 
 
+@pytest.mark.parametrize("smoothing", [0.0, 0.1])
+@pytest.mark.parametrize("layout", ["rows", "view"])
+@pytest.mark.parametrize("recipe", R.AUX_RECIPES)
+def test_chord_aux_loss(recipe, layout, smoothing):
+    """amt_chord_loss_aux_fwd_bwd at (2, 65): the six losses, `count`, the six per-clip columns and dlogits, each at its own scale.  An
+    inactive hinge of the `count_flip_guard` recipes is exactly 0, and with neither active the gradient is the plain loss kernel's."""
+    from tests import helpers_chord_aux as HA
+    y, tgt, emo = R.chord_aux_case(recipe, layout)
+    B, L = tgt.shape
+    yd, td, ed = dev(y), dev(tgt), dev(emo)
+    loss, clip, dlogits = ops.chord_loss_aux(yd, td, ed, R.AUX_W[0], R.AUX_W[1], smoothing, layout)
+    w64, w32 = R.chord_aux_refs(recipe, layout, smoothing)
+    got = R.chord_aux_split({"loss": host(loss), "clip": host(clip), "dlogits": host(dlogits)})
+    assert got["count"][0] == w64["count"][0]
+    check(f"chord_aux {recipe} {layout} smoothing {smoothing}", got, w64, w32, R.chord_aux_n(B, L))
+    for k in ("loss_aux3", "loss_aux5", "clip_a3", "clip_a5"):
+        if not w64[k].any():
+            assert not got[k].any(), k
+    if recipe.startswith("count_flip_guard"):                   # small cross-entropies at + 1000: the plain loss and the metrics kernel too
+        _, pclip, plain = ops.chord_loss(yd, td, ed, R.AUX_W[0], smoothing)
+        sums = lambda c, i, j: {"clip_ce": host(c)[:, i], "clip_bce": host(c)[:, j]}
+        check(f"chord_loss {recipe} {layout} smoothing {smoothing}", sums(pclip, 1, 2), w64, w32, R.chord_aux_n(B, L), only=("clip_ce", "clip_bce"))
+        if smoothing == 0.0:
+            f = {k: i for i, k in enumerate(HE.FIELDS)}
+            m = ops.chord_metrics(yd, td, ed, dev(np.full((B, L), 0.9, dtype=np.float32)), 0.8, return_rows=True)[0]
+            check(f"chord_metrics {recipe} {layout}", sums(m, f["ce_sum"], f["bce_sum"]), w64, w32, R.chord_aux_n(B, L), only=("clip_ce", "clip_bce"))
+        if recipe == "count_flip_guard1":
+            assert R.rel_err(host(dlogits), host(plain)) <= R.bound(R.rel_err(w32["dlogits"], w64["dlogits"]), HA.NC)
+
+
 # ---- B. selective scan ----------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("version", [0, 1])
@@ -135,8 +167,23 @@ def test_chord_loss_and_metrics(treatment, smoothing):
 @pytest.mark.parametrize("shape", R.SCAN_SHAPES)
 @pytest.mark.parametrize("recipe", R.SCAN_RECIPES)
 def test_selective_scan(recipe, shape, reverse, version):
+    scan_forward_and_backward(recipe, shape, 16, reverse, version)
+
+
+@pytest.mark.parametrize("version", [0, 1])
+@pytest.mark.parametrize("reverse", [0, 1])
+@pytest.mark.parametrize("N", R.SCAN_WIDE_N)
+@pytest.mark.parametrize("shape", R.SCAN_SHAPES)
+@pytest.mark.parametrize("recipe", R.SCAN_RECIPES)
+def test_selective_scan_wide_training(recipe, shape, N, reverse, version):
+    """amt_selective_scan_wide_train_fwd / amt_selective_scan_wide_bwd at 32 and 256 states: checkpoints every 32 steps (L = 33 and 70
+    cross one and two), N / 16 slices whose partial state sums a second launch adds."""
+    assert ops.scan_ckpt_steps(N) == R.SCAN_CHUNK
+    scan_forward_and_backward(recipe, shape, N, reverse, version)
+
+
+def scan_forward_and_backward(recipe, shape, N, reverse, version):
     B, L, ED = shape
-    N = 16
     c = R.scan_recipe(recipe, B, L, ED, N)
     Rk, M = c["R"], B * L
     d = {k: v.to(DEV) for k, v in c.items() if k != "R"}
@@ -152,7 +199,7 @@ def test_selective_scan(recipe, shape, reverse, version):
            "d_dt_bias": ddraw.sum(0), "dA_log": dA_log, "dD": dD}
     got = R.scan_split(recipe, {k: host(v) for k, v in got.items()})
     w64, w32 = R.scan_refs(recipe, B, L, ED, N, version, reverse)
-    check(f"scan {recipe} {shape} reverse {reverse} version {version}", got, w64, w32, R.scan_n(B, L, N), R.SCAN_VANISH)
+    check(f"scan {recipe} {shape} N {N} reverse {reverse} version {version}", got, w64, w32, R.scan_n(B, L, N), R.SCAN_VANISH)
 
 
 @pytest.mark.parametrize("reverse", [0, 1])
@@ -187,6 +234,29 @@ def test_recurrent_gates(recipe, G, n_dirs):
     got = {"y": host(y), "dxproj": host(dxp), "db_hh": host(hidden.sum(0).reshape(n_dirs, G * d))}
     w64, w32 = R.rnn_refs(recipe, G, n_dirs)
     check(f"rnn {recipe} G {G} dirs {n_dirs}", got, w64, w32, R.rnn_n(recipe, G))
+
+
+@pytest.mark.parametrize("recipe,G,n_dirs,d", R.RNN_WIDE_CASES)
+def test_wide_recurrent_gates(recipe, G, n_dirs, d):
+    """amt_rnn_wide_seq_fwd / _train_fwd / _bwd (csrc/rnn_wide.hip) at d = 160 and 256, driven as `test_recurrent_gates` drives the
+    register kernels."""
+    xproj, w_hh, b_hh, dy = R.rnn_recipe(recipe, G, n_dirs, R.RNN_SHAPE[0], d)
+    B, L = xproj.shape[:2]
+    M, Cc = B * L, ops.rnn_reserve_cols(G)
+    xp, wh, bh, dyd = dev(xproj.reshape(M, -1)), dev(w_hh.reshape(n_dirs * G * d, d)), dev(b_hh.reshape(-1)), dev(dy.reshape(M, -1))
+    nan = lambda cols: torch.full((M, cols), float("nan"), device=DEV)
+    y, y_eval, rsv, dxp = nan(n_dirs * d), nan(n_dirs * d), nan(n_dirs * Cc * d), nan(n_dirs * G * d)
+    dhn = nan(n_dirs * d) if G == 3 else None
+    ops.rnn_wide_seq(xp, wh, bh, y_eval, 0, B, L, d, G, n_dirs=n_dirs)
+    ops.rnn_wide_seq_train(xp, wh, bh, y, 0, rsv, B, L, d, G, n_dirs=n_dirs)
+    ops.rnn_wide_seq_bwd(dyd, 0, rsv, y, 0, wh, dxp, dhn, B, L, d, G, n_dirs=n_dirs)
+    assert torch.equal(y, y_eval)
+    hidden = dxp.view(M, n_dirs, G, d).clone()               # the hidden side's pre-activation gradients: a GRU's n block is dhn
+    if G == 3:
+        hidden[:, :, 2] = dhn.view(M, n_dirs, d)
+    got = {"y": host(y), "dxproj": host(dxp), "db_hh": host(hidden.sum(0).reshape(n_dirs, G * d))}
+    w64, w32 = R.rnn_refs(recipe, G, n_dirs, d)
+    check(f"rnn_wide {recipe} G {G} dirs {n_dirs} d {d}", got, w64, w32, R.rnn_n(recipe, G, d=d))
 
 
 @pytest.mark.parametrize("M,N,K,act,resid", R.ACT_CASES)
@@ -228,6 +298,23 @@ def test_diff_subln(recipe, shape):
     y = ops.diff_subln(dev(o1), dev(o2), dev(w), R.SUBLN_LAM, R.SUBLN_SCALE)
     check(f"diff_subln {recipe} {shape}", {"y": host(y)}, R.subln_run(o1, o2, w, torch.float64), R.subln_run(o1, o2, w, torch.float32),
           lambda k: shape[1])
+
+
+@pytest.mark.parametrize("shape", R.SUBLN_BWD_SHAPES)
+@pytest.mark.parametrize("recipe", R.SUBLN_BWD_RECIPES)
+def test_diff_subln_training_forward_and_backward(recipe, shape):
+    """amt_diff_subln_train_fwd / amt_diff_subln_bwd with lambda on the device: y is `ops.diff_subln`'s bits; d_o1, d_o2, dw and dlambda
+    each at its own scale.  On `constant` o2 is 0 and dlambda exactly 0."""
+    o1, o2, w, dy = (dev(a) for a in R.subln_bwd_inputs(recipe, *shape))
+    lam = torch.tensor([R.SUBLN_LAM], dtype=torch.float32, device=DEV)
+    y = ops.diff_subln_train(o1, o2, w, lam, R.SUBLN_SCALE)
+    assert torch.equal(y, ops.diff_subln(o1, o2, w, R.SUBLN_LAM, R.SUBLN_SCALE))
+    d_o1, d_o2, dw, dlam = ops.diff_subln_bwd(dy, o1, o2, w, lam, R.SUBLN_SCALE)
+    got = {"y": host(y), "d_o1": host(d_o1), "d_o2": host(d_o2), "dw": host(dw), "dlambda": host(dlam)}
+    w64, w32 = R.subln_bwd_refs(recipe, *shape)
+    check(f"diff_subln backward {recipe} {shape}", got, w64, w32, R.subln_bwd_n(*shape))
+    if recipe == "constant":
+        assert w64["dlambda"][0] == 0.0 and got["dlambda"][0] == 0.0
 
 
 # ---- the folded LayerNorm at the mean / std ladder -----------------------------------------------------------------------------
@@ -320,6 +407,25 @@ def test_moe_with_saturated_router(case):
         assert np.array_equal(ridx.cpu().numpy(), o64["idx"])
         check(f"moe_route gate x100 {case}", {"weights": host(rw)}, R.moe_tensors(o64), R.moe_tensors(o32), R.moe_n(n_tok, d, raw, k),
               only=("weights",))
+
+
+@pytest.mark.parametrize("case", R.MOE_CASES)
+def test_balanced_moe_with_saturated_router(case):
+    """amt_moe_train_fwd_balanced and amt_moe_bwd through a SharedMoELayer that trains its balancing: the experts chosen on
+    logits + bias in fp64's order, the weights from the raw logits, the output and every gradient."""
+    from tests.test_moe_bwd_gpu import run
+    from video2music_amd.model.moe import GLUExpert, SharedMoELayer
+    n_tok, d, raw, n_exp, k = case
+    x, dout, Pm, bias, o64, o32 = R.moe_biased_recipe(*case)
+    layer = SharedMoELayer(GLUExpert(d, raw, dropout=0.0), d, n_experts=n_exp, n_experts_per_token=k, dropout=0.0, balancing=True)
+    layer.load_state_dict({**{name: torch.from_numpy(v) for name, v in Pm.items()}, "bias": torch.from_numpy(bias).view(n_exp, 1)}, strict=True)
+    layer = layer.to(DEV)
+    layer.train_balancing = True
+    out, grads = run(layer, x, dout)
+    idx, wts = layer.last_routing
+    assert np.array_equal(idx.reshape(n_tok, k).cpu().numpy(), o64["idx"])
+    got = {"out": host(out), "weights": host(wts.reshape(n_tok, k)), **grads}
+    check(f"moe gate x100 biased {case}", got, R.moe_tensors(o64), R.moe_tensors(o32), R.moe_n(n_tok, d, raw, k))
 
 
 @pytest.mark.parametrize("case", R.GLU_CASES)

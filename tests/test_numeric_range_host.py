@@ -154,6 +154,69 @@ def test_chord_logit_treatments(treatment):
         under_cap(w64, w32, R.chord_n(2, 5), f"{treatment} smoothing {smoothing}")
 
 
+AUX_CASES = [(r, layout) for r in R.AUX_RECIPES for layout in ("rows", "view")]
+
+
+def aux_rows_of(recipe, layout):
+    """The valid auxiliary rows z (rows, 159) of the case and their targets."""
+    from tests import helpers_chord_aux as HA
+    y, tgt, emo = R.chord_aux_case(recipe, layout)
+    t, _ = HA.clean_targets(tgt, emo)
+    valid = t != HA.C.CHORD_PAD
+    return HA.aux_rows(y, layout)[valid], t[valid]
+
+
+@pytest.mark.parametrize("recipe,layout", AUX_CASES)
+def test_chord_aux_recipe(recipe, layout):
+    """Every case stays away from a tie at the top-k border and from the hinge's kink by floors derived from the fp32 spacing at its
+    logits' magnitude, reaches what it is named for, and `count` is the same in both precisions."""
+    from tests import helpers_chord_aux as HA
+    assert HA.LAYOUTS == ("rows", "view")
+    y, tgt, emo = R.chord_aux_case(recipe, layout)
+    assert y.shape == HA.REGIME_SHAPE + (HA.NC,) and y.dtype == np.float32
+    gap, margin = HA.conditions(y, tgt, layout)
+    gap_floor, margin_floor = R.chord_aux_floors(y)
+    print(recipe, layout, f"gap {gap:.2e} (floor {gap_floor:.1e}) margin {margin:.2e} (floor {margin_floor:.1e})")
+    assert gap >= gap_floor and margin >= margin_floor
+    z, t = aux_rows_of(recipe, layout)
+    s = -np.sort(-z.astype(np.float64), axis=-1)
+    if recipe == "ties_inside":
+        assert (s[:, 0] == s[:, 1]).all() and (s[:, 3] == s[:, 4]).all() and (s[:, 1] > s[:, 2]).all() and len(z) > 40
+    elif recipe.startswith("count_flip_guard"):
+        assert y.min() > 980
+    for smoothing in (0.0, 0.1):
+        w64, w32 = R.chord_aux_refs(recipe, layout, smoothing)
+        want = {"count_flip_guard2": 2, "count_flip_guard1": 1}.get(recipe, 3)
+        assert w64["count"][0] == w32["count"][0] == want
+        if want < 3:                                                  # the inactive hinges: exactly 0 in both precisions
+            for k in ("loss_aux5", "clip_a5") + (("loss_aux3", "clip_a3") if want == 1 else ()):
+                assert not w64[k].any() and not w32[k].any(), k
+        under_cap(w64, w32, R.chord_aux_n(*HA.REGIME_SHAPE), f"chord_aux {recipe} {layout} smoothing {smoothing}")
+
+
+@pytest.mark.parametrize("layout", ["rows", "view"])
+def test_second_softmax_without_its_maximum_is_not_finite_on_offset1000(layout):
+    z, t = aux_rows_of("offset1000", layout)
+    for i, k in ((4, 3), (5, 5)):
+        want = R.chord_aux_refs("offset1000", layout, 0.0)[0]["clip_" + R.AUX_CLIP[i]].sum()
+        ok, wrong = R.aux_hinge_sum_f32(z, t, k), R.aux_hinge_sum_f32(z, t, k, "no_max")
+        assert abs(ok - want) <= R.bound(0.0, 159 + len(z)) * want and not np.isfinite(wrong)        # inf / inf
+
+
+@pytest.mark.parametrize("layout", ["rows", "view"])
+def test_top_k_chosen_on_the_underflowed_probabilities_cannot_miss(layout):
+    """The second wrong variant the auxiliary loss was to be shown against, and why it is dropped: on `spread30` most of a row's
+    probabilities underflow to 0 and tie there, yet choosing the k largest on the rounded p gives the sums choosing on the logits gives,
+    bit for bit.  p is a non-decreasing function of the logit, so the k largest p are the p of the k largest logits as a multiset, ties
+    included: the hinge's value cannot tell the two apart on any input."""
+    z, t = aux_rows_of("spread30", layout)
+    with np.errstate(under="ignore"):
+        p = np.exp((z - z.max(-1, keepdims=True)).astype(np.float32))
+    assert ((p < R.FLT_MIN).sum(-1) >= 20).all()                      # 20 or more of a row's 159 classes are flushed to 0 and tie there
+    for k in (3, 5):
+        assert R.aux_hinge_sum_f32(z, t, k, "topk_of_p") == R.aux_hinge_sum_f32(z, t, k) > 0
+
+
 # ---- B. selective scan ----------------------------------------------------------------------------------------------------------
 
 def scan_facts(recipe, B, L, ED, N=16):
@@ -166,8 +229,12 @@ def scan_facts(recipe, B, L, ED, N=16):
 @pytest.mark.parametrize("shape", R.SCAN_SHAPES)
 @pytest.mark.parametrize("recipe", R.SCAN_RECIPES)
 def test_scan_recipe_reaches_its_regime(recipe, shape):
+    scan_regime(recipe, shape, 16)
+
+
+def scan_regime(recipe, shape, N):
     B, L, ED = shape
-    c, v, delta = scan_facts(recipe, B, L, ED)
+    c, v, delta = scan_facts(recipe, B, L, ED, N)
     A = -torch.exp(c["A_log"].double())
     if recipe == "slow_decay":
         assert float(torch.exp(delta.max() * A.min()) ** 32) > 0.9
@@ -223,13 +290,69 @@ def test_softplus_variants():
     assert R.rel_err(wrong, y64) <= R.bound(R.rel_err(ok, y64), 33 * 16)              # judged as one tensor it would go unseen
 
 
+@pytest.mark.parametrize("N", R.SCAN_WIDE_N)
+@pytest.mark.parametrize("shape", R.SCAN_SHAPES)
+@pytest.mark.parametrize("recipe", R.SCAN_RECIPES)
+def test_scan_wide_recipe_reaches_its_regime(recipe, shape, N):
+    scan_regime(recipe, shape, N)
+
+
+@pytest.mark.parametrize("version", [0, 1])
+@pytest.mark.parametrize("reverse", [0, 1])
+@pytest.mark.parametrize("N", R.SCAN_WIDE_N)
+@pytest.mark.parametrize("shape", R.SCAN_SHAPES)
+@pytest.mark.parametrize("recipe", R.SCAN_RECIPES)
+def test_scan_wide_training_bound_is_under_the_cap(recipe, shape, N, reverse, version):
+    """The largest bounds are the n U floor of the state chains at N = 256, n = L N: 5.0e-4 at L = 33; at L = 70 it would be 1.07e-3,
+    over the cap, and `scan_n` holds n at CAP / U there: the case runs, against the cap itself."""
+    B, L, ED = shape
+    assert R.scan_n(B, L, N)("y") == min(L * N, int(R.CAP / R.U)) and R.scan_n(B, L, N)("dD") == B * L
+    w64, w32 = R.scan_refs(recipe, B, L, ED, N, version, reverse)
+    under_cap(w64, w32, R.scan_n(B, L, N), f"{recipe} {shape} N {N} reverse {reverse} version {version}", R.SCAN_VANISH)
+
+
+@pytest.mark.parametrize("shape", R.SCAN_SHAPES)
+@pytest.mark.parametrize("carry", ["zero", "neighbour"])
+def test_a_wrong_carried_state_misses_slow_decay_at_32_states(carry, shape):
+    B, L, ED = shape
+    c = R.scan_recipe("slow_decay", B, L, ED, 32)
+    y64 = R.scan_state_np(c, B, L, ED, 32, np.float64)
+    b = R.bound(R.rel_err(R.scan_state_np(c, B, L, ED, 32, np.float32), y64), L * 32)
+    assert b <= R.CAP and R.rel_err(R.scan_state_np(c, B, L, ED, 32, np.float32, carry), y64) > 100 * b
+
+
+@pytest.mark.parametrize("N", R.SCAN_WIDE_N)
+@pytest.mark.parametrize("shape", R.SCAN_SHAPES)
+def test_a_state_slice_left_out_of_the_sum_misses(shape, N):
+    """y's state sum over the first N - 16 states only, what a lost partial of the wide kernels' slice sum leaves."""
+    B, L, ED = shape
+    for recipe in ("slow_decay", "fast_decay"):
+        c = R.scan_recipe(recipe, B, L, ED, N)
+        y64 = R.scan_state_np(c, B, L, ED, N, np.float64)
+        b = R.bound(R.rel_err(R.scan_state_np(c, B, L, ED, N, np.float32), y64), R.scan_n(B, L, N)("y"))
+        miss = R.rel_err(R.scan_state_np(c, B, L, ED, N, np.float32, slices_left_out=1), y64) / b
+        print(f"{recipe} {shape} N {N}: one slice left out, err / bound = {miss:.1f}")
+        assert b <= R.CAP and miss > (100 if recipe == "slow_decay" else 1)
+
+
 # ---- C. gates --------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("recipe,G,n_dirs", R.RNN_CASES)
 def test_rnn_recipe(recipe, G, n_dirs):
-    xproj, w_hh, b_hh, dy = R.rnn_recipe(recipe, G, n_dirs)
-    d = R.RNN_SHAPE[2]
-    w64, w32 = R.rnn_refs(recipe, G, n_dirs)
+    rnn_regime(recipe, G, n_dirs, R.RNN_SHAPE[2])
+
+
+@pytest.mark.parametrize("recipe,G,n_dirs,d", R.RNN_WIDE_CASES)
+def test_rnn_wide_recipe(recipe, G, n_dirs, d):
+    """The recipes at the wide kernels' widths.  Largest bounds: `xproj30` and `cell_ramp` 6.5e-5; `whh2` 6.8e-4 at d = 160 and 9.1e-4 at
+    256 (GRU, two directions), under the cap."""
+    assert d > 128 and d % 32 == 0                                    # past ops.RNN_NARROW_MAX, whole 32-column tiles
+    rnn_regime(recipe, G, n_dirs, d)                                  # xproj30: exp(v) / (1 + exp(v)) is NaN at every width
+
+
+def rnn_regime(recipe, G, n_dirs, d):
+    xproj, w_hh, b_hh, dy = R.rnn_recipe(recipe, G, n_dirs, R.RNN_SHAPE[0], d)
+    w64, w32 = R.rnn_refs(recipe, G, n_dirs, d)
     if recipe == "xproj30":
         assert xproj.max() > R.EXP_OVERFLOW and xproj.min() < -R.EXP_OVERFLOW
         assert np.isnan(R.sigmoid_f32(xproj, "exp_over")).any() and np.isfinite(R.sigmoid_f32(xproj)).all()       # inf / inf
@@ -253,7 +376,7 @@ def test_rnn_recipe(recipe, G, n_dirs):
                 assert ((y[:, step(t, r), r] >= lo * (1 - 1e-7)) & (y[:, step(t, r), r] <= hi)).all()
             assert np.abs(y[:, step(0, r), r]).max() < np.tanh(1.0) + 1e-6    # while at the first step c = 1
         assert np.abs(w64["dxproj"]).max() > 1e-2
-    under_cap(w64, w32, R.rnn_n(recipe, G), f"{recipe} G {G} dirs {n_dirs}")
+    return under_cap(w64, w32, R.rnn_n(recipe, G, d=d), f"{recipe} G {G} dirs {n_dirs} d {d}")
 
 
 @pytest.mark.parametrize("M,N,K,act,resid", R.ACT_CASES)
@@ -325,6 +448,50 @@ def test_subln_bound_is_under_the_cap(recipe, shape):
     under_cap(R.subln_run(o1, o2, w, torch.float64), R.subln_run(o1, o2, w, torch.float32), lambda k: shape[1], f"diff_subln {recipe} {shape}")
 
 
+@pytest.mark.parametrize("shape", R.SUBLN_BWD_SHAPES)
+@pytest.mark.parametrize("recipe", R.SUBLN_BWD_RECIPES)
+def test_subln_backward_recipe(recipe, shape):
+    """o1 - lam o2 is the recipe's row; every bound of y, d_o1, d_o2, dw and dlambda is under the cap (the largest, 7.9e-5, is the 8 n U
+    of `constant`'s exactly-zero dlambda; 9.8e-6 at 1e12)."""
+    rows, hd = shape
+    o1, o2, w, dy = R.subln_bwd_inputs(recipe, rows, hd)
+    a = R.norm_recipe(recipe, rows, hd, True)
+    u = o1.astype(np.float64) - R.SUBLN_LAM * o2.astype(np.float64)
+    assert np.array_equal(u, a["x"].astype(np.float64) + a["resid"].astype(np.float64)) and hd in (32, 64, 128)
+    w64, w32 = R.subln_bwd_refs(recipe, rows, hd)
+    assert w64["dlambda"].shape == (1,)
+    if recipe == "constant":                                          # o2 = 0: dlambda = -sum du o2 is exactly 0
+        assert not o2.any() and not u.std(1).any() and w64["dlambda"][0] == 0.0 and w32["dlambda"][0] == 0.0
+    elif recipe == "cancel":                                          # o1 and lam o2 at 1e4, their difference a unit row; dlambda at 1e5 .. 1e6
+        assert np.abs(o1).min() > 0.5 * R.BIG and np.allclose(u.std(1), 1.0, atol=5e-2) and 1e4 < abs(w64["dlambda"][0]) < 1e7
+    elif recipe == "huge12":
+        assert u.std(1).min() > 5e11
+    under_cap(w64, w32, R.subln_bwd_n(rows, hd), f"diff_subln backward {recipe} {shape}")
+
+
+def test_subln_backward_at_1e15_is_past_the_fp32_reference():
+    """Why `huge` is `huge12` here: at rows of 1e15 torch's own fp32 autograd of the written-out sub-norm is percents to tenths off fp64
+    in d_o1, d_o2 and dlambda (ms^-3/2 underflows, as in the RMSNorm), and 8 e32 is far over the cap."""
+    for rows, hd in R.SUBLN_BWD_SHAPES:
+        o1, o2, w = R.subln_inputs("huge", rows, hd)
+        dy = R.norm_recipe("huge", rows, hd, True)["dy"]
+        w64, w32 = (R.subln_run(o1, o2, w, dt, grads=True, dy=dy) for dt in (torch.float64, torch.float32))
+        e = {k: R.rel_err(w32[k], w64[k]) for k in ("d_o1", "d_o2", "dlambda")}
+        print((rows, hd), e)
+        assert 8 * min(e.values()) > 10 * R.CAP
+
+
+@pytest.mark.parametrize("shape", R.SUBLN_BWD_SHAPES)
+def test_statistics_of_o1_alone_miss_the_cancelling_pair_of_the_subln(shape):
+    rows, hd = shape
+    o1, o2, w, dy = R.subln_bwd_inputs("cancel", rows, hd)
+    w64, w32 = R.subln_bwd_refs("cancel", rows, hd)
+    wrong = R.subln_run(o1, o2, w, torch.float32, grads=True, dy=dy, stats_of_o1_alone=True)
+    n = R.subln_bwd_n(rows, hd)
+    for k in ("y", "d_o1", "d_o2", "dw"):
+        assert R.rel_err(wrong[k], w64[k]) > 100 * R.bound(R.rel_err(w32[k], w64[k]), n(k)), k
+
+
 @pytest.mark.parametrize("m", R.FOLD_LADDER)
 def test_fold_bounds_are_under_the_cap(m):
     """The folded forms' bound is 8 x the fp32 evaluation of (raw - mu g) rstd + c; the fused LayerNorm's 8 x the unfolded fp32.  At
@@ -351,6 +518,27 @@ def test_moe_gate_times_100(case):
                 assert float(g.max()) > R.EXP_OVERFLOW and float(g.min()) < -R.EXP_OVERFLOW
                 assert np.isnan(R.sigmoid_f32(g.numpy(), "exp_over")).any()
     under_cap(R.moe_tensors(o64), R.moe_tensors(o32), R.moe_n(n_tok, d, raw, k), f"moe {case}")
+
+
+@pytest.mark.parametrize("case", R.MOE_CASES)
+def test_moe_gate_times_100_with_a_selection_bias(case):
+    """The bias moves at least a quarter of the rows to another expert set, the biased k-th versus (k+1)-th gap stays above the floor
+    (relative to the largest selection value: helpers_moe_train.GAP, and never under 8 d U, eight times what an fp32 dot product of
+    length d loses at that magnitude), fp32 picks fp64's experts in fp64's order, and weights from logits + bias miss."""
+    from tests import helpers_moe_train as TMoe
+    from tests import helpers_v3_train as V
+    n_tok, d, raw, n_exp, k = case
+    x, dout, P, bias, o64, o32 = R.moe_biased_recipe(*case)
+    assert sorted(R.MOE_BIAS_ORDER) == list(range(n_exp)) and sorted(V.BIAS_ORDER) == list(range(6)) and bias.dtype == np.float32
+    assert np.array_equal(np.sort(bias), np.sort(bias)[::-1] * -1)                   # a ramp, permuted
+    print(f"moe bias {case}: flipped {o64['flipped']:.2f} gap {o64['gap']:.2e}")
+    assert o64["flipped"] >= 0.25 and o64["gap"] >= max(TMoe.GAP, 8 * d * R.U)
+    assert np.array_equal(o64["idx"], o32["idx"])
+    n_of = R.moe_n(n_tok, d, raw, k)
+    c = under_cap(R.moe_tensors(o64), R.moe_tensors(o32), n_of, f"moe biased {case}")
+    wrong = R.moe_tensors(R.moe_biased_grads(x, dout, P, bias, n_exp, k, torch.float32, weights_biased=True))
+    for name in ("weights", "out"):
+        assert R.rel_err(wrong[name], R.moe_tensors(o64)[name]) > 100 * c[name], name
 
 
 @pytest.mark.parametrize("case", R.GLU_CASES)

@@ -123,12 +123,12 @@ __global__ __launch_bounds__(THREADS) void chord_aux_kernel(const float* __restr
         const float m = wave_max(fmaxf(fmaxf(y0, y1), y2));
         const float e0 = expf(y0 - m), e1 = expf(y1 - m), e2 = has2 ? expf(y2 - m) : 0.0f;
         const float se = wave_sum((e0 + e1) + e2);
-        const float lse = m + logf(se);
+        const float lse = logf(se);                         // not m + log se: see chord_loss.hip
         const float ysel = t < 64 ? y0 : t < 128 ? y1 : y2;
-        const float nll = lse - readlane_f(ysel, t & 63);
+        const float nll = lse - (readlane_f(ysel, t & 63) - m);
         float ce = nll;
         if (smoothing != 0.0f) {
-            const float sy = wave_sum((y0 + y1) + (has2 ? y2 : 0.0f));
+            const float sy = wave_sum(((y0 - m) + (y1 - m)) + (has2 ? y2 - m : 0.0f));
             ce = (1.0f - smoothing) * nll + smoothing * (((float)NC * lse - sy) / (float)NC);
         }
         const bool t0 = chord && lane != 0 && ((qm >> q0) & 1u);

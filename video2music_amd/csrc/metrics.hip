@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void chord_metrics_kernel(
 
             // cross-entropy, max-subtracted
             const float se = wave_sum((expf(y0 - m) + expf(y1 - m)) + (has2 ? expf(y2 - m) : 0.0f));
-            const float ce = (m + logf(se)) - yt;
+            const float ce = logf(se) - (yt - m);           // not (m + log se) - yt: see chord_loss.hip
 
             // BCE against the emotion row of the target's second
             const bool t0 = chord && lane != 0 && ((qm >> q0) & 1u);
