@@ -157,6 +157,12 @@ amt_status amt_generate_run(amt_handle* h, int32_t n_steps, float* logits_out, v
  *   of the folded step take the lean front (row, tile and weight addresses worked out on the scalar unit from one block of kernel
  *   arguments).
  *   Part of the key of a captured graph; results are bit-identical either way.
+ *   "gemm_rows_dma" = 0 (any time): every row chunk of the decode step's skinny GEMMs goes through registers and a ds_write; 1, the
+ *   default: the lean-front launches request the chunks that nothing is done to on their way (all of a plain launch's; behind the
+ *   folded-FFN prologue the raw columns, when K1 = 2 (K - K1)) by LDS-DMA, straight into the staged row.  Part of the
+ *   key of a captured graph; results are bit-identical either way.  With a NULL handle the option sets the process-wide default of
+ *   the entry points that carry no handle (amt_decode_gemm_ex_fwd; initially 1 as well); a launch takes the DMA form when neither
+ *   its handle (or AMT_GEMM_PRO_REG_ROWS) nor, without a handle, the process-wide default says otherwise.
  *   "scalar_key_stream" = 0 (any time): the decode attentions of this handle keep the per-lane controlled key stream (every load
  *   clamped, every key guarded, one batch requested past a wave's last); 1, the default: the scalar-controlled one (per wave a scalar
  *   batch count, buffer loads on a scalar base, nothing requested behind the last batch).  Part of the key of a captured
@@ -290,6 +296,9 @@ amt_status amt_attn_decode_fold_fwd(const float* raw, int32_t ldq, float* kcache
  * the launch would take the lean one (wave-uniform address work on the scalar unit; see "gemm_scalar_front").  The serial loop
  * implies it.  What is loaded and summed is the same: y_low / y_high are bit-identical either way. */
 #define AMT_GEMM_PRO_GENERIC_FRONT 0x200
+/* Bit of amt_decode_gemm_args.pro: stage every row chunk through registers where the launch would request it by LDS-DMA (see
+ * "gemm_rows_dma").  Only the data path differs: y_low / y_high are bit-identical either way. */
+#define AMT_GEMM_PRO_REG_ROWS 0x400
 typedef struct amt_decode_gemm_args {
     const float* x;  int32_t ldx;          /* first K1 columns of the rows (all K when x2 is null) */
     const float* x2; int32_t ldx2;         /* remaining K - K1 columns, or null */
@@ -297,7 +306,7 @@ typedef struct amt_decode_gemm_args {
     const float* w_low;  const float* bias_low;  const float* resid; int32_t relu;   /* y_low = act(x . w_low^T + b (+ resid)) */
     const float* w_high; const float* bias_high;                                     /* y_high = [x | x2] . w_high^T + b_high */
     int32_t n_low, n_high;
-    int32_t pro;                           /* 1: folded-FFN prologue (see above); | AMT_GEMM_PRO_SERIAL_LOOP: the serial tile loop; | AMT_GEMM_PRO_GENERIC_FRONT */
+    int32_t pro;                           /* 1: folded-FFN prologue (see above); | AMT_GEMM_PRO_SERIAL_LOOP: the serial tile loop; | AMT_GEMM_PRO_GENERIC_FRONT; | AMT_GEMM_PRO_REG_ROWS */
     const float* fold_g; const float* fold_c; const float* ln_w; const float* ln_b;
     float* y_low; float* y_high;
     float* scratch_low; float* scratch_high;   /* packed copies of the weights, ceil(n/16)*16*K floats each */

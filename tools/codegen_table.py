@@ -7,7 +7,9 @@
 For every kernel: registers, LDS, spills, scratch and instruction count on both sides; whether the sub-sequence of matrix, LDS and
 global-memory instructions is the same, and whether it still is with waits, barriers and branches counted in; and every
 mnemonic-level difference of the whole body.
-Kernels are matched by name with enum template arguments read as their integer values."""
+Kernels are matched by name with enum template arguments read as their integer values.  A kernel of NEW.s whose name is a parent's
+with one more trailing `false` template argument (a template flag added with its default) is matched to that parent; kernels that
+only NEW.s holds (the flag's `true` instantiations) are listed behind the table with their own figures."""
 import difflib
 import re
 import subprocess
@@ -66,7 +68,15 @@ def main():
     pm, pb = parse(sys.argv[1])
     nm, nb = parse(sys.argv[2])
     names = sorted(pm)
-    assert names == sorted(nm), "the two files do not hold the same kernels"
+    for k in sorted(nm):                              # a trailing `false` template argument more than the parent's name
+        old = re.sub(r"Lb0EEEv", "EEv", k, count=1)
+        if k not in pm and old in pm and old not in nm:
+            nm[old], nb[old] = nm.pop(k), nb.pop(k)
+    added = sorted(set(nm) - set(pm))
+    for k in added:
+        pm[k], pb[k] = nm[k], nb[k]                   # (no parent: shown against itself)
+    names = sorted(pm)
+    assert names == sorted(nm), "a kernel of the parent is missing from the new file"
     assert len(names) == len(pb) == len(nb), "kernel names fell together after enum arguments were read as integers"
     pretty = demangle(names)
     print("kernel | vgpr | sgpr | lds | spill | scratch | instructions   (parent -> new where they differ) | MFMA / LDS / global sequence | the same with waits, barriers, branches | mnemonic diff lines")
@@ -86,12 +96,12 @@ def main():
         bad_mem += not same_mem
         bad_ord += not same_ord
         bad_spill += spills != 0
-        print(f"{pretty[k]} | " + " | ".join(cols) + f" | {'identical' if same_mem else 'DIFFERENT'} | {'identical' if same_ord else 'DIFFERENT'} | {nd}")
+        print(f"{'NEW ' if k in added else ''}{pretty[k]} | " + " | ".join(cols) + f" | {'identical' if same_mem else 'DIFFERENT'} | {'identical' if same_ord else 'DIFFERENT'} | {nd}")
         if ops:
             notes.append(f"\n{pretty[k]}")
             for _, i1, i2, j1, j2 in ops:
                 notes.append(f"  @{i1}: - {' '.join(a[i1:i2]) or '(nothing)'}\n  {' ' * len(str(i1))}   + {' '.join(b[j1:j2]) or '(nothing)'}")
-    print(f"\n{len(names)} kernels; spills or scratch in {bad_spill}; MFMA / LDS / global sequence different in {bad_mem}; with waits, barriers and branches in {bad_ord}")
+    print(f"\n{len(names)} kernels ({len(added)} only in the new file, marked NEW); spills or scratch in {bad_spill}; MFMA / LDS / global sequence different in {bad_mem}; with waits, barriers and branches in {bad_ord}")
     print("\nMnemonic-level differences (parent '-', new '+', @ = instruction index in the parent's body):" + ("" if notes else " none"))
     print("\n".join(notes))
 

@@ -116,11 +116,12 @@ struct amt_handle {
     bool l0_tables = true;               // amt_set_option("layer0_kv_from_tables"): 0 = the attention that carries the sampling head streams layer 0's keys from the cache
     bool gemm_pipe = true;               // amt_set_option("gemm_tile_pipeline"): 0 = the skinny GEMMs of the decode step run the serial tile loop (DecodeGemmParams::serial_loop)
     bool gemm_lean = true;               // amt_set_option("gemm_scalar_front"): 0 = the skinny GEMMs of the decode step keep their generic front (DecodeGemmParams::generic_front)
+    bool rows_dma = AMT_GEMM_ROWS_DMA_DEFAULT != 0;      // amt_set_option("gemm_rows_dma"): 0 = the skinny GEMMs of the decode step stage their rows through registers (DecodeGemmParams::reg_rows)
     bool scalar_stream = true;           // amt_set_option("scalar_key_stream"): 0 = the decode attentions keep the per-lane controlled key stream (AttnDecodeParams::lane_key_stream)
     bool plain_chain = false;            // amt_set_option("decode_chain_plain"), before the first amt_finalize: the 49-launch chain without folded LayerNorms
     bool gen_active = false;
     // graphs keyed by the parameters baked into the captured kernel arguments
-    struct GraphKey { int B, T, P, beam, mcN, mcC, S, nsteps, skip, pad, short_ctx, parity, gemm_pipe, spare, key_stream, gemm_front; float* logits; };      // (compared bytewise: an even number of ints, no padding)
+    struct GraphKey { int B, T, P, beam, mcN, mcC, S, nsteps, skip, pad, short_ctx, parity, gemm_pipe, spare, key_stream, gemm_front, gemm_rows, spare2; float* logits; };      // (compared bytewise: an even number of ints, no padding)
     struct GraphEntry { GraphKey key; hipGraphExec_t exec; hipGraph_t graph; };
     std::vector<GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;    // capture-only stream (the caller's may be the legacy null stream)
@@ -265,6 +266,7 @@ struct StepProf {
 int32_t launch_step_gemm(const amt_handle* h, DecodeGemmParams g, hipStream_t s) {
     g.serial_loop = h->gemm_pipe ? 0 : 1;
     g.generic_front = h->gemm_lean ? 0 : 1;
+    g.reg_rows = h->rows_dma ? -1 : 1;
     return amt_launch_decode_gemm(g, s);
 }
 
@@ -445,7 +447,7 @@ int32_t get_graph(amt_handle* h, int first_pos, int nsteps, float* logits_out, h
     // of keys, every self-attention of the graph is the short-context instantiation (a graph that straddles the limit keeps the long one)
     const bool short_ctx = h->short_attn && first_pos + nsteps <= amt_attn_decode_stride(h->hd);
     amt_handle::GraphKey key{h->genB, h->genT, h->genP, h->beam, h->mcN, h->mcC, h->encS, nsteps, h->skip_mask | (h->fuse_head ? 4 : 0), h->use_unif,
-                             short_ctx ? 1 : 0, first_pos & 1, h->gemm_pipe ? 1 : 0, h->l0_tables ? 1 : 0, h->scalar_stream ? 1 : 0, h->gemm_lean ? 1 : 0, logits_out};
+                             short_ctx ? 1 : 0, first_pos & 1, h->gemm_pipe ? 1 : 0, h->l0_tables ? 1 : 0, h->scalar_stream ? 1 : 0, h->gemm_lean ? 1 : 0, h->rows_dma ? 1 : 0, 0, logits_out};
     for (auto& g : h->graphs)
         if (memcmp(&g.key, &key, sizeof(key)) == 0) { *out = g.exec; return 0; }
     hipGraph_t graph;
@@ -756,6 +758,10 @@ extern "C" int32_t amt_set_option(amt_handle* h, const char* name, int32_t value
         amt_attn_decode_scalar_stream(value != 0);
         return 0;
     }
+    if (!h && name && strcmp(name, "gemm_rows_dma") == 0) {       // ... and of the skinny-GEMM entry points (amt_decode_gemm_ex_fwd)
+        amt_decode_gemm_rows_dma(value != 0);
+        return 0;
+    }
     AMT_CHECK_ARG(h && name, "amt_set_option: null argument");
     if (strcmp(name, "chord_embed") == 0) {
         AMT_CHECK_ARG(!h->KVx || h->chord_embed == (value != 0), "amt_set_option: chord_embed must be chosen before the first amt_finalize");
@@ -785,6 +791,10 @@ extern "C" int32_t amt_set_option(amt_handle* h, const char* name, int32_t value
     }
     if (strcmp(name, "gemm_scalar_front") == 0) {            // 0: the decode step's skinny GEMMs keep their generic front (A/B and bit-identity tests); part of the graph key
         h->gemm_lean = value != 0;
+        return 0;
+    }
+    if (strcmp(name, "gemm_rows_dma") == 0) {                // 0: the decode step's skinny GEMMs stage their rows through registers (A/B and bit-identity tests); part of the graph key
+        h->rows_dma = value != 0;
         return 0;
     }
     if (strcmp(name, "layer0_kv_from_tables") == 0) {        // 0: layer 0's self-attention always streams its keys from the K/V cache (A/B and bit-identity tests); part of the graph key

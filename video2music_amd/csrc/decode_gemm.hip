@@ -17,6 +17,7 @@
 #include <limits.h>
 #include <stdlib.h>
 
+#include <atomic>
 #include <mutex>
 
 #include "amt_common.h"
@@ -88,11 +89,12 @@ __device__ __forceinline__ float4 glu4(const float4 v, const float4 g, float um,
 // the row is full).  It takes n, not 1/n, and divides behind the first sum: a reciprocal formed by the caller is scheduled in front of
 // the sums and moves a wait of the folded-FFN prologue (profiles/r06_decode_gemm_refactor_codegen.txt).
 struct RowStats { float mean, rstd; };
-template <bool MUL, int KCH, typename F>
+// C0: the first chunk the wave holds (rows staged by LDS-DMA keep only the u half in registers: the chunks in front of it have w(c) = 0)
+template <bool MUL, int C0 = 0, int KCH, typename F>
 __device__ __forceinline__ RowStats row_stats(const float4 (&v)[KCH], F w, float n, float eps) {
     float s = 0.f;
 #pragma unroll
-    for (int c = 0; c < KCH; ++c) {
+    for (int c = C0; c < KCH; ++c) {
         if constexpr (MUL) s += w(c) * sum4(v[c]);
         else if (w(c)) s += sum4(v[c]);
     }
@@ -100,7 +102,7 @@ __device__ __forceinline__ RowStats row_stats(const float4 (&v)[KCH], F w, float
     const float mean = wave_sum(s) * inv_n;
     float q = 0.f;
 #pragma unroll
-    for (int c = 0; c < KCH; ++c) {
+    for (int c = C0; c < KCH; ++c) {
         if constexpr (MUL) q += w(c) * sq4(v[c], mean);
         else if (w(c)) q += sq4(v[c], mean);
     }
@@ -283,6 +285,37 @@ __device__ __forceinline__ float4 ld4_buf(wbuf_t r, unsigned voff, unsigned soff
     return make_float4(t.x, t.y, t.z, t.w);
 }
 
+// s_waitcnt's gfx9 immediate for vmcnt(n) alone: vmcnt in bits 3:0 (and 15:14), expcnt 6:4 and lgkmcnt 11:8 left at their maxima
+constexpr int vmcnt_imm(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0f70; }
+// A counted wait that the compiler's own wait bookkeeping follows (an asm statement's it does not see).  The s_nop takes the wait:
+// into a wait that stands directly in front of an instruction the compiler folds whatever that instruction needs by its own count,
+// and while a global_load_lds is in flight (a pending flat access to it) that is vmcnt(0) for any loaded register.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    __builtin_amdgcn_s_waitcnt(vmcnt_imm(N));
+    asm volatile("s_nop 0");
+}
+// ... and straight into LDS (gfx950 LDS-DMA, `global_load_lds_dwordx4 v_off, s[base:base+1] offset:OFF`): lane l's 16 bytes land at
+// lds + OFF + 16 l, one contiguous KiB per wave-instruction, no VGPR in between.  `lds` is wave-uniform (it travels in M0); OFF is
+// the instruction's immediate and moves source and destination alike.  The load counts on vmcnt like a register load, in issue
+// order with them; nothing but the issuing wave's own wait (and then a barrier, for the other waves) orders a ds_read behind it.
+template <int OFF>
+__device__ __forceinline__ void dma16_s(const char* sbase, unsigned lane_off, float* lds) {
+    typedef const __attribute__((address_space(1))) char* gptr;
+    __builtin_amdgcn_global_load_lds((gptr)sbase + lane_off, (__attribute__((address_space(3))) void*)lds, 16, OFF, 0);
+}
+// chunks C .. N-1 of a row by LDS-DMA: chunk c from (256 c < K1 ? xr : x2r) + 1024 c to row + 256 c (floats).  As in the register
+// front, chunks 0-3 ride in the immediate; from the fourth on 4 KiB go into the scalar base and into the LDS base
+template <int C, int N>
+__device__ __forceinline__ void dma_row_chunks(const char* xr, const char* x2r, int K1, unsigned lane_off, float* row) {
+    if constexpr (C < N) {
+        const char* side = (256 * C < K1 ? xr : x2r) + (C >= 4 ? 4096 : 0);
+        if (C >= 4) asm volatile("" : "+s"(side));
+        dma16_s<1024 * (C & 3)>(side, lane_off, row + (C >= 4 ? 1024 : 0));
+        dma_row_chunks<C + 1, N>(xr, x2r, K1, lane_off, row);
+    }
+}
+
 // PIPE: the tile loop with wave-uniform control and one tile of read-ahead; false keeps the serial loop
 // (DecodeGemmParams::serial_loop: A/B and the bit-identity tests)
 // LEAN: the scalar address front (amt_decode_gemm_lean_ok: two-source rows of whole 256-column chunks, packed weights, none of the
@@ -290,12 +323,21 @@ __device__ __forceinline__ float4 ld4_buf(wbuf_t r, unsigned voff, unsigned soff
 // arrive in one round of scalar loads (DecodeGemmFront): the row, the side of K1 a chunk lies on, the column tile's weight base and
 // the clamped tile indices are scalars, a load is a scalar base plus ONE lane offset (lane * 16 bytes).  What is loaded, and
 // everything behind the loads, is the generic kernel's.
-template <int KCH, bool FULL, Pro PRO, bool PIPE, bool LEAN = false>
+// DMA (lean front only; amt_decode_gemm_rows_dma_ok): the row chunks that nothing is done to on their way go from memory into the
+// staged row by LDS-DMA instead of through registers and a ds_write_b128 each.  Plain: all KCH chunks, the wave holds no row register
+// at all.  FoldedFfn: the raw columns below K1 (the launcher admits K1 = 2 (K - K1): the first 2/3 of the chunks); the u half stays
+// in registers for the statistics, is requested first and written by the wave itself.  The wave waits for its own DMA loads with a
+// counted vmcnt -- the weight tiles behind them stay in flight -- and the one staging barrier follows that wait.  What is staged, and
+// every arithmetic instruction, is the register path's.
+template <int KCH, bool FULL, Pro PRO, bool PIPE, bool LEAN = false, bool DMA = false>
 __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p) {
     static_assert(!LEAN || (PIPE && FULL && (PRO == Pro::Plain || PRO == Pro::FoldedFfn)), "the lean front serves the folded chain's launches");
+    static_assert(!DMA || (LEAN && (PRO == Pro::Plain || KCH % 3 == 0)), "LDS-DMA rows: the lean front, a u half of KCH / 3 chunks");
+    constexpr int DCH = !DMA ? 0 : PRO == Pro::Plain ? KCH : KCH - KCH / 3;      // row chunks 0 .. DCH-1 go by LDS-DMA, the others through v[]
     extern __shared__ __attribute__((aligned(16))) float smem[];
 #ifdef AMT_STAMPS
     unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long st_land = 0, st_lds = 0;     // this wave's row: landed (registers, or LDS by DMA) and complete in LDS
 #endif
     STAMP(0);
     constexpr bool FFN = pro_folded(PRO), LN1 = pro_layernorm(PRO);
@@ -329,12 +371,17 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
         const char* xr = reinterpret_cast<const char*>(f.x) + rc * f.x_row_bytes;
         const char* x2r = reinterpret_cast<const char*>(f.x2b) + rc * f.x2_row_bytes;
 #pragma unroll
-        for (int c = 0; c < KCH; ++c) {
+        for (int c = DCH; c < KCH; ++c) {
             // chunks 0-3 ride in the instruction's immediate offset; from the fourth on 4 KiB go into the base on the scalar unit (opaque:
             // the compiler otherwise adds them to the lane's 64-bit address)
             const char* side = (256 * c < K1 ? xr : x2r) + (c >= 4 ? 4096 : 0);
             if (c >= 4) asm volatile("" : "+s"(side));
             v[c] = ld4_s(side + 1024 * (c & 3), loff);
+        }
+        if constexpr (DMA) {
+            // (the u half's register loads in front: its statistics start while the DMA chunks land)
+            if (DCH < KCH) asm volatile("" ::: "memory");
+            dma_row_chunks<0, DCH>(xr, x2r, K1, loff, xs + wv * LD);
         }
         // rows first: the prologue's wait counts the loads behind them.  (A compiler barrier for memory operations, not a scheduling
         // boundary: behind sched_barrier(0) the epilogue's kernel arguments are requested and waited for between the rows and the weights.)
@@ -420,8 +467,15 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
     if constexpr (LEAN) {
         // ... and nothing that reads a row may rise above it (with every operand of the statistics in SGPRs early, instruction selection
         // otherwise places them, and their wait, between the row loads and the weight loads)
+        // (DMA: a global_load_lds in flight counts as a pending flat access, in front of which the compiler waits vmcnt(0) for any
+        // loaded register -- the weight tiles included.  So the waits up to the one that retires the DMA loads are spelled out, through
+        // the builtin, which its bookkeeping follows: here for the u half, the loads behind it still in flight.)
+        if constexpr (DMA && DCH < KCH) {
+            wait_vmcnt<DCH + 1 + KCH>();
+            __builtin_amdgcn_sched_barrier(0);      // (not a register copy in front of the wait either)
+        }
 #pragma unroll
-        for (int c = 0; c < KCH; ++c) asm volatile("" : "+v"(v[c].x), "+v"(v[c].y), "+v"(v[c].z), "+v"(v[c].w));
+        for (int c = DCH; c < KCH; ++c) asm volatile("" : "+v"(v[c].x), "+v"(v[c].y), "+v"(v[c].z), "+v"(v[c].w));
         asm volatile("" : "+s"(n_u));               // (the division by the u half's width as well)
     }
     STAMP(1);
@@ -438,7 +492,16 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
         // when they are read for the MFMAs -- under the shadow of the weight tiles still in flight, every element exactly once (a wave
         // owns its k range), and with ONE barrier instead of two (1.56 us of a 6.5 us launch were this prologue)
         float* gs = smem + MT * LD;                 // [2][K]: g|gamma , c|beta ; then [16][2]: mu, rstd per staged row
-        const RowStats st = row_stats<true>(v, u_half, (float)n_u, p.eps);
+        const RowStats st = row_stats<true, DCH>(v, u_half, (float)n_u, p.eps);
+        if constexpr (DMA) {
+            // the vector's float4 and, in front of it, this wave's DMA chunks; the KCH weight tiles stay in flight
+            asm volatile("" ::: "memory");
+            wait_vmcnt<KCH>();
+            asm volatile("" ::: "memory");
+#ifdef AMT_STAMPS
+            __builtin_amdgcn_sched_barrier(0); st_[6] = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0);      // (kept for st_land below; STAMP 6 overwrites it)
+#endif
+        }
         gs[2 * K + 2 * wave + (lane & 1)] = (lane & 1) ? st.rstd : st.mean;      // (every lane stores one of the two words: no branch)
         st4(gs + gs_vec * K + gs_i, gs_val);        // unconditional (surplus threads repeat the last float4): a guarded
                                                     // store lets the compiler sink the load behind the weight loads
@@ -487,17 +550,46 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
         }
     }
 #pragma unroll
-    for (int c = 0; c < KCH; ++c) {
+    for (int c = DCH; c < KCH; ++c) {
         const int i = chunk_col(c, lane);             // (the column kept in a local: through in_row() the Plain kernels take two VGPRs more)
         if (FULL || i < K) st4(xs + wave * LD + i, v[c]);    // (rows >= B hold a copy of row B-1; their outputs are never stored)
     }
     STAMP(2);
 #ifdef AMT_STAMPS
-    if (tid == 0) *reinterpret_cast<unsigned long long*>(red + NW * 256) = 0;      // the matrix phase's end stamp (below)
+    // the matrix phase's end stamp, and the latest "row landed" and "row complete in LDS" stamps of the 16 waves (all below)
+    if (tid < 3) reinterpret_cast<unsigned long long*>(red + NW * 256)[tid] = 0;
+    st_land = st_[1];                               // (lean front: the pins in front of STAMP 1 wait for the row registers)
 #endif
-    __syncthreads();
+    if constexpr (DMA) {
+        // This wave's DMA chunks are in LDS once at most the loads requested behind them are outstanding: the KCH weight tiles.
+        // __syncthreads() would wait vmcnt(0) for the fence in front of it, so the wait is spelled out, then the LDS writes of this
+        // wave, then the bare barrier.  Through the builtin the compiler's wait bookkeeping sees the DMA loads retired: left to an asm
+        // statement it waits vmcnt(0) -- weight tiles and epilogue operands -- in front of the first ds_read behind the barrier.
+        asm volatile("" ::: "memory");
+        if constexpr (!FFN) wait_vmcnt<KCH>();                      // (FoldedFfn: waited for in front of the vectors' LDS writes)
+#ifdef AMT_STAMPS
+        if (FFN) st_land = st_[6];
+        else { __builtin_amdgcn_sched_barrier(0); st_land = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0); }
+#endif
+        __builtin_amdgcn_s_waitcnt(0xc07f);                         // lgkmcnt(0)
+#ifdef AMT_STAMPS
+        __builtin_amdgcn_sched_barrier(0); st_lds = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0);
+#endif
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    } else {
+#ifdef AMT_STAMPS
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0); st_lds = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0);
+#endif
+        __syncthreads();
+    }
     STAMP(3);
 #ifdef AMT_STAMPS
+    if (lane == 0) {
+        atomicMax(reinterpret_cast<unsigned long long*>(red + NW * 256) + 1, st_land);
+        atomicMax(reinterpret_cast<unsigned long long*>(red + NW * 256) + 2, st_lds);
+    }
     __builtin_amdgcn_sched_barrier(0);
     const unsigned long long clk3 = __builtin_amdgcn_s_memtime();                  // shader-clock counter, against the 100 MHz stamps
     __builtin_amdgcn_sched_barrier(0);
@@ -594,6 +686,7 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
         const unsigned long long clk5 = __builtin_amdgcn_s_memtime();
         __builtin_amdgcn_sched_barrier(0);
         st_[7] = ((*wg_end - st_[3]) << 32) | ((clk5 - clk3) & 0xffffffffull);
+        st_land = wg_end[1]; st_lds = wg_end[2];
     }
 #endif
     float val = 0.f;
@@ -636,6 +729,10 @@ __global__ __launch_bounds__(NW * 64) void decode_gemm_kernel(DecodeGemmParams p
     if (p.stamps && tid == 0) {
         unsigned long long* o = p.stamps + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8;
         for (int i = 0; i < 8; ++i) o[i] = st_[i];
+        if (p.stamps_rows) {
+            unsigned long long* r = p.stamps_rows + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+            r[0] = st_land; r[1] = st_lds;
+        }
     }
 #endif
 }
@@ -662,10 +759,10 @@ int32_t allow_big_lds() {
     return 0;
 }
 
-template <int KCH, bool FULL, Pro PRO, bool PIPE, bool LEAN = false>
+template <int KCH, bool FULL, Pro PRO, bool PIPE, bool LEAN = false, bool DMA = false>
 int32_t launch_one_loop(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
-    if (int32_t rc = allow_big_lds<decode_gemm_kernel<KCH, FULL, PRO, PIPE, LEAN>>()) return rc;
-    hipLaunchKernelGGL((decode_gemm_kernel<KCH, FULL, PRO, PIPE, LEAN>), dim3(cdiv(p.N, 16), cdiv(p.B, MT), p.n_groups > 1 ? p.n_groups : 1), dim3(NW * 64), lds, stream, p);
+    if (int32_t rc = allow_big_lds<decode_gemm_kernel<KCH, FULL, PRO, PIPE, LEAN, DMA>>()) return rc;
+    hipLaunchKernelGGL((decode_gemm_kernel<KCH, FULL, PRO, PIPE, LEAN, DMA>), dim3(cdiv(p.N, 16), cdiv(p.B, MT), p.n_groups > 1 ? p.n_groups : 1), dim3(NW * 64), lds, stream, p);
     AMT_LAUNCH_CHECK();
     return 0;
 }
@@ -694,6 +791,9 @@ int32_t launch_one(const DecodeGemmParams& p, size_t lds, hipStream_t stream) {
             if (amt_decode_gemm_lean_ok(p)) {
                 DecodeGemmParams q = p;
                 q.front = lean_front(p);
+                if constexpr (PRO == Pro::Plain || KCH % 3 == 0) {
+                    if (amt_decode_gemm_rows_dma_ok(p)) return launch_one_loop<KCH, FULL, PRO, true, true, true>(q, lds, stream);
+                }
                 return launch_one_loop<KCH, FULL, PRO, true, true>(q, lds, stream);
             }
         }
@@ -986,6 +1086,18 @@ bool amt_decode_gemm_lean_ok(const DecodeGemmParams& p) {
     return true;
 }
 
+// Rows by LDS-DMA: what the lean front already asks for (whole 256-column chunks, 32-bit offsets, 16-byte aligned rows: ldx and
+// ldx2 are multiples of four floats) and, behind the folded-FFN prologue, a u half of exactly a third of the chunks (dff = 2 d_model:
+// K1 = 2 (K - K1)), which is what the kernel's instantiations keep in registers.  reg_rows 1 keeps the registers, 0 follows the
+// process-wide default, -1 takes the DMA form whatever that says.
+static std::atomic<int> g_rows_dma{AMT_GEMM_ROWS_DMA_DEFAULT};
+void amt_decode_gemm_rows_dma(int on) { g_rows_dma.store(on ? 1 : 0, std::memory_order_relaxed); }
+bool amt_decode_gemm_rows_dma_ok(const DecodeGemmParams& p) {
+    if (p.reg_rows > 0 || (p.reg_rows == 0 && g_rows_dma.load(std::memory_order_relaxed) == 0) || !amt_decode_gemm_lean_ok(p)) return false;
+    if (((uintptr_t)p.x | (uintptr_t)p.x2) % 16 != 0) return false;
+    return p.pro == 0 || p.K1 == 2 * (p.K - p.K1);
+}
+
 int32_t amt_launch_pack_weight(const float* W, float* P, int N, int K, hipStream_t stream, int ldw) {
     AMT_CHECK_ARG(K % 16 == 0 && (ldw == 0 || (ldw >= K && ldw % 4 == 0)), "pack_weight: K=%d must be a multiple of 16 (ldw=%d)", K, ldw);
     const int tiles = cdiv(N, 16) * (K / 16);
@@ -1066,7 +1178,7 @@ int32_t amt_launch_decode_gemm(const DecodeGemmParams& p_in, hipStream_t stream)
     const size_t lds = (size_t)MT * (p.K + XPAD) * sizeof(float) + (p.pro == 1 ? (size_t)(2 * p.K + 2 * MT) * sizeof(float) : 0) +
                        (p.pro == 2 ? (size_t)(2 * p.K + 2 * p.K1) * sizeof(float) : 0) + (size_t)NW * 256 * sizeof(float)
 #ifdef AMT_STAMPS
-                       + 16                          // the matrix phase's end stamp
+                       + 32                          // the matrix phase's end stamp, the rows' two
 #endif
         ;
     int32_t rc;

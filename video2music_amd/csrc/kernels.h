@@ -219,11 +219,25 @@ struct DecodeGemmParams {
     // 1: the generic front (per-lane 64-bit addresses, options decided at run time) where the launch could take the lean one
     // (amt_decode_gemm_lean_ok); serial_loop implies it.  What is loaded and summed is the same: bit-identical results
     int generic_front;
+    // 1: stage every row chunk through registers where the launch could take the LDS-DMA form (amt_decode_gemm_rows_dma_ok); 0: as the
+    // process-wide default says (amt_decode_gemm_rows_dma); -1: by LDS-DMA whatever it says (a handle's own option).  Only the data
+    // path differs: bit-identical results
+    int reg_rows;
+    // diagnostic builds only (-DAMT_STAMPS): [workgroup][2], the latest stamp over the workgroup's 16 waves of "this wave's row has landed"
+    // (lean front: in registers; by LDS-DMA: in LDS) and of "this wave's row is complete in LDS"; null and unused in the library build
+    unsigned long long* stamps_rows;
 };
 int32_t amt_launch_decode_gemm(const DecodeGemmParams& p, hipStream_t stream);
 // The launcher's rule for the lean front (decode_gemm.hip), evaluated on the host on the parameters alone: does this launch take
 // the LEAN instantiation of decode_gemm_kernel?
 bool amt_decode_gemm_lean_ok(const DecodeGemmParams& p);
+// ... and does it stage its rows by LDS-DMA (the DMA instantiation of the lean front)?  The lean rule, reg_rows, the process-wide
+// default below, and behind the folded-FFN prologue K1 = 2 (K - K1)
+bool amt_decode_gemm_rows_dma_ok(const DecodeGemmParams& p);
+// what launches whose reg_rows is 0 do: 1 = rows by LDS-DMA where the rule admits it, 0 = through registers; initially
+// AMT_GEMM_ROWS_DMA_DEFAULT, as a handle's "gemm_rows_dma"
+#define AMT_GEMM_ROWS_DMA_DEFAULT 1
+void amt_decode_gemm_rows_dma(int on);
 // allocates the per-device zero words (hipMalloc): call once outside any stream capture
 int32_t amt_decode_gemm_init();
 

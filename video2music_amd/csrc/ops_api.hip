@@ -215,16 +215,17 @@ extern "C" int32_t amt_attn_decode_fold_fwd(const float* raw, int32_t ldq, float
 
 // the launch amt_decode_gemm_ex_fwd makes of an argument block (the weights as packed into the scratch buffers)
 static int32_t decode_gemm_ex_params(const amt_decode_gemm_args* a, const char* who, DecodeGemmParams* out) {
-    constexpr int32_t LOOP_BITS = AMT_GEMM_PRO_SERIAL_LOOP | AMT_GEMM_PRO_GENERIC_FRONT;
+    constexpr int32_t LOOP_BITS = AMT_GEMM_PRO_SERIAL_LOOP | AMT_GEMM_PRO_GENERIC_FRONT | AMT_GEMM_PRO_REG_ROWS;
     AMT_CHECK_ARG(a, "%s: null argument block", who);
     AMT_CHECK_ARG(a->x && a->w_low && a->y_low && a->scratch_low && a->n_low > 0 && a->n_low % 16 == 0, "%s: bad low part", who);
     AMT_CHECK_ARG(a->n_high == 0 || (a->w_high && a->y_high && a->scratch_high && a->x2), "%s: incomplete high part", who);
-    AMT_CHECK_ARG((a->pro & ~LOOP_BITS) == 0 || (a->pro & ~LOOP_BITS) == 1, "%s: pro takes 0 or 1 (| AMT_GEMM_PRO_SERIAL_LOOP | AMT_GEMM_PRO_GENERIC_FRONT)", who);
+    AMT_CHECK_ARG((a->pro & ~LOOP_BITS) == 0 || (a->pro & ~LOOP_BITS) == 1, "%s: pro takes 0 or 1 (| AMT_GEMM_PRO_SERIAL_LOOP | AMT_GEMM_PRO_GENERIC_FRONT | AMT_GEMM_PRO_REG_ROWS)", who);
     DecodeGemmParams g{};
     g.B = a->B; g.eps = a->eps; g.scale = 1.f; g.x = a->x; g.ldx = a->ldx; g.x2 = a->x2; g.ldx2 = a->ldx2; g.K1 = a->K1; g.K = a->K;
     g.Wp = a->scratch_low; g.bias = a->bias_low; g.resid = a->resid; g.ldr = a->n_low; g.relu = a->relu; g.y = a->y_low; g.ldy = a->n_low;
     g.serial_loop = (a->pro & AMT_GEMM_PRO_SERIAL_LOOP) ? 1 : 0;
     g.generic_front = (a->pro & AMT_GEMM_PRO_GENERIC_FRONT) ? 1 : 0;
+    g.reg_rows = (a->pro & AMT_GEMM_PRO_REG_ROWS) ? 1 : 0;
     g.pro = a->pro & ~LOOP_BITS; g.fold_g = a->fold_g; g.fold_c = a->fold_c; g.ln_w = a->ln_w; g.ln_b = a->ln_b;
     g.N = a->n_low + a->n_high;
     if (a->x2) { g.n_split = a->n_low; g.Wp2 = a->scratch_high; g.bias2 = a->bias_high; g.y2 = a->y_high; g.ldy2 = a->n_high; }
